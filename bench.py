@@ -29,7 +29,14 @@ Other modes (not the headline line):
   --config c1 / c2 / c2nm / c3deep   the other BASELINE.json configs (and C3
                 with 10 % of the topics 33-64 levels deep), topic-sharded
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3]
+A plain run sets up, warms up, times --steps steps and prints the headline
+line.  --full then also runs everything else measured or checked beside the
+headline (isolated-walk roofline, the other output form, host-side latency,
+concurrent-caller, host-fed and route-write legs, oracle parity sample, CPU
+baseline) and adds it to the line.  --dump-outputs DIR writes the last timed
+step's hit lists as .npy files (dump_outputs).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--full] [--dump-outputs DIR]
        torchrun ... bench.py --gpus N  (one rank per GPU)
 """
 from __future__ import annotations
@@ -136,7 +143,55 @@ def parse():
     p.add_argument("--small-kernel", default="auto", choices=["auto", "wave", "wave8"],
                    help="the one-launch kernel of batches <= 65536 topics (latency and concurrent-caller legs): "
                         "the library's default, k_walk_small with 16 or 8 lanes per topic (TM_DEBUG_SMALL_KERNEL)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline's timed steps also run every other measurement and check: the profiled "
+                        "repeat and the isolated walk (roofline), the other output form, the host-side latency, "
+                        "concurrent-caller, host-fed, replica and route-write legs, the oracle parity sample and the "
+                        "CPU baseline.  Without it the run sets up, warms up, times the steps and prints the headline "
+                        "line, and the options of those legs have no effect")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the hit lists the last timed step produced as DIR/<name>.npy (dump_outputs)")
     return p.parse_args()
+
+
+DUMP_SEED = 0x454D5158
+DUMP_TOPICS = 1_000_000   # at most 8 + 8 + 4 MB of topics, counts and error flags
+DUMP_VALUES = 4_000_000   # and 32 MB of values
+
+
+def dump_outputs(dirname, parts, total, suffix=""):
+    """--dump-outputs: what a caller of the timed path received from the last
+    timed step, in a form that does not depend on where the kernels put each
+    list (the pairs form reserves its spans in launch order): for a fixed,
+    seeded sample of the step's topics, ascending, `topics.npy` (their index
+    in the batch), `counts.npy` (hits of each), `values.npy` (their lists
+    back to back, each in the order the call returned it) and `err.npy`
+    (their error flags); `total_hits.npy` is the whole step's hit count.
+    float64 (exact for u32), err float32.  `parts`: the step's consecutive
+    topic ranges as (starts, counts, values, err) device tensors."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    counts = torch.cat([c for _, c, _, _ in parts]).cpu().numpy().astype(np.int64)
+    n = counts.size
+    pick = np.random.default_rng(DUMP_SEED).permutation(n)[:DUMP_TOPICS]
+    keep = int(np.searchsorted(np.cumsum(counts[pick]), DUMP_VALUES, side="right"))
+    idx = np.sort(pick[:keep])
+    vals, errs, lo = [], [], 0
+    for starts, cnt, v, err in parts:
+        m = cnt.numel()
+        sel = torch.from_numpy(idx[(idx >= lo) & (idx < lo + m)] - lo).to(v.device)
+        c = cnt[sel].to(torch.int64)
+        first = torch.cumsum(c, 0) - c
+        pos = torch.repeat_interleave(starts[sel].to(torch.int64) - first, c) + \
+            torch.arange(int(c.sum().item()), device=v.device)
+        vals.append(v[pos].cpu().numpy().view(np.uint32))
+        errs.append(err[sel].cpu().numpy())
+        lo += m
+    for name, arr in (("topics", idx.astype(np.float64)), ("counts", counts[idx].astype(np.float64)),
+                      ("values", np.concatenate(vals).astype(np.float64)),
+                      ("err", np.concatenate(errs).astype(np.float32)),
+                      ("total_hits", np.array([total], np.float64))):
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), arr)
 
 
 def host_cpus():
@@ -389,6 +444,96 @@ def main():
     gc.enable()
     if world > 1:
         dist.barrier()
+    if xch is not None:   # the on-device high-water mark: did any timed batch overflow the capacity?
+        assert xch.check(), "filter-sharded exchange capacity overflowed during the timed steps"
+    last_k = kstep[0] - 1
+    last_batch = last_k % R
+    # the last timed step's CSR(s): (first topic, topics, output set) per sub-batch
+    last_parts = ([(lo, n, outs[j]) for j, (lo, n) in enumerate(parts)] if split > 1
+                  else [(0, B, outs[last_k % nstreams])])
+    last_hits = 0
+    for lo, n, o in last_parts:
+        h = total_of(o, n)
+        assert h <= cap
+        if pairs_out:   # the extent: no value dropped
+            assert (int(o["hit"][n].item()) >> 32) <= cap
+        last_hits += h
+    merged_total = int(merged[0][-1].item()) if merged is not None else None
+    merged_topics = merged[0].numel() - 1 if merged is not None else None
+    el_t = torch.tensor([el], dtype=torch.float64, device=cdev)
+    if world > 1:
+        dist.all_reduce(el_t, op=dist.ReduceOp.MAX)
+    el_max = float(el_t.item())
+    # whole-job topics/s: topic-sharded = every rank's own batch; filter-sharded = the one shared batch
+    topics_per_step = B if filter_sharded else world * B
+    value = topics_per_step * a.steps / el_max
+    ms_per_step = el_max / a.steps * 1e3
+
+    if a.dump_outputs and a.steps > 0:
+        if merged is not None:   # filter-sharded: the merged CSR of this rank's slice of the batch
+            lo, hi = xch.bounds[xch.rank] if xch is not None else (0, B)
+            dparts = [(merged[0][:-1], merged[0][1:] - merged[0][:-1], merged[1], last_parts[0][2]["err"][lo:hi])]
+        elif pairs_out:
+            dparts = []
+            for _, n, o in last_parts:
+                pr = o["hit"][:n].view(torch.int32).view(n, 2).to(torch.int64) & 0xFFFFFFFF
+                dparts.append((pr[:, 0], pr[:, 1], o["out"], o["err"][:n]))
+        else:
+            dparts = [(o["hit"][:n], o["hit"][1:n + 1] - o["hit"][:n], o["out"], o["err"][:n]) for _, n, o in last_parts]
+        dump_outputs(a.dump_outputs, dparts, merged_total if merged is not None else last_hits,
+                     f".rank{rank}" if world > 1 else "")
+        del dparts
+
+    metric = {"c3": "topic matches/sec at 10M filters"}.get(a.config, f"topic matches/sec ({a.config})")
+    par = (f"filter-sharded x{world} (RCCL all_to_all of per-slice counts and hit lists, device merge)" if filter_sharded
+           else f"level-0 sharded x{world} (first-level words partitioned, '+'/'#' roots replicated; "
+                f"topics routed by first level; no data-path collective)" if level0
+           else f"topic-sharded x{world} (trie replicated)")
+    # the headline line: what the timed steps alone give (--full adds every other leg's figures to it)
+    res = {
+        "metric": metric,
+        "value": round(value, 1),
+        "unit": "topic matches/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "strong" if filter_sharded else "weak",
+        "vs_baseline": None,
+        "dtype": "u8/u32",
+        "data": "synthetic (emqx_amd/csrc/workload.cpp, seed 0x454D5158+cfg)",
+        "config": {"workload": f"{a.config}: {desc}", "filters": nf if (filter_sharded or level0) else len(fs),
+                   "topics_per_gpu_step": B, "global_batch": topics_per_step, "parallelism": par,
+                   "streams": nstreams, "sub_batches_per_step": split, "distinct_batches": R,
+                   "table_copies": copies, "outputs": a.outputs},
+        "matched_ids_per_s": round(last_hits * (1 if filter_sharded else world) * a.steps / el_max, 1),
+        "hits_per_topic": round(merged_total / max(merged_topics, 1) if merged_total is not None else last_hits / B, 3),
+        "build": {"generate_s": round(t_gen, 1), "compile_s": round(t_compile, 1), "upload_s": round(t_upload, 2),
+                  "device_MiB": round(st["device_bytes"] / 2**20, 1),
+                  "device_MiB_all_copies": round(copies * st["device_bytes"] / 2**20, 1), "nodes": st["n_nodes"],
+                  "edges": st["n_edges"], "words": st["n_words"], "keys_this_rank": st["n_keys"],
+                  "kernel_source_hash": source_hash()},
+    }
+    if dchunks:
+        res["deltas_per_step"] = a.deltas / every
+        res["delta_batch"] = {"deltas": a.deltas, "every_steps": every}
+        res["deltas_per_s"] = round(a.deltas / every * a.steps / el_max, 1)
+        res["delta_apply_host_ms_per_step"] = round(apply_s[0] / a.steps * 1e3, 4)
+    if filter_sharded:
+        res["merged_hits_this_rank_slice"] = merged_total
+        res["merged_topics_this_rank_slice"] = merged_topics
+        if xch is not None:
+            res["exchange"] = {"per_peer_capacity": xch.per_peer, "slice": xch.s,
+                               "collectives": "all_to_all_single of u32 counts + padded u32 values (RCCL)"}
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # the profiled repeat: the same steps again with the library's events
     # around each walk (the overlapped per-kernel figures), untimed
     prof_steps = 0 if (filter_sharded or split > 1 or dchunks) else a.steps
@@ -408,22 +553,6 @@ def main():
     ix.profile(False)
     kstep[0] = kstep0
     del pouts
-    if xch is not None:   # the on-device high-water mark: did any timed batch overflow the capacity?
-        assert xch.check(), "filter-sharded exchange capacity overflowed during the timed steps"
-    last_k = kstep[0] - 1
-    last_batch = last_k % R
-    # the last timed step's CSR(s): (first topic, topics, output set) per sub-batch
-    last_parts = ([(lo, n, outs[j]) for j, (lo, n) in enumerate(parts)] if split > 1
-                  else [(0, B, outs[last_k % nstreams])])
-    last_hits = 0
-    for lo, n, o in last_parts:
-        h = total_of(o, n)
-        assert h <= cap
-        if pairs_out:   # the extent: no value dropped
-            assert (int(o["hit"][n].item()) >> 32) <= cap
-        last_hits += h
-    merged_total = int(merged[0][-1].item()) if merged is not None else None
-    merged_topics = merged[0].numel() - 1 if merged is not None else None
     # The walk kernel alone: two passes over the R batches, back to back on
     # one stream (so no other kernel runs beside a walk), waited for once at
     # the end.  An event recorded on an idle stream is stamped before the
@@ -461,10 +590,6 @@ def main():
     path = max(range(3), key=lambda i: paths1[i] - paths0[i])
     kernel = "k_walk_pairs" if pairs_out else ("k_walk_fast", "k_walk_small", "k_walk_small")[path]
     one_launch = path != 0 or pairs_out   # (the kernel writes the values too)
-    el_t = torch.tensor([el], dtype=torch.float64, device=cdev)
-    if world > 1:
-        dist.all_reduce(el_t, op=dist.ReduceOp.MAX)
-    el_max = float(el_t.item())
 
     # The other output form over the same batches, streams and step count
     # (rank 0 of a one-GPU topic-sharded run): the CSR next to the pairs
@@ -499,10 +624,6 @@ def main():
                "note": "same batches, streams, warm-up and step count, timed after the headline region"}
         del aouts
 
-    # whole-job topics/s: topic-sharded = every rank's own batch; filter-sharded = the one shared batch
-    topics_per_step = B if filter_sharded else world * B
-    value = topics_per_step * a.steps / el_max
-    ms_per_step = el_max / a.steps * 1e3
     walk_avg_ms = walk_ms / max(nb, 1)
     batch_avg_ms = batch_ms / max(nb, 1)
     iso_ms = iso_walk_ms / max(iso_nb, 1)
@@ -771,28 +892,7 @@ def main():
                        "ceiling_per_s": RANDOM_REQ_CEILING, "frac": round(rate / RANDOM_REQ_CEILING, 4),
                        "source": "profiles/r1_gather.md (64-B random requests beyond L2, 256 MiB-2 GiB tables)"}
 
-    metric = {"c3": "topic matches/sec at 10M filters"}.get(a.config, f"topic matches/sec ({a.config})")
-    par = (f"filter-sharded x{world} (RCCL all_to_all of per-slice counts and hit lists, device merge)" if filter_sharded
-           else f"level-0 sharded x{world} (first-level words partitioned, '+'/'#' roots replicated; "
-                f"topics routed by first level; no data-path collective)" if level0
-           else f"topic-sharded x{world} (trie replicated)")
-    res = {
-        "metric": metric,
-        "value": round(value, 1),
-        "unit": "topic matches/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "strong" if filter_sharded else "weak",
-        "vs_baseline": None,
-        "dtype": "u8/u32",
-        "data": "synthetic (emqx_amd/csrc/workload.cpp, seed 0x454D5158+cfg)",
-        "config": {"workload": f"{a.config}: {desc}", "filters": nf if (filter_sharded or level0) else len(fs),
-                   "topics_per_gpu_step": B, "global_batch": topics_per_step, "parallelism": par,
-                   "streams": nstreams, "sub_batches_per_step": split, "distinct_batches": R,
-                   "table_copies": copies, "outputs": a.outputs},
+    res.update({
         "roofline": {"bound": "hbm", "achieved": None if achieved is None else round(achieved, 1),
                      "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": None if achieved is None else round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
@@ -825,8 +925,6 @@ def main():
                    "step_ge_isolated_walk_over_streams": bool(ms_per_step >= iso_ms / nstreams)},
         "other_outputs": alt,
         "cpu_baseline": cpu,
-        "matched_ids_per_s": round(last_hits * (1 if filter_sharded else world) * a.steps / el_max, 1),
-        "hits_per_topic": round(merged_total / max(merged_topics, 1) if merged_total is not None else last_hits / B, 3),
         "batch_device_ms": round(batch_avg_ms, 4) if nb else None,
         "batch_device_isolated_ms": round(iso_batch, 4),
         "batch_latency_host_ms": lat_pinned,
@@ -836,28 +934,12 @@ def main():
                                                     "against": "oracle over this rank's keys" + (
                                                         " (every filter that can match a topic this rank owns: "
                                                         "the unsharded answer, order included)" if level0 else "")},
-        "build": {"generate_s": round(t_gen, 1), "compile_s": round(t_compile, 1), "upload_s": round(t_upload, 2),
-                  "device_MiB": round(st["device_bytes"] / 2**20, 1),
-                  "device_MiB_all_copies": round(copies * st["device_bytes"] / 2**20, 1), "nodes": st["n_nodes"],
-                  "edges": st["n_edges"], "words": st["n_words"], "keys_this_rank": st["n_keys"],
-                  "kernel_source_hash": source_hash()},
-    }
+    })
     res.update(res_extra)
     if replicas is not None:
         res["replicas"] = replicas
     if writes is not None:
         res["route_writes"] = writes
-    if dchunks:
-        res["deltas_per_step"] = a.deltas / every
-        res["delta_batch"] = {"deltas": a.deltas, "every_steps": every}
-        res["deltas_per_s"] = round(a.deltas / every * a.steps / el_max, 1)
-        res["delta_apply_host_ms_per_step"] = round(apply_s[0] / a.steps * 1e3, 4)
-    if filter_sharded:
-        res["merged_hits_this_rank_slice"] = merged_total
-        res["merged_topics_this_rank_slice"] = merged_topics
-        if xch is not None:
-            res["exchange"] = {"per_peer_capacity": xch.per_peer, "slice": xch.s,
-                               "collectives": "all_to_all_single of u32 counts + padded u32 values (RCCL)"}
     if cpu:
         res["speedup_vs_cpu"] = round(value / cpu["value"], 1)
     if not res["checks"]["step_ge_isolated_walk_over_streams"]:

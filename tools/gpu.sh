@@ -7,9 +7,10 @@
 #   smoke                     __graft_entry__.smoke()
 #   tests[:<pytest -k expr>]  pytest -m gpu (verbose, per-test timeout; '+' in the
 #                             expression stands for a space)
-#   bench[:<name>:<args>]     bench.py <args> -> <name>.json (args: comma separated)
+#   bench[:<name>:<args>]     bench.py <args> -> <name>.json (args: comma separated;
+#                             --full for every leg beside the headline)
 #   prof[:<profile_walk args>]  rocprofv3 --kernel-trace --stats over bench.py
-#                             defaults + tools/profile_walk.py, then the PMC
+#                             --full + tools/profile_walk.py, then the PMC
 #                             passes (one rocprofv3 --pmc run per group)
 #   walk[:<args>]             tools/profile_walk.py <args> (isolated walk timing)
 #   py:<name>:<script args>   python3 -u <script args> -> <name>.txt
@@ -52,7 +53,7 @@ for step in "$@"; do
     prof)
       mkdir -p "$OUT/prof"
       timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$OUT/prof/bench" -o run --output-format csv -- \
-        python3 -u bench.py > "$OUT/prof/bench.json" 2> "$OUT/prof/bench.err"
+        python3 -u bench.py --full > "$OUT/prof/bench.json" 2> "$OUT/prof/bench.err"
       gzip -f "$OUT/prof/bench/run_kernel_trace.csv"
       timeout -k 10 200 python3 -u tools/profile_walk.py ${rest//,/ } > "$OUT/prof/timing.txt" 2>&1
       timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$OUT/prof/trace" -o run --output-format csv -- \

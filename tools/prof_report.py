@@ -19,7 +19,7 @@ scattered 16-B and 64-B reads FETCH_SIZE counts exactly 64 B per memory-side
 request, so the value is taken as is (no x2).
 It also counts Infinity-Cache (MALL) hits, so it is an upper bound on HBM.
 
-The bench run's kernel trace is split by phase: its last 2 x rotate
+The bench run's (bench.py --full) kernel trace is split by phase: its last 2 x rotate
 full-grid launches of the main kernel (k_walk_small for a one-launch batch,
 else k_walk_fast) are the isolated pass bench.py times for
 roofline.kernel_avg_ms (one stream, back to back), the launches before them
@@ -127,7 +127,7 @@ def main(prof, rnd, tag, config, filters, batch, rotate=4, batches=8):
         lines += ["## bench.py line (run under rocprofv3 --kernel-trace --stats)", "", "```",
                   open(bench_json).read().strip(), "```", ""]
     durations = {}
-    for sub, title in (("bench", "bench.py with its defaults (includes the 4k/64k latency batches and the isolated walk batches)"),
+    for sub, title in (("bench", "bench.py --full with its defaults (includes the 4k/64k latency batches and the isolated walk batches)"),
                        ("trace", "tools/profile_walk.py (full batches only)")):
         p = os.path.join(prof, sub, "run_kernel_trace.csv")
         if not (os.path.isfile(p) or os.path.isfile(p + ".gz")):
