@@ -25,6 +25,7 @@
 // Integer/byte work only; the path is HBM-latency bound, so the
 // design goal is many independent loads in flight per CU, not MFMA.
 #include "tm_dev.h"
+#include "tm_scan.h"
 
 // The tail kernels' last-block ticket (k_walk_tail, reset_lists_if_last) and
 // k_walk_small's look-back read totals other blocks published with relaxed
@@ -352,12 +353,6 @@ __device__ int tokenize(const DevIndex &ix, const Src &src, uint64_t beg, uint64
                         uint32_t &L, bool &dollar, uint64_t &xh, bool &all_found) {
     uint64_t longmask = 0;   // levels resolved before the deferred probes
     all_found = true; dollar = false; xh = FNV_OFF;
-    const uint64_t p0 = beg & ~15ull;
-    // aligned 16-byte loads (the first two issued together): a chunk shares its 16-byte granule with a valid
-    // byte, so it never crosses a page the caller does not own
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    const uint4 c0 = p0 < end ? src.ld16(p0) : z;
-    const uint4 c1 = p0 + 16 < end ? src.ld16(p0 + 16) : z;
     if constexpr (S::deferred) {
         // The scan keeps only (first 8 bytes, length) per word and parks them in
         // the level's LDS slots when a '/' ends it; the checks (badarg, depth,
@@ -370,59 +365,19 @@ __device__ int tokenize(const DevIndex &ix, const Src &src, uint64_t beg, uint64
         // or all of them when a binary key of L levels exists -- so a 64-level
         // topic against a 6-level trie stays on the LDS path (need_levels).
         constexpr bool NEED = S::need;
-        uint32_t lev = 0, len = 0, b0 = 0, b1 = 0;
-        uint64_t ws = beg;
-        bool bad = false;   // tail store: a level past the stored ones is exactly '+' or '#'
-        auto park = [&]() {
-            if (lev < S::maxl) {
-                if (len <= VINL) st.put_word(lev, b0, b1, len);
-                else st.put_word(lev, len, (uint32_t)(ws - beg), 255);
-            } else if constexpr (NEED) {
-                bad |= len == 1 && ((b0 & 0xFFu) == '+' || (b0 & 0xFFu) == '#');
-            }
-            lev++;
-        };
-        uint32_t ci = 0;
-        uint64_t p = p0;
-        uint4 ra = c0, rb = c1;   // tail store: chunks loaded two ahead (deep topics run hundreds of bytes)
-        for (; p < end; p += 16, ci++) {
-            if (!NEED && lev > S::maxl) break;   // deeper than the main walk's store
-            uint4 v;
-            if constexpr (NEED) {
-                v = ra; ra = rb;
-                rb = p + 32 < end ? src.ld16(p + 32) : z;
-            } else {
-                v = ci == 0 ? c0 : ci == 1 ? c1 : src.ld16(p);
-            }
-            const uint32_t k0 = p < beg ? (uint32_t)(beg - p) : 0;
-            const uint32_t k1 = end - p < 16 ? (uint32_t)(end - p) : 16;
-#pragma unroll
-            for (uint32_t k = 0; k < 16; k++) {
-                if (k < k0 || k >= k1) continue;
-                const uint32_t word = k < 4 ? v.x : k < 8 ? v.y : k < 12 ? v.z : v.w;
-                const uint32_t c = (word >> ((k & 3) * 8)) & 0xFFu;
-                if (c == '/') {
-                    park();
-                    len = 0; b0 = 0; b1 = 0; ws = p + k + 1;
-                } else {
-                    const uint32_t sh = (len & 3) * 8;
-                    b0 |= len < 4 ? c << sh : 0u;
-                    b1 |= len - 4 < 4 ? c << sh : 0u;
-                    len++;
-                }
-            }
-        }
-        if (!NEED && p < end) {   // left early: hand the topic over to the tail lists
+        const ScanOut sc = scan_levels<NEED>(src, beg, end, st);   // (tm_scan.h)
+        const uint32_t lev = sc.lev;
+        bool bad = sc.bad;   // tail store: a level past the stored ones is exactly '+' or '#'
+        if (sc.early) {   // left early: hand the topic over to the tail lists
             // The level count only picks the tail list.  With no binary key
             // deeper than this store and a trie the LDS tail resolves, every
             // count from here on picks the LDS list (need_levels <= depth), so
             // the rest is not scanned: a long topic made its whole wave wait
             const bool any = ix.xlen_max <= S::maxl && ix.depth + 2 <= (uint32_t)MID_L &&
                              end - beg < (uint64_t)MAX_LEVELS;
-            L = any ? lev + 1 : lev + 1 + count_slashes(src, p, end);
+            L = any ? lev + 1 : lev + 1 + count_slashes(src, sc.p, end);
             return RC_DEEP;
         }
-        park();
         if (lev > (NEED ? MAX_LEVELS : S::maxl)) { L = lev; return RC_DEEP; }   // (> MAX_LEVELS: the global walk flags it)
         L = lev;
         // a level exactly '+' or '#' is badarg (:374-375), at any depth: the
@@ -446,6 +401,12 @@ __device__ int tokenize(const DevIndex &ix, const Src &src, uint64_t beg, uint64
             longmask |= 1ull << l;
         }
     } else {
+        const uint64_t p0 = beg & ~15ull;
+        // aligned 16-byte loads (the first two issued together): a chunk shares its 16-byte granule with a valid
+        // byte, so it never crosses a page the caller does not own
+        const uint4 z = make_uint4(0, 0, 0, 0);
+        const uint4 c0 = p0 < end ? src.ld16(p0) : z;
+        const uint4 c1 = p0 + 16 < end ? src.ld16(p0 + 16) : z;
         WordAcc w; w.reset(beg);
         uint32_t lev = 0;
         auto finish = [&]() -> int {
@@ -505,6 +466,7 @@ __device__ int tokenize(const DevIndex &ix, const Src &src, uint64_t beg, uint64
                 pin(wid);   // consume e[k] here on every path
                 if (use[k]) {
                     if (wid == NONE - 1) {   // rare at load <= 1/2: walk the probe sequence on
+                        // (the hash again: six home slots kept across the loads spill k_walk_fast)
                         const uint32_t len = st.word_len(l);
                         const uint64_t h = word_hash_short(b0, b1, len);
                         wid = vocab_probe_short(ix, ((uint32_t)h + 1) & ix.vmask, tg[k], b0, b1);

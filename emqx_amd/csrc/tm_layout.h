@@ -161,8 +161,18 @@ TM_HD uint32_t vocab_tag(uint64_t h, uint32_t len) {
     return ((uint32_t)(h >> 32) & 0xFFFFFF00u) | (len < 255 ? len : 255);
 }
 
-// child table hash: low bits pick the slot, the high 16 bits the Bloom bits
-TM_HD uint32_t child_hash(uint32_t wid) { return (uint32_t)mix64((uint64_t)wid * 0x9e3779b97f4a7c15ull + 1); }
+// child table hash: low bits pick the slot, the high 16 bits the Bloom bits.
+// A 32-bit multiply / xor-shift finaliser (two rounds, constants of the
+// published "lowbias32" search, avalanche bias below murmur3's fmix32): wids
+// are small consecutive integers, and the walk evaluates this up to three
+// times per node step, where a 64-bit mix cost 21 vector instructions.
+TM_HD uint32_t child_hash(uint32_t wid) {
+    uint32_t x = wid + 0x9e3779b9u;   // (0 is the finaliser's fixed point)
+    x ^= x >> 16; x *= 0x7feb352du;
+    x ^= x >> 15; x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
 TM_HD uint32_t child_bit(uint32_t h) { return ((h >> 16) * 192u) >> 16; }      // 0..191, table-mode Bloom
 TM_HD uint32_t psum_bit(uint32_t h) { return ((h >> 16) * PSUM_BLOOM) >> 16; }   // 0..27, + PSUM_BQ / PSUM_BQQ
 // Bloom word j (bits 32j .. 32j+31) of a table-mode node line

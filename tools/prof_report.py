@@ -120,7 +120,6 @@ def main(prof, rnd, tag, config, filters, batch, rotate=4, batches=8):
     bench_json = os.path.join(prof, "bench.json")
     if os.path.isfile(bench_json) and os.path.getsize(bench_json):
         # the stamp names THIS tree's sources: refuse a profile of other sources
-        import json
         profiled = json.loads(open(bench_json).read().strip().splitlines()[-1])["build"]["kernel_source_hash"]
         if profiled != source_hash():
             sys.exit(f"refused: {prof} profiled kernel sources {profiled}, this tree is {source_hash()}")
