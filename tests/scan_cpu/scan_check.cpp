@@ -202,6 +202,44 @@ int main() {
         check_both<8>(buf, beg, beg + t.size());
         check_both<32>(buf, beg, beg + t.size());
     }
+    // seeded random topics over all 256 byte values (topics are arbitrary binaries: NUL, the high-bit twins
+    // 0xAF / 0xAB / 0xA3 / 0xA4 of '/', '+', '#', '$' and the neighbours 0x2E / 0x30 of '/' drawn more often)
+    const uint8_t hot[] = {0x00, 0xAF, 0xAB, 0xA3, 0xA4, 0x2E, 0x30, 0x80, 0xFF, 0x7F, '+', '#', '$'};
+    for (uint32_t it = 0; it < 60000; it++) {
+        const uint32_t n = rnd(it % 4 == 0 ? 301 : it % 4 == 1 ? 40 : 18);
+        const uint32_t slash = it % 5 == 0 ? 3 : it % 5 == 1 ? 20 : 8;   // one byte in `slash` is a '/'
+        std::string t;
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t c = rnd(slash) == 0 ? '/' : rnd(4) == 0 ? hot[rnd(sizeof hot)] : rnd(256);
+            t += (char)c;
+        }
+        const uint64_t beg = rnd(48);
+        const std::vector<uint8_t> buf = place(t, beg);
+        check_both<2>(buf, beg, beg + t.size());
+        check_both<8>(buf, beg, beg + t.size());
+        check_both<32>(buf, beg, beg + t.size());
+    }
+    // slash_mask16 against a byte loop: every pair of byte values at every pair of adjacent positions of a
+    // chunk, over backgrounds that hold no '/', only '/', and the bytes one bit away from it
+    const uint8_t bg[] = {0x00, 0x2F, 0xAF, 0x2E, 0xFF};
+    for (uint32_t g = 0; g < sizeof bg; g++)
+        for (uint32_t pos = 0; pos + 1 < 16; pos++)
+            for (uint32_t a = 0; a < 256; a++)
+                for (uint32_t b = 0; b < 256; b++) {
+                    uint8_t c[16];
+                    memset(c, bg[g], 16);
+                    c[pos] = (uint8_t)a;
+                    c[pos + 1] = (uint8_t)b;
+                    uint32_t w[4], want = 0;
+                    memcpy(w, c, 16);
+                    for (uint32_t k = 0; k < 16; k++) want |= (c[k] == '/' ? 1u : 0u) << k;
+                    const uint32_t got = slash_mask16(w[0], w[1], w[2], w[3]);
+                    g_cases++;
+                    if (got == want) continue;
+                    fprintf(stderr, "MISMATCH slash_mask16: bytes %02x %02x at %u over %02x: %04x, byte loop %04x\n", a, b, pos,
+                            bg[g], got, want);
+                    return 1;
+                }
     printf("scan ok: %llu cases\n", (unsigned long long)g_cases);
     return 0;
 }

@@ -11,6 +11,7 @@ import random
 
 import pytest
 
+from bytes_vocab import short_vocabulary
 from emqx_amd.trie_search import filter_words, get_id, key_order, make_key
 from pyoracle import Oracle, search_filter
 
@@ -71,28 +72,44 @@ def _rand_level(r):
     return ("%X" % r.randint(1, 6)).encode()
 
 
-def _rand_filter(r, n, wild, hash_last=False):
+BYTE_VOCAB = short_vocabulary()
+
+
+def _byte_level(r):
+    """a level from the full-byte-range vocabulary (bytes_vocab): NUL runs, the
+    high-bit twins of '/', '+', '#', '$', UTF-8 words, long words differing in
+    their last byte -- the ranks matches_filter compares are in byte order"""
+    c = r.random()
+    if c < 0.3:
+        return r.choice([b"", b"\0", b"\0\0", b"a", b"a\0", b"\0a", b"$", b"$\xa4", b"\xa4", b"\xaf", b"\xab", b"\xa3",
+                         b"\x2e", b"\x30", b"\x7f", b"\x80", b"\xff"])
+    return r.choice(BYTE_VOCAB)
+
+
+def _rand_filter(r, n, wild, hash_last=False, level=_rand_level):
     out = []
     for i in range(n):
         p = r.choices(["level", "+", "#"], wild)[0]
         if p == "#" and hash_last and i != n - 1:
             p = "+"
-        out.append(b"#" if p == "#" else b"+" if p == "+" else _rand_level(r))
+        out.append(b"#" if p == "#" else b"+" if p == "+" else level(r))
     return b"/".join(out)
 
 
-@pytest.mark.parametrize("seed", range(12))
-def test_matches_filter_mirror_vs_oracle(seed):
+@pytest.mark.parametrize("seed,level", [(s, _rand_level) for s in range(12)] + [(s, _byte_level) for s in range(12)],
+                         ids=[str(s) for s in range(12)] + ["bytes-%d" % s for s in range(12)])
+def test_matches_filter_mirror_vs_oracle(seed, level):
     """Random key sets (binary keys, '+'/'#' anywhere -- '#' not last included
     -- word-list keys, '$' words) and random filter queries: the mirror and the
     oracle return the same ids in the same order.  Queries are valid MQTT
     filters ('#' last only; callers such as emqx_ds_new_streams.erl:325 pass
     subscription filters): with a '#' mid-query the reference's seek goes
-    backwards ('#' < '+' in term order) and the walk never ends."""
+    backwards ('#' < '+' in term order) and the walk never ends.  The "bytes"
+    runs draw the levels from the full byte range instead of ASCII."""
     r = random.Random(0x454D5158 + 500 + seed)
-    filters = [_rand_filter(r, r.randint(1, 5), [6, 2, 1]) for _ in range(300)]
+    filters = [_rand_filter(r, r.randint(1, 5), [6, 2, 1], level=level) for _ in range(300)]
     wf = {i for i in range(len(filters)) if r.random() < 0.1}
     keys, order, o = _index(filters, wf)
     for _ in range(200):
-        q = _rand_filter(r, r.randint(1, 5), [4, 3, 1], hash_last=True)
+        q = _rand_filter(r, r.randint(1, 5), [4, 3, 1], hash_last=True, level=level)
         assert _mirror(keys, order, q) == o.matches_filter(q), q

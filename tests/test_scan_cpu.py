@@ -7,7 +7,11 @@ over the same inputs and compares level count, every stored level's
 
 * every string over {a, /, +, #, $} up to 7 bytes at all 16 start alignments;
 * seeded random topics up to 300 bytes: word lengths 0-20, up to 70 levels;
-* stores of 2, 8 and 32 levels, with and without NEED.
+* seeded random topics up to 300 bytes over all 256 byte values (NUL, the
+  high-bit twins of '/', '+', '#', '$' and the neighbours of '/' more often);
+* stores of 2, 8 and 32 levels, with and without NEED;
+* slash_mask16 alone against a byte loop: every pair of byte values at every
+  pair of adjacent positions of a chunk.
 
 Buffers are padded to a 16-byte multiple and its byte source aborts on a load
 that is not an aligned granule holding a byte of the topic.  Built with
