@@ -22,12 +22,16 @@
 //            k_rewalk_list   topics with more than RCAP ranges are walked again
 //                            and write their values directly.
 //
+// Small batches (latency): a group of 16 or 8 lanes per topic, breadth first
+// (group_walk), in k_walk_small (the whole batch in one launch) or, on an
+// index its store cannot take, k_walk_wave as phase 1.
+//
 // Integer/byte work only; the path is HBM-latency bound, so the
 // design goal is many independent loads in flight per CU, not MFMA.
 #include "tm_dev.h"
 #include "tm_scan.h"
 
-// The tail kernels' last-block ticket (k_walk_tail, reset_lists_if_last) and
+// The tail kernels' last-block ticket (last_ticket) and
 // k_walk_small's look-back read totals other blocks published with relaxed
 // device-scope atomics, ordered only by s_waitcnt(0) before the ticket and
 // by agent-scope (sc1) loads in the reader -- no release/acquire fence, which
@@ -897,8 +901,9 @@ __global__ __launch_bounds__(WALK_BLOCK, 8) void k_walk_fast(DevIndex ix, Worksp
 
 // ------------------------------------------------------ wave per topic
 //
-// Small batches (latency).  One wavefront per topic: the lanes split the topic
-// on '/' together (ballot over 64-byte windows), look its levels up in the
+// Small batches (latency): group_walk, shared by k_walk_wave and k_walk_small.
+// One wavefront per topic: the lanes split the topic on '/' together (ballot
+// over 64-byte windows), look its levels up in the
 // vocab at once (lane l = level l), then walk the trie breadth first -- the
 // live '+'/literal frontier of a level is one state per lane, compacted into
 // LDS with ballot + prefix count, so every state of a level is one request in
@@ -939,31 +944,36 @@ struct Group {
     }
 };
 
-// W lanes per topic: W <= 31 levels (one level per lane; 2 code bits per level
-// plus the digit at level L fit 64 bits up to 31), at most W frontier states
-// and W hit ranges; anything larger goes to the lane walk's lists.
-template <int MODE, int W>
-__global__ __launch_bounds__(WV_BLOCK) void k_walk_wave(DevIndex ix, Workspace ws, uint64_t n,
-                                                        const uint8_t *blob, const uint64_t *offs, Outs o) {
-    constexpr uint32_t G = 64 / W;                        // topics per wave
+// One topic walked by a group of W lanes: at most W <= 31 levels (one per lane;
+// 2 code bits per level plus the digit at level L fit 64 bits), W frontier
+// states and HC hit ranges, which it leaves unranked in hcode / hoff / hcnt.
+// More of any, or the cut of a '#'-not-last key at the topic's last level
+// (NLIT_HDESC drops later hits: the lane walk's stores make it), and it stops
+// with `cant` set; L is valid even then.  All results are group-uniform.
+// Inlined: a call would pass the kernel's DevIndex through scratch.
+// tb: topic byte 0 -- global memory, or an LDS array plus a non-negative
+// offset (StagedSrc) -- which word starts are relative to.  `walk` false
+// (group-uniform): the group has no topic.  The two callers differ in
+//  - the bytes: k_walk_wave passes blob + beg, k_walk_small its LDS copy;
+//  - HC: W in k_walk_wave, max(W, 16) in k_walk_small (SmallShape);
+//  - PROBE_WIDE: k_walk_small probes a wide node without its bitmap line;
+//  - `cant`: k_walk_wave pushes the topic to a tail list and returns (as for
+//    t >= n, so its `walk` is constant), k_walk_small's first lane walks it;
+//  - what follows: ranking and output, k_walk_small's staging and look-back.
+struct GroupWalk { uint32_t L, nh; bool badarg, cant; };
+template <int W, uint32_t HC, bool PROBE_WIDE>
+__device__ __forceinline__ GroupWalk group_walk(const DevIndex &ix, const Group<W> &grp, const uint8_t *tb, uint64_t len,
+                                                bool walk, uint32_t *sl_, uint32_t *sn_, uint64_t *sc_,
+                                                uint64_t *hcode, uint32_t *hoff, uint32_t *hcnt) {
     constexpr uint32_t MAXL = W < 31 ? W : 31;
-    __shared__ uint32_t s_slash[WV_WAVES][64];
-    __shared__ uint32_t s_node[WV_WAVES][64];
-    __shared__ uint64_t s_code[WV_WAVES][64];
-    __shared__ uint64_t s_hcode[WV_WAVES][64];
-    __shared__ uint32_t s_hoff[WV_WAVES][64], s_hcnt[WV_WAVES][64];
-    const Group<W> grp;
-    const uint32_t wv = threadIdx.x >> 6, gl = grp.gl, base = grp.g * W;
-    const uint64_t t = ((uint64_t)blockIdx.x * WV_WAVES + wv) * G + grp.g;
-    if (t >= n) return;                       // the whole group
-    uint32_t *sl_ = s_slash[wv] + base, *sn_ = s_node[wv] + base, *hoff = s_hoff[wv] + base, *hcnt = s_hcnt[wv] + base;
-    uint64_t *sc_ = s_code[wv] + base, *hcode = s_hcode[wv] + base;
-    const uint64_t beg = offs[t], end = offs[t + 1], len = end - beg;
+    const uint32_t gl = grp.gl;
+    GroupWalk r{1, 0, false, false};
+    if (!walk) return r;
 
     // ---- topic_words/1: level boundaries by ballot over W-byte windows
     uint32_t nsl = 0;
     for (uint64_t p = 0; p < len; p += W) {
-        const bool sl = p + gl < len && blob[beg + p + gl] == '/';
+        const bool sl = p + gl < len && tb[p + gl] == '/';
         const uint64_t m = grp.ballot(sl);
         if (sl) {
             const uint32_t k = nsl + grp.rank(m);
@@ -971,27 +981,20 @@ __global__ __launch_bounds__(WV_BLOCK) void k_walk_wave(DevIndex ix, Workspace w
         }
         nsl += (uint32_t)__popcll(m);
     }
-    const uint32_t L = nsl + 1;
+    const uint32_t L = r.L = nsl + 1;
     wave_sync();
-    auto to_lists = [&]() {
-        if (gl == 0) {
-            list_push(ws, n, tail_list(ix, L), (uint32_t)t);
-        }
-    };
-    if (L > MAXL) { to_lists(); return; }
+    if (L > MAXL) { r.cant = true; return r; }
 
     // ---- this lane's level: bytes, badarg check, vocab lookup
     const bool mine = gl < L;
     const uint32_t ws0 = !mine || gl == 0 ? 0 : sl_[gl - 1] + 1;
     const uint32_t we0 = !mine ? 0 : gl == L - 1 ? (uint32_t)len : sl_[gl];
     const uint32_t wl = we0 - ws0;
-    const uint8_t *wp = blob + beg + ws0;
-    WordAcc w; w.reset(beg + ws0);
-    if (mine) for (uint32_t i = 0; i < wl; i++) w.push(wp[i]);
-    const bool bad = mine && wl == 1 && (w.b0 == '+' || w.b0 == '#');
-    const bool badarg = grp.ballot(bad) != 0;
+    WordAcc w; w.reset(ws0);
+    if (mine) for (uint32_t i = 0; i < wl; i++) w.push(tb[ws0 + i]);
+    const bool badarg = r.badarg = grp.ballot(mine && wl == 1 && (w.b0 == '+' || w.b0 == '#')) != 0;
     const bool dollar = grp.bcast(mine && wl >= 1 && (w.b0 & 0xFFu) == '$' ? 1u : 0u, 0) != 0;
-    uint32_t wid = mine && !badarg ? vocab_find(ix, w, GlobalSrc{blob}) : NONE;
+    uint32_t wid = mine && !badarg ? vocab_find(ix, w, GlobalSrc{tb}) : NONE;   // (long words: bytes from tb)
     const bool allf = grp.ballot(mine && wid == NONE) == 0;
     uint64_t xh = FNV_OFF;
     for (uint32_t l = 0; l < L; l++) xh = seq_hash_step(xh, grp.bcast(wid, l));
@@ -1003,12 +1006,11 @@ __global__ __launch_bounds__(WV_BLOCK) void k_walk_wave(DevIndex ix, Workspace w
     uint32_t nst = badarg ? 0 : 1, nh = 0;
     uint32_t node = ROOT;
     uint64_t code = 0;
-    bool ovf = false;
     auto add_hits = [&](bool h, uint64_t c, uint32_t off, uint32_t cnt) {
         const uint64_t m = grp.ballot(h);
         if (h) {
             const uint32_t k = nh + grp.rank(m);
-            if (k < W) { hcode[k] = c; hoff[k] = off; hcnt[k] = cnt; }
+            if (k < HC) { hcode[k] = c; hoff[k] = off; hcnt[k] = cnt; }
         }
         nh += (uint32_t)__popcll(m);
     };
@@ -1023,8 +1025,7 @@ __global__ __launch_bounds__(WV_BLOCK) void k_walk_wave(DevIndex ix, Workspace w
         const bool droot = dollar && l == 0;
         const uint32_t sh = 62 - 2 * l;
         if (l == L) {
-            // a '#'-not-last key's cut (NLIT_HDESC) drops later hits: the lane walk's lists make it
-            if (grp.ballot(act && (n1.y & NLIT_HDESC))) { to_lists(); return; }
+            if (grp.ballot(act && (n1.y & NLIT_HDESC))) { r.cant = true; break; }   // the cut: the lane walk makes it
             add_hits(act && n1.x, code, n0.w, n1.x);                              // exact terminal: digit 0
             add_hits(act && !droot && n0.z, code | (1ull << sh), n0.y, n0.z);     // '#' terminal: digit 1
             break;
@@ -1039,7 +1040,9 @@ __global__ __launch_bounds__(WV_BLOCK) void k_walk_wave(DevIndex ix, Workspace w
                 lit = n2.x == wl_ ? n3.x : n2.y == wl_ ? n3.y : n2.z == wl_ ? n3.z : n2.w == wl_ ? n3.w : NONE;
             } else {
                 const uint32_t h = child_hash(wl_);
-                const uint32_t mb = child_maybe(ix, n1, n2, n3, wl_, h);
+                // PROBE_WIDE: a wide node's bitmap line would be one more round trip before
+                // the probe: at a small batch's load the probe itself is cheaper
+                const uint32_t mb = PROBE_WIDE && (n1.y & NLIT_MASK) >= WIDE_LIT ? 1u : child_maybe(ix, n1, n2, n3, wl_, h);
                 if (mb & 1u) {
                     uint32_t slo, shi;
                     lit = ctab_find(ix, n2.x, n2.y, wl_, h, slo, shi);
@@ -1051,7 +1054,7 @@ __global__ __launch_bounds__(WV_BLOCK) void k_walk_wave(DevIndex ix, Workspace w
         if (plus != NONE && !child_alive(n1.z, n1.w, l + 1, L, wnext, wnext2)) plus = NONE;
         const uint64_t mp = grp.ballot(plus != NONE), ml = grp.ballot(lit != NONE);
         const uint32_t np_ = (uint32_t)__popcll(mp), nn = np_ + (uint32_t)__popcll(ml);
-        if (nn > W) { ovf = true; break; }
+        if (nn > W) { r.cant = true; break; }
         wave_sync();   // every lane has read its state before the slots are reused
         if (plus != NONE) { const uint32_t k = grp.rank(mp); sn_[k] = plus; sc_[k] = code | (1ull << sh); }
         if (lit != NONE) { const uint32_t k = np_ + grp.rank(ml); sn_[k] = lit; sc_[k] = code | (2ull << sh); }
@@ -1061,7 +1064,7 @@ __global__ __launch_bounds__(WV_BLOCK) void k_walk_wave(DevIndex ix, Workspace w
     }
 
     // ---- match_topics/4: the binary key equal to the topic, after every list key
-    if (!ovf && allf && !badarg) {
+    if (!r.cant && allf && !badarg) {
         uint32_t slot = xslot, f = xf, xoff = 0, xcnt = 0;
         const uint32_t fp = exact_fp(xh);
         for (;;) {
@@ -1079,7 +1082,33 @@ __global__ __launch_bounds__(WV_BLOCK) void k_walk_wave(DevIndex ix, Workspace w
         }
         add_hits(gl == 0 && xcnt, ~0ull, xoff, xcnt);
     }
-    if (ovf || nh > W) { to_lists(); return; }
+    r.nh = nh;
+    r.cant |= nh > HC;
+    return r;
+}
+
+template <int MODE, int W>
+__global__ __launch_bounds__(WV_BLOCK) void k_walk_wave(DevIndex ix, Workspace ws, uint64_t n,
+                                                        const uint8_t *blob, const uint64_t *offs, Outs o) {
+    constexpr uint32_t G = 64 / W;                        // topics per wave
+    __shared__ uint32_t s_slash[WV_WAVES][64];
+    __shared__ uint32_t s_node[WV_WAVES][64];
+    __shared__ uint64_t s_code[WV_WAVES][64];
+    __shared__ uint64_t s_hcode[WV_WAVES][64];
+    __shared__ uint32_t s_hoff[WV_WAVES][64], s_hcnt[WV_WAVES][64];
+    const Group<W> grp;
+    const uint32_t wv = threadIdx.x >> 6, gl = grp.gl, base = grp.g * W;
+    const uint64_t t = ((uint64_t)blockIdx.x * WV_WAVES + wv) * G + grp.g;
+    if (t >= n) return;                       // the whole group
+    uint32_t *sl_ = s_slash[wv] + base, *sn_ = s_node[wv] + base, *hoff = s_hoff[wv] + base, *hcnt = s_hcnt[wv] + base;
+    uint64_t *sc_ = s_code[wv] + base, *hcode = s_hcode[wv] + base;
+    const uint64_t beg = offs[t], end = offs[t + 1];
+    const GroupWalk gw = group_walk<W, W, false>(ix, grp, blob + beg, end - beg, true, sl_, sn_, sc_, hcode, hoff, hcnt);
+    if (gw.cant) {   // (group-uniform) the lane walk's lists take it
+        if (gl == 0) list_push(ws, n, tail_list(ix, gw.L), (uint32_t)t);
+        return;
+    }
+    const uint32_t nh = gw.nh; const bool badarg = gw.badarg;
 
     // ---- rank the hits by path code (traversal order) and write them out
     wave_sync();
@@ -1113,7 +1142,7 @@ __global__ __launch_bounds__(WV_BLOCK) void k_walk_wave(DevIndex ix, Workspace w
 // A batch of <= SMALL_TOPICS topics is latency: its walk, scan and emit as
 // separate kernels (k_walk_wave, the tail kernels, k_emit) cost ~4 launches
 // of mostly idle grids.  k_walk_small does all of it in one: each group of W
-// lanes walks its topic as k_walk_wave does; a topic the group cannot take
+// lanes walks its topic with group_walk; a topic the group cannot take
 // (deeper than the group, a frontier or hit list wider than it, a
 // '#'-not-last cut) is walked by the group's first lane with an LDS store of
 // MID_L levels (small_path_ok: the index never needs more); the block's 16
@@ -1164,7 +1193,6 @@ template <int W>
 struct SmallShape {
     static constexpr uint32_t G = 64 / W;                          // topics per wave
     static constexpr uint32_t ST = WV_WAVES * G;                   // topics per block
-    static constexpr uint32_t MAXL = W < 31 ? W : 31;              // levels a group takes
     static constexpr uint32_t HC = W < 16 ? 16 : W;                // hit ranges a group keeps
     static constexpr uint32_t TBQ = (W >= 16 ? SM_TB : SM_TB / 2) / 16 + 1;   // 16-B chunks of a topic staged
 };
@@ -1208,7 +1236,7 @@ __global__ __launch_bounds__(WV_BLOCK) void k_walk_small(DevIndex ix, Workspace 
         vb = s_tk;
     }
     using SH = SmallShape<W>;
-    constexpr uint32_t G = SH::G, ST = SH::ST, MAXL = SH::MAXL, HC = SH::HC;
+    constexpr uint32_t G = SH::G, ST = SH::ST, HC = SH::HC;
     __shared__ uint32_t s_slash[WV_WAVES][64];
     __shared__ uint32_t s_node[WV_WAVES][64];
     __shared__ uint64_t s_code[WV_WAVES][64];
@@ -1274,119 +1302,11 @@ __global__ __launch_bounds__(WV_BLOCK) void k_walk_small(DevIndex ix, Workspace 
     }
     const uint8_t *tb = span ? reinterpret_cast<const uint8_t *>(s_tb) + (live ? beg - B0 : 0)   // topic byte i = tb[i]
                              : reinterpret_cast<const uint8_t *>(s_tb + gi * TBQ) + (beg - a0);
-    const uint64_t tlen = fb ? 0 : len;
 
-    // ---- the wave walk (k_walk_wave), falling back instead of listing
-    uint32_t nsl = 0;
-    for (uint64_t p = 0; p < tlen; p += W) {
-        const bool sl = p + gl < tlen && tb[p + gl] == '/';
-        const uint64_t m = grp.ballot(sl);
-        if (sl) {
-            const uint32_t k = nsl + grp.rank(m);
-            if (k < W) sl_[k] = (uint32_t)(p + gl);
-        }
-        nsl += (uint32_t)__popcll(m);
-    }
-    const uint32_t L = nsl + 1;
-    wave_sync();
-    fb = live && (fb || L > MAXL);
-    const bool mine = live && !fb && gl < L;
-    const uint32_t ws0 = !mine || gl == 0 ? 0 : sl_[gl - 1] + 1;
-    const uint32_t we0 = !mine ? 0 : gl == L - 1 ? (uint32_t)len : sl_[gl];
-    const uint32_t wl = we0 - ws0;
-    const uint8_t *wp = tb + ws0;
-    WordAcc w; w.reset(ws0);
-    if (mine) for (uint32_t i = 0; i < wl; i++) w.push(wp[i]);
-    const bool bad = mine && wl == 1 && (w.b0 == '+' || w.b0 == '#');
-    const bool badarg = grp.ballot(bad) != 0;
-    const bool dollar = grp.bcast(mine && wl >= 1 && (w.b0 & 0xFFu) == '$' ? 1u : 0u, 0) != 0;
-    uint32_t wid = mine && !badarg ? vocab_find(ix, w, GlobalSrc{tb}) : NONE;   // (long words: bytes from LDS)
-    const bool allf = grp.ballot(mine && wid == NONE) == 0;
-    uint64_t xh = FNV_OFF;
-    for (uint32_t l = 0; l < L && !fb; l++) xh = seq_hash_step(xh, grp.bcast(wid, l));
-    xh = seq_hash_finish(xh, L);
-    const uint32_t xslot = (uint32_t)xh & ix.xmask;
-    const uint32_t xf = live && !fb && allf && !badarg ? ix.xfp[xslot] : 0;   // in flight during the walk
-
-    uint32_t nst = live && !fb && !badarg ? 1 : 0, nh = 0;
-    uint32_t node = ROOT;
-    uint64_t code = 0;
-    auto add_hits = [&](bool h, uint64_t c, uint32_t off, uint32_t cnt) {
-        const uint64_t m = grp.ballot(h);
-        if (h) {
-            const uint32_t k = nh + grp.rank(m);
-            if (k < HC) { hcode[k] = c; hoff[k] = off; hcnt[k] = cnt; }
-        }
-        nh += (uint32_t)__popcll(m);
-    };
-    for (uint32_t l = 0; nst; l++) {
-        const bool act = gl < nst;
-        uint4 n0 = make_uint4(NONE, 0, 0, 0), n1 = make_uint4(0, 0, 0, 0), n2 = n1, n3 = n1;
-        if (act) {
-            const uint4 *np = reinterpret_cast<const uint4 *>(ix.nodes + node);
-            n0 = np[0]; n1 = np[1]; n2 = np[2]; n3 = np[3];
-        }
-        pin(n0); pin(n1); pin(n2); pin(n3);
-        const bool droot = dollar && l == 0;
-        const uint32_t sh = 62 - 2 * l;
-        if (l == L) {
-            if (grp.ballot(act && (n1.y & NLIT_HDESC))) { fb = true; break; }   // the cut: the lane walk makes it
-            add_hits(act && n1.x, code, n0.w, n1.x);                              // exact terminal: digit 0
-            add_hits(act && !droot && n0.z, code | (1ull << sh), n0.y, n0.z);     // '#' terminal: digit 1
-            break;
-        }
-        add_hits(act && !droot && n0.z, code, n0.y, n0.z);                       // '#' terminal: digit 0
-        const uint32_t wl_ = grp.bcast(wid, l);
-        const uint32_t wnext = l + 1 < L ? grp.bcast(wid, l + 1) : NONE;
-        const uint32_t wnext2 = l + 2 < L ? grp.bcast(wid, l + 2) : NONE;
-        uint32_t lit = NONE;
-        if (act && wl_ != NONE) {
-            if ((n1.y & NLIT_MASK) <= KINL) {
-                lit = n2.x == wl_ ? n3.x : n2.y == wl_ ? n3.y : n2.z == wl_ ? n3.z : n2.w == wl_ ? n3.w : NONE;
-            } else {
-                const uint32_t h = child_hash(wl_);
-                // a wide node's bitmap line would be one more round trip before
-                // the probe: at a small batch's load the probe itself is cheaper
-                const uint32_t mb = (n1.y & NLIT_MASK) >= WIDE_LIT ? 1u : child_maybe(ix, n1, n2, n3, wl_, h);
-                if (mb & 1u) {
-                    uint32_t slo, shi;
-                    lit = ctab_find(ix, n2.x, n2.y, wl_, h, slo, shi);
-                    if (lit != NONE && !child_alive(slo, shi, l + 1, L, wnext, wnext2)) lit = NONE;
-                }
-            }
-        }
-        uint32_t plus = act && !droot && !(n1.y & NLIT_HDESC) ? n0.x : NONE;   // seek past '+' (dfs)
-        if (plus != NONE && !child_alive(n1.z, n1.w, l + 1, L, wnext, wnext2)) plus = NONE;
-        const uint64_t mp = grp.ballot(plus != NONE), ml = grp.ballot(lit != NONE);
-        const uint32_t np_ = (uint32_t)__popcll(mp), nn = np_ + (uint32_t)__popcll(ml);
-        if (nn > W) { fb = true; break; }
-        wave_sync();   // every lane has read its state before the slots are reused
-        if (plus != NONE) { const uint32_t k = grp.rank(mp); sn_[k] = plus; sc_[k] = code | (1ull << sh); }
-        if (lit != NONE) { const uint32_t k = np_ + grp.rank(ml); sn_[k] = lit; sc_[k] = code | (2ull << sh); }
-        wave_sync();
-        nst = nn;
-        if (gl < nst) { node = sn_[gl]; code = sc_[gl]; }
-    }
-    // ---- match_topics/4: the binary key equal to the topic, after every list key
-    if (live && !fb && allf && !badarg) {
-        uint32_t slot = xslot, f = xf, xoff = 0, xcnt = 0;
-        const uint32_t fp = exact_fp(xh);
-        for (;;) {
-            if (f == 0) break;
-            if (f == fp) {
-                const uint32_t *e = reinterpret_cast<const uint32_t *>(ix.exact + slot);
-                const bool keyok = e[0] == (uint32_t)xh && e[1] == (uint32_t)(xh >> 32) && e[2] == L;
-                if (keyok) {
-                    const uint32_t ew = !mine ? wid : L <= XINL ? e[6 + gl] : ix.wseq[e[5] + gl];
-                    if (grp.ballot(mine && ew != wid) == 0) { xoff = e[3]; xcnt = e[4]; break; }
-                }
-            }
-            slot = (slot + 1) & ix.xmask;
-            f = ix.xfp[slot];
-        }
-        add_hits(gl == 0 && xcnt, ~0ull, xoff, xcnt);
-    }
-    fb |= live && nh > HC;
+    // ---- the group's walk (group_walk), falling back instead of listing
+    const GroupWalk gw = group_walk<W, HC, true>(ix, grp, tb, len, live && !fb, sl_, sn_, sc_, hcode, hoff, hcnt);
+    fb |= gw.cant;
+    const uint32_t nh = gw.nh; const bool badarg = gw.badarg;
 
     // ---- the hits' total (every lane); their ranks by path code below
     wave_sync();
@@ -1574,24 +1494,53 @@ static uint32_t tail_blocks(const Workspace &ws, uint64_t n, int list, uint32_t 
     return b >= most ? most : (b <= MID_GRID_MIN ? (uint32_t)MID_GRID_MIN : (uint32_t)b);
 }
 
-// last block of a grid (atomic ticket) resets the list counters for the next
-// batch; hint_n != 0 (the count-mode batch's last kernel): it also leaves the
-// list lengths and hint_n in the workspace's mapped hint words (tail_blocks)
-// (no fence: a block only READ the list counters, and those loads completed
-// before its ticket was taken, so the reset cannot overtake them)
-__device__ __forceinline__ void reset_lists_if_last(const Workspace &ws, uint32_t hint_n = 0) {
+// the tail kernels' LDS-frontier block (one lane per topic, MID_L levels) and stores
+struct MidLds {
+    uint32_t wid[MID_L * MID_BLOCK];
+    uint32_t pend[(MID_L + 1) * MID_BLOCK];
+    uint8_t len[MID_L * MID_BLOCK];
+};
+__device__ __forceinline__ LdsStore<MID_L> mid_store(MidLds &m) {
+    return LdsStore<MID_L>{m.wid + threadIdx.x, m.pend + threadIdx.x, m.len + threadIdx.x, MID_BLOCK, 0};
+}
+__device__ __forceinline__ GlobalStore deep_store(const Workspace &ws, uint32_t lane) {
+    return GlobalStore{ws.deep_wid + (uint64_t)lane * MAX_LEVELS, ws.deep_stk + (uint64_t)lane * (MAX_LEVELS + 1),
+                       ws.deep_plus + (uint64_t)lane * MAX_LEVELS, 0};
+}
+
+// The grid's last block to get here takes the last ticket of `word` (zero
+// between launches: reset_lists): true in its thread 0 only.  What a block
+// wrote before -- only device-scope atomics (tile totals, reservations),
+// coherent across the XCDs -- its s_waitcnt drains before the ticket, and the
+// last block reads it with agent-scope (sc1) loads: no L2 write-back per block
+// (a __threadfence in every block: C3deep's tail 159 -> 227 us, profiles/r5/scan/).
+// What a block only READ (the list counters) completed before its ticket too.
+__device__ __forceinline__ bool last_ticket(uint32_t *word) {
+    __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t ticket = atomicAdd(&ws.list_n[L_COUNT], 1u);
-        if (ticket == gridDim.x - 1) {
-            for (int k = 0; k < L_COUNT; k++) {
-                const uint32_t len = atomicExch(&ws.list_n[k], 0u);
-                if (hint_n && ws.hint_d) ws.hint_d[k] = len;
-            }
-            if (hint_n && ws.hint_d) ws.hint_d[L_COUNT] = hint_n;
-            atomicExch(&ws.list_n[L_COUNT], 0u);
-        }
+    return threadIdx.x == 0 && atomicAdd(word, 1u) == gridDim.x - 1;
+}
+// the same, in every thread of the block (s_last: a word of its LDS)
+__device__ __forceinline__ bool last_block(uint32_t *word, uint32_t &s_last) {
+    const bool last = last_ticket(word);
+    if (threadIdx.x == 0) s_last = last;
+    __syncthreads();
+    return s_last;
+}
+
+// the last ticket's holder resets the list counters and the ticket word; n != 0 (a count-mode batch's
+// last kernel): it leaves the list lengths and n in the workspace's mapped hint words (tail_blocks)
+__device__ __forceinline__ void reset_lists(const Workspace &ws, uint32_t *ticket, uint64_t n) {
+    const uint32_t hint_n = n < 0xFFFFFFFFull ? (uint32_t)n : 0xFFFFFFFFu;
+    for (int k = 0; k < L_COUNT; k++) {
+        const uint32_t len = atomicExch(&ws.list_n[k], 0u);
+        if (hint_n && ws.hint_d) ws.hint_d[k] = len;
     }
+    if (hint_n && ws.hint_d) ws.hint_d[L_COUNT] = hint_n;
+    atomicExch(ticket, 0u);
+}
+__device__ __forceinline__ void reset_lists_if_last(const Workspace &ws, uint64_t n = 0) {
+    if (last_ticket(&ws.list_n[L_COUNT])) reset_lists(ws, &ws.list_n[L_COUNT], n);
 }
 
 // topics deeper than FAST_L: blocks < MID_GRID take the MID list (LDS frontier,
@@ -1600,14 +1549,12 @@ template <int MODE>
 __global__ __launch_bounds__(MID_BLOCK) void k_walk_tail(DevIndex ix, Workspace ws, uint64_t n,
                                                          const uint8_t *blob, const uint64_t *offs, Outs o,
                                                          uint32_t mid_grid) {
-    __shared__ uint32_t s_wid[MID_L * MID_BLOCK];
-    __shared__ uint32_t s_pend[(MID_L + 1) * MID_BLOCK];
-    __shared__ uint8_t s_len[MID_L * MID_BLOCK];
+    __shared__ MidLds s;
     uint32_t hits = 0;
     if (blockIdx.x < mid_grid) {
         const uint32_t cnt = ws.list_n[L_MID];
         const uint32_t *lst = ws.lists + (uint64_t)L_MID * n;
-        LdsStore<MID_L> st{s_wid + threadIdx.x, s_pend + threadIdx.x, s_len + threadIdx.x, MID_BLOCK, 0};
+        LdsStore<MID_L> st = mid_store(s);
         for (uint32_t i = blockIdx.x * MID_BLOCK + threadIdx.x; i < cnt; i += mid_grid * MID_BLOCK) {
             run_topic<MODE>(ix, ws, n, blob, offs, lst[i], st, o, &hits);
             if (MODE == MODE_COUNT && hits) add_tile_total(ws, lst[i], hits);
@@ -1616,8 +1563,7 @@ __global__ __launch_bounds__(MID_BLOCK) void k_walk_tail(DevIndex ix, Workspace 
         const uint32_t lane = (blockIdx.x - mid_grid) * 64 + threadIdx.x;   // < DEEP_LANES
         const uint32_t cnt = ws.list_n[L_DEEP];
         const uint32_t *lst = ws.lists + (uint64_t)L_DEEP * n;
-        GlobalStore st{ws.deep_wid + (uint64_t)lane * MAX_LEVELS, ws.deep_stk + (uint64_t)lane * (MAX_LEVELS + 1),
-                       ws.deep_plus + (uint64_t)lane * MAX_LEVELS, 0};
+        GlobalStore st = deep_store(ws, lane);
         for (uint32_t i = lane; i < cnt; i += DEEP_LANES) {
             run_topic<MODE>(ix, ws, n, blob, offs, lst[i], st, o, &hits);
             if (MODE == MODE_COUNT && hits) add_tile_total(ws, lst[i], hits);
@@ -1625,19 +1571,9 @@ __global__ __launch_bounds__(MID_BLOCK) void k_walk_tail(DevIndex ix, Workspace 
     }
     if (MODE == MODE_FIRST) reset_lists_if_last(ws);   // count mode: k_rewalk_tail resets
     if (MODE == MODE_COUNT) {
-        // the grid's last block: the superblock totals from the (now final)
-        // tile totals.  The tile totals are written only by device-scope
-        // atomics, which are performed coherently across the XCDs: each block
-        // drains its own (s_waitcnt) before its ticket, and the last block
-        // reads them with agent-scope (sc1) loads -- no L2 write-back per
-        // block (an agent-scope release, __threadfence, in every block cost
-        // C3deep's tail 68 us: 159 -> 227 us, profiles/r5/scan/).
+        // the grid's last block: the superblock totals from the now final tile totals (last_ticket)
         __shared__ uint32_t s_last;
-        __builtin_amdgcn_s_waitcnt(0);
-        __syncthreads();
-        if (threadIdx.x == 0) s_last = atomicAdd(&ws.list_n[L_COUNT + 1], 1u) == gridDim.x - 1;
-        __syncthreads();
-        if (!s_last) return;
+        if (!last_block(&ws.list_n[L_COUNT + 1], s_last)) return;
         const uint64_t nb = (n + TILE - 1) / TILE, ns = (nb + SUP - 1) / SUP;
         for (uint64_t sb = threadIdx.x; sb < ns; sb += MID_BLOCK) {   // a lane per superblock
             const uint64_t t0 = sb * SUP, t1 = t0 + SUP < nb ? t0 + SUP : nb;
@@ -1668,9 +1604,7 @@ __device__ void rewalk(const DevIndex &ix, const uint8_t *blob, const uint64_t *
 __global__ __launch_bounds__(MID_BLOCK) void k_rewalk_tail(DevIndex ix, Workspace ws, uint64_t n, const uint8_t *blob,
                                                            const uint64_t *offs, const uint64_t *hit_offs,
                                                            uint32_t *out, uint64_t cap, uint32_t mid_grid) {
-    __shared__ uint32_t s_wid[MID_L * MID_BLOCK];
-    __shared__ uint32_t s_pend[(MID_L + 1) * MID_BLOCK];
-    __shared__ uint8_t s_len[MID_L * MID_BLOCK];
+    __shared__ MidLds s;
     {   // every k_emit block has read the totals: zero them for the next batch
         const uint64_t nb = (n + TILE - 1) / TILE, ns = (nb + SUP - 1) / SUP;
         for (uint64_t i = (uint64_t)blockIdx.x * MID_BLOCK + threadIdx.x; i < nb + ns; i += (uint64_t)gridDim.x * MID_BLOCK)
@@ -1679,19 +1613,18 @@ __global__ __launch_bounds__(MID_BLOCK) void k_rewalk_tail(DevIndex ix, Workspac
     if (blockIdx.x < mid_grid) {
         const uint32_t cnt = ws.list_n[L_OVF_MID];
         const uint32_t *lst = ws.lists + (uint64_t)L_OVF_MID * n;
-        LdsStore<MID_L> st{s_wid + threadIdx.x, s_pend + threadIdx.x, s_len + threadIdx.x, MID_BLOCK, 0};
+        LdsStore<MID_L> st = mid_store(s);
         for (uint32_t i = blockIdx.x * MID_BLOCK + threadIdx.x; i < cnt; i += mid_grid * MID_BLOCK)
             rewalk(ix, blob, offs, lst[i], hit_offs, out, cap, st);
     } else {
         const uint32_t lane = (blockIdx.x - mid_grid) * 64 + threadIdx.x;
         const uint32_t cnt = ws.list_n[L_OVF_DEEP];
         const uint32_t *lst = ws.lists + (uint64_t)L_OVF_DEEP * n;
-        GlobalStore st{ws.deep_wid + (uint64_t)lane * MAX_LEVELS, ws.deep_stk + (uint64_t)lane * (MAX_LEVELS + 1),
-                       ws.deep_plus + (uint64_t)lane * MAX_LEVELS, 0};
+        GlobalStore st = deep_store(ws, lane);
         for (uint32_t i = lane; i < cnt; i += DEEP_LANES)
             rewalk(ix, blob, offs, lst[i], hit_offs, out, cap, st);
     }
-    reset_lists_if_last(ws, n < 0xFFFFFFFFull ? (uint32_t)n : 0xFFFFFFFFu);
+    reset_lists_if_last(ws, n);
 }
 
 // ------------------------------------------------------------------- emit
@@ -2107,18 +2040,13 @@ __device__ __forceinline__ void tail_pair(const DevIndex &ix, const Workspace &w
 // walk handed over, walked here from scratch) and the overflow list (span
 // reserved by the walk, values re-walked into it); the grid's last block
 // writes the total, zeroes the value counter and resets the lists
-struct MidLds {
-    uint32_t wid[MID_L * MID_BLOCK];
-    uint32_t pend[(MID_L + 1) * MID_BLOCK];
-    uint8_t len[MID_L * MID_BLOCK];
-};
 __global__ __launch_bounds__(MID_BLOCK) void k_tail_pairs(DevIndex ix, Workspace ws, uint64_t n, const uint8_t *blob,
                                                           const uint64_t *offs, uint8_t *err, uint32_t *pairs,
                                                           uint32_t *out, uint64_t cap, uint32_t mid_grid) {
     __shared__ union { MidLds w; SpanLds e; } s;
     static_assert(MID_BLOCK == 64, "one wave per tail block");
     if (blockIdx.x < mid_grid) {
-        LdsStore<MID_L> st{s.w.wid + threadIdx.x, s.w.pend + threadIdx.x, s.w.len + threadIdx.x, MID_BLOCK, 0};
+        LdsStore<MID_L> st = mid_store(s.w);
         const uint32_t cnt = ws.list_n[L_MID];
         const uint32_t *lst = ws.lists + (uint64_t)L_MID * n;
         for (uint32_t i0 = blockIdx.x * MID_BLOCK; i0 < cnt; i0 += mid_grid * MID_BLOCK) {
@@ -2135,8 +2063,7 @@ __global__ __launch_bounds__(MID_BLOCK) void k_tail_pairs(DevIndex ix, Workspace
         }
     } else {
         const uint32_t lane = (blockIdx.x - mid_grid) * 64 + threadIdx.x;   // < DEEP_LANES
-        GlobalStore st{ws.deep_wid + (uint64_t)lane * MAX_LEVELS, ws.deep_stk + (uint64_t)lane * (MAX_LEVELS + 1),
-                       ws.deep_plus + (uint64_t)lane * MAX_LEVELS, 0};
+        GlobalStore st = deep_store(ws, lane);
         const uint32_t cnt = ws.list_n[L_DEEP];
         const uint32_t *lst = ws.lists + (uint64_t)L_DEEP * n;
         for (uint32_t i0 = lane - threadIdx.x; i0 < cnt; i0 += DEEP_LANES) {
@@ -2145,13 +2072,9 @@ __global__ __launch_bounds__(MID_BLOCK) void k_tail_pairs(DevIndex ix, Workspace
         }
     }
     // the grid's last block: every block's reservations have returned (their
-    // atomics drained before its ticket), so the counter is the total
+    // atomics drained before its ticket: last_ticket), so the counter is the total
     __shared__ uint32_t s_last;
-    __builtin_amdgcn_s_waitcnt(0);
-    __syncthreads();
-    if (threadIdx.x == 0) s_last = atomicAdd(&ws.list_n[L_COUNT + 1], 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!s_last) return;
+    if (!last_block(&ws.list_n[L_COUNT + 1], s_last)) return;
     // the total (every region's successful reservations and the pool's) and
     // the extent (the end of the last value position used; past cap: values
     // were dropped), then the counters zeroed for the next batch
@@ -2178,12 +2101,7 @@ __global__ __launch_bounds__(MID_BLOCK) void k_tail_pairs(DevIndex ix, Workspace
     if (threadIdx.x) return;
     pairs[2 * n] = total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)total;
     pairs[2 * n + 1] = extent > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)extent;
-    for (int k = 0; k < L_COUNT; k++) {
-        const uint32_t len = atomicExch(&ws.list_n[k], 0u);
-        if (ws.hint_d) ws.hint_d[k] = len;
-    }
-    if (ws.hint_d) ws.hint_d[L_COUNT] = n < 0xFFFFFFFFull ? (uint32_t)n : 0xFFFFFFFFu;
-    atomicExch(&ws.list_n[L_COUNT + 1], 0u);
+    reset_lists(ws, &ws.list_n[L_COUNT + 1], n);   // (n != 0: launch_match_pairs)
 }
 
 // The LITE fallback store of k_walk_small<8> (FAST_L levels resolving only
@@ -2441,6 +2359,19 @@ static inline uint32_t blocks_for(uint64_t n, uint32_t per) { return (uint32_t)(
 
 constexpr uint32_t WV_TOPICS_PER_BLOCK = WV_WAVES * (64 / WAVE_W);
 
+// the two phases' main walk of n > 0 topics: k_walk_wave up to WAVE_TOPICS (true), else the lane walk
+template <int MODE>
+static bool launch_main_walk(const DevIndex &ix, const Workspace &ws, uint64_t n, const uint8_t *bytes,
+                             const uint64_t *offs, const Outs &o, hipStream_t s) {
+    if (n <= WAVE_TOPICS)
+        hipLaunchKernelGGL((k_walk_wave<MODE, WAVE_W>), dim3(blocks_for(n, WV_TOPICS_PER_BLOCK)), dim3(WV_BLOCK), 0, s,
+                           ix, ws, n, bytes, offs, o);
+    else
+        hipLaunchKernelGGL(k_walk_fast<MODE>, dim3(blocks_for(n, WALK_BLOCK)), dim3(WALK_BLOCK), 0, s, ix, ws, n, bytes,
+                           offs, o);
+    return n <= WAVE_TOPICS;
+}
+
 hipError_t launch_match_phase1(const DevIndex &ix, const Workspace &ws, uint64_t n, const uint8_t *bytes,
                                const uint64_t *offs, uint64_t *hit_offs, uint8_t *err, hipStream_t s,
                                hipEvent_t ev_walk0, hipEvent_t ev_walk1) {
@@ -2448,15 +2379,9 @@ hipError_t launch_match_phase1(const DevIndex &ix, const Workspace &ws, uint64_t
     Outs o{err, nullptr, nullptr};
     // tile and superblock totals are zero between batches (k_rewalk_tail
     // leaves them so): the walks add their topics' hits into them
-    const bool wave = n && n <= WAVE_TOPICS;
     if (n) {
         if (ev_walk0 && (e = hipEventRecord(ev_walk0, s)) != hipSuccess) return e;
-        if (wave)
-            hipLaunchKernelGGL((k_walk_wave<MODE_COUNT, WAVE_W>), dim3(blocks_for(n, WV_TOPICS_PER_BLOCK)),
-                               dim3(WV_BLOCK), 0, s, ix, ws, n, bytes, offs, o);
-        else
-            hipLaunchKernelGGL(k_walk_fast<MODE_COUNT>, dim3(blocks_for(n, WALK_BLOCK)), dim3(WALK_BLOCK), 0, s, ix, ws,
-                               n, bytes, offs, o);
+        const bool wave = launch_main_walk<MODE_COUNT>(ix, ws, n, bytes, offs, o, s);
         if (ev_walk1 && (e = hipEventRecord(ev_walk1, s)) != hipSuccess) return e;
         const uint32_t mg = tail_blocks(ws, n, L_MID, wave ? MID_GRID : MID_GRID_BIG);
         hipLaunchKernelGGL(k_walk_tail<MODE_COUNT>, dim3(mg + DEEP_LANES / 64), dim3(MID_BLOCK), 0, s, ix, ws, n,
@@ -2610,12 +2535,7 @@ hipError_t launch_first(const DevIndex &ix, const Workspace &ws, uint64_t n, con
                            SmallSegs{});
         return hipGetLastError();
     }
-    if (n <= WAVE_TOPICS)
-        hipLaunchKernelGGL((k_walk_wave<MODE_FIRST, WAVE_W>), dim3(blocks_for(n, WV_TOPICS_PER_BLOCK)),
-                           dim3(WV_BLOCK), 0, s, ix, ws, n, bytes, offs, o);
-    else
-        hipLaunchKernelGGL(k_walk_fast<MODE_FIRST>, dim3(blocks_for(n, WALK_BLOCK)), dim3(WALK_BLOCK), 0, s,
-                           ix, ws, n, bytes, offs, o);
+    launch_main_walk<MODE_FIRST>(ix, ws, n, bytes, offs, o, s);
     hipLaunchKernelGGL(k_walk_tail<MODE_FIRST>, dim3(MID_GRID + DEEP_LANES / 64), dim3(MID_BLOCK), 0, s, ix, ws, n, bytes, offs, o,
                        (uint32_t)MID_GRID);
     return hipGetLastError();

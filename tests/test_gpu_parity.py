@@ -2317,6 +2317,142 @@ def test_small_walks_vs_oracle_and_the_two_phase_path(torch_dev, seed):
     assert _paths(ix)[1] > p2[1]
 
 
+def _full_case(r):
+    """A few hundred filters holding at once everything the group walk
+    (group_walk: k_walk_small and k_walk_wave call it) treats specially, and
+    topics that hit and just miss each: -> filters, flags (1: binary key),
+    the topic pool (the long topics in one run: whole blocks of them)."""
+    v6 = [b"v1", b"v2", b"v3", b"v4", b"v5", b"v6"]
+    h4 = [b"h1", b"h2", b"h3", b"h4"]
+    l16 = [b"l%d" % i for i in range(1, 17)]
+    k12 = [b"k%d" % i for i in range(1, 13)]
+    longw = b"a-level-word-longer-than-16-bytes"
+    filters = [b"a/#/b", b"p/+/#/q", b"tab/+/#/c",                    # '#'-not-last keys (NLIT_HDESC), one under '+'
+               b"#", b"+/+", b"$SYS/#", b"$SYS/+/x", b"$share/g/t",   # root '#', '$'-rooted
+               b"/".join(l16), b"l1/+/l3/#", longw + b"/x", b"+/" + longw, b"a//b", b"/", b"wide//5"]
+    filters += [b"wide/%d" % i for i in range(300)]                   # a node with >= 256 literal children (WIDE_LIT)
+    filters += [b"tab/%d" % i for i in range(40)]                     # 5-255 children: table mode with its Bloom
+    for m in range(64):   # every '+' / literal variant of a 6-level prefix: 32 frontier states, 64 hit ranges
+        filters.append(b"/".join(b"+" if (m >> k) & 1 else w for k, w in enumerate(v6)))
+    for m in range(16):   # <= 16 frontier states, but 31 hit ranges ('#' terminals at every level)
+        f = [b"+" if (m >> k) & 1 else w for k, w in enumerate(h4)]
+        filters += [b"/".join(g) for g in (f, f[:-1] + [b"#"], f + [b"#"])]
+    filters = sorted(set(filters))
+    flags = [0] * len(filters)
+    keys = [b"bk/x/y", b"/".join(k12), b"wide/5", b"v1/v2/v3/v4/v5/v6"]   # binary keys of 3 and 12 (> XINL) levels
+    filters += keys
+    flags += [1] * len(keys)
+    for f in r.sample(filters[:200], 12):   # several IDs on one filter: multi-value runs
+        filters += [f] * r.randint(2, 20)
+        flags += [0] * (len(filters) - len(flags))
+    vocab = [b"a", b"b", b"c", b"p", b"q", b"x", b"y", b"bk", b"wide", b"tab", b"5", b"7", b"39", b"299", b"", b"zz",
+             b"$SYS", longw] + v6 + h4 + l16[:4] + k12[:3]
+    topics = [b"a", b"a/b", b"a/x/b", b"a/x/y/b", b"a/x", b"a/b/b", b"p/z/q", b"p/z/w/q", b"p/z", b"p", b"tab/7/c",
+              b"tab/7/y/c", b"c", b"$SYS", b"$SYS/y/x", b"$SYS/y/z", b"$share/g/t", b"$share/g", b"x", b"x/y",
+              b"wide/5", b"wide/299", b"wide/300", b"wide/tab", b"wide", b"wide//5", b"tab/7", b"tab/39", b"tab/40",
+              b"tab/wide", b"/".join(v6), b"/".join(v6[:5]), b"/".join(v6[:5] + [b"zz"]), b"/".join(v6 + [b"v7"]),
+              b"/".join(h4), b"/".join(h4[:3]), b"/".join(h4 + [b"h5"]), b"h1/zz/h3/h4",
+              b"bk/x/y", b"bk/y/x", b"bk/x", b"/".join(k12), b"/".join(k12[:10] + [b"k12", b"k11"]),
+              b"/".join(k12[:11]), b"/".join(l16), b"/".join(l16[:15] + [b"zz"]), b"/".join(l16 + [b"l17"]),
+              b"/".join([b"l1", b"zz", b"l3"] + [b"d"] * 30), b"/".join([b"d"] * 33),
+              b"", b"/", b"//", b"a//b", b"a//", b"/a",
+              b"a/+/b", b"#", b"+", b"/".join([b"d"] * 17 + [b"#", b"d"]), b"/".join([b"l1"] * 19 + [b"+"]),
+              longw + b"/x", longw + b"!/x", longw[:-1] + b"/x", b"x/" + longw,
+              b"/".join([b"w" * 60] * 5), b"wide/5/" + b"/".join([b"w" * 30] * 12)]   # > 256 bytes (SM_TB)
+    assert max(len(t) for t in topics) > 256
+    for _ in range(300):
+        topics.append(b"/".join(r.choice(vocab) for _ in range(r.choice([1, 2, 2, 3, 3, 4, 6, 6, 7, 12, 16, 17]))))
+    # two blocks' worth of topics whose byte span is beyond the staged array:
+    # ~250-byte ones (a row each, walked by their group) among ~700-byte ones
+    # (longer than a row: the group's first lane walks them)
+    for i in range(40):
+        lv = [r.choice(vocab[:14])] + [b"w" * 40] * (16 if i % 2 else 5) + [r.choice(vocab[:14])]
+        topics.append(b"/".join(lv))
+    return filters, np.array(flags, np.uint8), topics
+
+
+def _pool_batch(r, topics, n):
+    """n consecutive topics of the pool (wrapping), from a random start"""
+    s = r.randrange(len(topics))
+    return items_of([topics[(s + i) % len(topics)] for i in range(n)])
+
+
+@pytest.mark.parametrize("seed", range(3))
+def test_group_walk_kernels_agree_on_a_full_index(torch_dev, seed):
+    """k_walk_small and k_walk_wave share one group walk: on an index with
+    '#'-not-last keys, a wide node, a table-mode node, a prefix whose topic
+    outgrows a group's frontier and hit ranges, and binary keys of 3 and 12
+    levels (_full_case), batches of 1 to 3,000 topics (forced phases:
+    k_walk_wave) and 9,000 (forced phases: k_walk_fast, the cross-check) give
+    the exact CSR of the oracle and the same offsets, values and flags from
+    every kernel; after half the keys are deleted, and re-inserted, too."""
+    r = random.Random(0x454D5158 + 600 + seed)
+    filters, flags, topics = _full_case(r)
+    fs = items_of(filters)
+    ix, o = gpu_index(fs, flags), oracle_of(fs, flags)
+
+    def check(n):
+        ts = _pool_batch(r, topics, n)
+        runs = _all_kernels(ix, ts)
+        assert [tuple(x > 0 for x in p) for _, p in runs] == [(0, 1, 0), (0, 1, 0), (1, 0, 0)], [p for _, p in runs]
+        hit, vals = assert_same(ix, o, ts)
+        e0 = runs[0][0][2]
+        for (h, v, e), _ in runs:
+            assert np.array_equal(hit, h) and np.array_equal(vals, v) and np.array_equal(e0, e)
+        return hit
+
+    for n in (1, 63, 64, 65, 3_000, 9_000):
+        hit = check(n)
+    assert np.diff(hit.astype(np.int64)).max() >= 64   # the 6-level prefix's topic: every variant hits
+    dele = sorted(r.sample(range(len(filters)), len(filters) // 2))
+    d = items_of([filters[i] for i in dele], dele)
+    for ops in (np.zeros(len(dele), np.uint8), np.ones(len(dele), np.uint8)):   # deleted, then re-inserted
+        ix.apply(ops, d.blob, d.offs, d.vals, flags[dele])
+        o.apply(ops, d.blob, d.offs, d.vals, flags[dele])
+        for n in (65, 3_000):
+            check(n)
+
+
+def test_first_batch_through_every_small_kernel(torch_dev):
+    """match/2's first hit of every topic against the oracle, on the index of
+    _full_case: k_walk_small (65 and 3,000 topics); then, with a 40-level
+    binary key the one-launch store cannot take, k_walk_wave (65 and 3,000
+    topics) and k_walk_fast (9,000)."""
+    r = random.Random(0x454D5158 + 610)
+    filters, flags, topics = _full_case(r)
+    fs = items_of(filters)
+    ix, o = gpu_index(fs, flags), oracle_of(fs, flags)
+    exp = {}
+
+    def check(n):
+        ts = _pool_batch(r, topics, n)
+        val, found = ix.first_batch(ts.blob, ts.offs)
+        for i in range(n):
+            t = ts.item(i)
+            if t not in exp:
+                exp[t] = o.first(t)
+            rc, v = exp[t]
+            assert found[i] == {-1: 2, 0: 0, 1: 1}[rc], t
+            if rc == 1:
+                assert val[i] == v, t
+
+    for n in (65, 3_000):
+        check(n)
+    p0 = _paths(ix)
+    assert_same(ix, o, _pool_batch(r, topics, 65))
+    assert _paths(ix)[1] > p0[1]                      # (the one-launch path so far)
+    deep = items_of([b"/".join([b"z"] * 40)], [1_000_000])
+    ix.apply(np.ones(1, np.uint8), deep.blob, deep.offs, deep.vals, np.ones(1, np.uint8))
+    o.apply(np.ones(1, np.uint8), deep.blob, deep.offs, deep.vals, np.ones(1, np.uint8))
+    exp.clear()
+    topics = topics + [b"/".join([b"z"] * 40), b"/".join([b"z"] * 39)]
+    p0 = _paths(ix)
+    assert_same(ix, o, _pool_batch(r, topics, 65))
+    assert _paths(ix)[0] > p0[0] and _paths(ix)[1] == p0[1]   # one_launch_ok is false now: the two phases
+    for n in (65, 3_000, 9_000):
+        check(n)
+
+
 @pytest.mark.parametrize("kind", ["wave", "wave8"])
 def test_small_walk_long_topics(torch_dev, kind):
     """A block whose topics span more than k_walk_small stages in LDS at once
