@@ -27,7 +27,7 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_matches_filter", "tm_apply_deltas_ex", "tm_read_begin", "tm_read_end", "tm_epoch",
            "tm_create_replicas", "tm_replica_stats", "tm_debug_set", "tm_debug_get", "tm_match_batch32_ex",
            "tm_match_batch32_dev", "tm_matches_filter_ex", "tm_host_alloc_ex", "tm_commit",
-           "tm_match_batch32_pairs", "tm_match_batch_dev_pairs")
+           "tm_match_batch32_pairs", "tm_match_batch_dev_pairs", "tm_set_dests", "tm_fanout_dev", "tm_route_batch")
 TM_ALLOC_VRAM = 1
 TM_DEBUG_LB_SPINS, TM_DEBUG_LB_FAIL_BLOCK, TM_DEBUG_LB_LAUNCHES, TM_DEBUG_PHASES = 1, 2, 3, 4
 TM_DEBUG_FAILED_BATCHES, TM_DEBUG_RETRIED_BATCHES = 5, 6
@@ -41,6 +41,8 @@ TM_DEBUG_COMMITS, TM_DEBUG_COMMIT_WAITS, TM_DEBUG_COMMIT_FORCED = 19, 20, 21
 TM_DEBUG_SMALL_TICKET = 22
 TM_DEBUG_CMB_SPIN = 23
 TM_DEBUG_PATCH_ZC = 24
+TM_DEBUG_FANOUT_GRID = 25   # (get only) one-wave blocks of a fan-out pass
+MAX_DESTS = 65536           # tm_fanout_dev / tm_route_batch: n_dests is 1 .. MAX_DESTS
 
 
 class NativeUnavailable(RuntimeError):
@@ -119,6 +121,9 @@ def load_library(path: Path | None = None):
         "tm_match_batch32_ex": (i32, [vp, u64, vp, vp, vp, vp, u64, vp, u32, vp]),
         "tm_match_batch32_dev": (i32, [vp, u64, vp, vp, vp, vp, u64, vp, vp]),
         "tm_match_batch32_pairs": (i32, [vp, u64, vp, vp, vp, vp, u64, vp]),
+        "tm_set_dests": (i32, [vp, u64, vp, vp]),
+        "tm_fanout_dev": (i32, [vp, u64, vp, vp, u64, vp, u64, u32, vp, vp, vp, vp]),
+        "tm_route_batch": (i32, [vp, u64, vp, vp, u32, vp, vp, vp, u64, vp]),
         "tm_debug_set": (i32, [vp, u32, u64]),
         "tm_debug_get": (i32, [vp, u32, C.POINTER(u64)]),
     }
@@ -384,6 +389,50 @@ class Index:
                       d_unique: int | None = None, stream: int | None = None):
         """tm_sort_segments: sort each of n CSR segments on the device in place."""
         self._check(self._lib.tm_sort_segments(self._h, n, d_hit, d_vals, cap, order, d_unique, stream))
+
+    # ---- route fan-out (include/tmatch.h "Route fan-out")
+    def set_dests(self, values, dests):
+        """tm_set_dests: dests[i] becomes the destination id of values[i] (u32 each)."""
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        dests = np.ascontiguousarray(dests, dtype=np.uint32)
+        if len(values) != len(dests):
+            raise ValueError("set_dests: one destination per value")
+        self._check(self._lib.tm_set_dests(self._h, len(values), _ptr(values), _ptr(dests)))
+
+    def fanout_dev(self, n: int, d_hit: int, d_vals: int, cap: int, n_dests: int, d_dest_offs: int, d_out_topic: int,
+                   d_out_value: int, d_dest_of: int | None = None, dest_len: int = 0, stream: int | None = None):
+        """tm_fanout_dev on device pointers: the CSR (d_hit u64[n+1], d_vals)
+        stably partitioned by destination into d_out_topic / d_out_value, bucket
+        b at [d_dest_offs[b], d_dest_offs[b+1]) (u64[n_dests+2]; bucket n_dests:
+        unrouted).  d_dest_of None: the table of set_dests."""
+        self._check(self._lib.tm_fanout_dev(self._h, n, d_hit, d_vals, cap, d_dest_of, dest_len, n_dests, d_dest_offs,
+                                            d_out_topic, d_out_value, stream))
+
+    def route_batch(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, cap: int | None = None):
+        """tm_route_batch -> (dest_offsets u64[n_dests+2], topic u32[total],
+        values u32[total], err u8[n]): destination b's (topic index, value)
+        pairs are [dest_offsets[b], dest_offsets[b+1]), in topic order and
+        traversal order inside a topic; bucket n_dests holds the values
+        without a destination.  A cap that proves too small is retried once,
+        sized from the returned bucket sizes."""
+        n = len(offs) - 1
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        doff = np.zeros(n_dests + 2, dtype=np.uint64)
+        err = np.zeros(max(n, 1), dtype=np.uint8)
+        if cap is None:
+            cap = max(4 * n, 1024)
+        while True:
+            topic = np.empty(max(cap, 1), dtype=np.uint32)
+            vals = np.empty(max(cap, 1), dtype=np.uint32)
+            rc = self._lib.tm_route_batch(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff), _ptr(topic),
+                                          _ptr(vals), cap, _ptr(err))
+            if rc == TM_ECAP and int(doff[-1]) > cap:
+                cap = int(doff[-1])
+                continue
+            self._check(rc)
+            total = int(doff[-1])
+            return doff, topic[:total], vals[:total], err[:n]
 
     def release_stream(self, stream: int | None):
         """Drop the batch scratch the library keeps for `stream`."""

@@ -98,6 +98,47 @@ class Broker:
             out.append((agg, [self._route2(r, m) for r in agg]))
         return out
 
+    def publish_batch_by_dest(self, msgs):
+        """do_publish/1 for a micro-batch, destination-major: the routes come
+        from Router.match_routes_by_dest (matched and bucketed on the device),
+        so each destination gets ONE plan for the whole batch -- the
+        (message, To) pairs do_route2/2 (emqx_broker.erl:401-406) would
+        dispatch, forward (forward/4, :429) or hand to the shared group one
+        hit at a time.  A group's plan is deduplicated per message on
+        (To, Group), which is what aggre/1's usort does to a message's routes
+        (:412-424; node routes are unique per message as they are).
+        -> (plans, errors): plans = {destination: [(message index, To,
+        result)]}, the destination being what aggre/1 names (a node, or the
+        group); errors = {message index: exception} for invalid topics, which
+        fail alone as in publish_batch.  Every plan is in message order.
+        As in aggre/1, every ("external", X) destination goes into the one
+        plan "external"; and, as in do_route2/2, a destination is told apart
+        by its name only, so a node and a group must not share one (a class
+        is taken for a group when its first route's dest is a pair).  The
+        deliveries are the same
+        (destination, To, message) multiset as publish_batch's."""
+        if not msgs:
+            return {}, {}
+        by_dest = self.router.match_routes_by_dest([m.topic for m in msgs], errors="return")
+        self.batches += 1
+        plans: dict = {}
+        seen = set()
+        for cls, rows in by_dest.items():
+            node = not isinstance(rows[0][1].dest, tuple)
+            dest = cls[0] if isinstance(cls, tuple) else cls   # aggre/1: {Group, _Node} -> Group, whatever the pair
+            plan = plans.setdefault(dest, [])
+            for i, r in rows:
+                if not node:
+                    if (i, r.topic, dest) in seen:
+                        continue
+                    seen.add((i, r.topic, dest))
+                plan.append((i, r.topic))
+        out = {}
+        for dest, plan in plans.items():
+            plan.sort(key=lambda e: e[0])   # several classes in one plan (every ("external", X)): message order again
+            out[dest] = [(i, to) + (self._route2((to, dest), msgs[i])[2],) for i, to in plan]
+        return out, by_dest.errors
+
     # ---- asynchronous micro-batching
     def publish(self, msg) -> Future:
         """Queue one message; the future resolves to (routes, results) once its

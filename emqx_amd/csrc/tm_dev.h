@@ -191,6 +191,27 @@ hipError_t launch_sort_segments(const Workspace &ws, uint64_t n, const uint64_t 
 // out[0 .. min(hit[n], cap)) = src[...] (device -> device or mapped host memory)
 hipError_t launch_copy_values(const uint64_t *hit_offs, uint64_t n, const uint32_t *src, uint32_t *dst, uint64_t cap,
                               hipStream_t s);
+// Route fan-out (tm_fanout.hip): the CSR's (topic, value) entries at positions
+// below min(hit[n], cap), stably partitioned by bucket = dest_of[value] (bucket
+// n_dests: v >= dest_len or dest_of[v] >= n_dests) into out_topic / out_value,
+// bucket b at [dest_offsets[b], dest_offsets[b + 1]), dest_offsets[n_dests + 1]
+// the total.  A fixed grid of FO_GRID one-wave blocks; digits of up to
+// FO_MAX_BITS bits; one pass for n_dests + 1 <= 256 buckets, else two through
+// the scratch's triples (fs.cap >= min(cap, 2^32 - 1) entries then).
+constexpr int FO_GRID = 4096;
+constexpr int FO_MAX_BITS = 9;                 // 65537 buckets: 17 bits, 9 + 8
+constexpr int FO_BINS = 1 << FO_MAX_BITS;
+constexpr uint32_t FO_MAX_DESTS = 65536;
+struct FanoutScratch {
+    uint32_t *tab;        // [FO_BINS * FO_GRID] per (bin, block) counts, then their scan per bin
+    uint32_t *tot;        // [FO_BINS] the bins' totals
+    uint32_t *t, *v, *b;  // [cap] a first of two passes' (topic, value, bucket)
+    uint64_t cap;
+};
+bool fanout_two_pass(uint32_t n_dests);
+hipError_t launch_fanout(const FanoutScratch &fs, uint64_t n, const uint64_t *hit, const uint32_t *values,
+                         uint64_t cap, const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests,
+                         uint64_t *dest_offsets, uint32_t *out_topic, uint32_t *out_value, hipStream_t s);
 // delta upload: run i copies runs[i].n u32 words from data + runs[i].src to
 // word (dst & PATCH_OFF) of table (dst >> 48), whose device address on the
 // replica being patched is bases.b[table] (the same runs patch every replica)

@@ -1,0 +1,313 @@
+// tm_fanout.hip -- route fan-out on the device: a batch's topic-major hit lists
+// (the CSR tm_match_batch_dev writes) regrouped by the destination of each
+// value, for gfx950.
+//
+// emqx_broker:do_publish/1 is route(aggre(match_routes(Topic)), Delivery)
+// (apps/emqx/src/emqx_broker.erl:293-298): every hit is a route {To, Dest} and
+// do_route2/2 (:401-406) dispatches it locally, forwards it to
+// get_dest_node(Dest) (emqx_router.erl:580-585) or hands it to a shared group.
+// A batched broker wants, per destination, the (message, route) pairs that go
+// there: one forward per node per micro-batch.  That is a stable partition of
+// the flat (topic, value) list by bucket = dest_of[value]; bucket n_dests takes
+// every value without a destination (v >= dest_len, dest_of[v] >= n_dests), so
+// nothing is dropped.  The result equals numpy.argsort(bucket, kind="stable")
+// applied to (topic, value).
+//
+// The total is known only on the device and the call is asynchronous, so the
+// grid is fixed: FO_GRID one-wave blocks, block k owns the positions
+// [k * chunk, (k + 1) * chunk) with chunk = ceil(E / FO_GRID) rounded up to 64,
+// E = min(hit[n], cap), and goes through them in order.  One LSD pass over a
+// digit of `bits` bits is three launches:
+//   k_fo_hist     the block's digit histogram (LDS atomics), written bin-major
+//                 into tab[bin * FO_GRID + block] -- every block writes every
+//                 bin, so nothing of an earlier, larger run survives;
+//   k_fo_scan     one block per bin: the exclusive scan of its row in place,
+//                 the row's total into tot[bin];
+//   k_fo_scatter  base[bin] = (scan of tot)[bin] + tab[bin][block] into LDS,
+//                 then 64 entries a step: the lanes with an equal digit find
+//                 each other with one ballot per digit bit (peer mask), a
+//                 lane's slot is base[digit] + the peers below it, and the
+//                 highest peer adds the group's size to base[digit].  Stable
+//                 because blocks, steps and lanes are all in position order.
+// One pass (digit = the bucket) when n_dests + 1 <= 256 -- clusters have tens
+// of nodes --, else two: the low ceil(w / 2) bits of the w-bit bucket ids
+// first, into the stream's scratch as (topic, value, bucket) triples, then the
+// high bits from there into the outputs.  A first pass finds an entry's topic
+// from the offsets: a 64-ary search by the wave at the chunk's start, then per
+// step a window of the next 64 offsets in LDS that each lane searches; lanes
+// whose topic lies beyond the window (a run of more than 64 empty topics)
+// search again from the first of them.
+//
+// Bucket b's entries end up at [dest_offsets[b], dest_offsets[b + 1]);
+// dest_offsets[n_dests + 1] = E.  One pass: the scan of tot is that array.
+// Two passes: k_fo_bounds finds each bucket's first position in the output by
+// binary search (the output is sorted by bucket).
+// Bytes per entry and pass: 4 read twice (histogram, scatter) + 4 gathered
+// twice (dest_of) + 8 written -- (topic, value); a first of two passes writes
+// 12 and the second reads 4 + 12.
+#include <hip/hip_runtime.h>
+
+#include "tm_dev.h"
+
+namespace tmx {
+
+namespace {
+
+static_assert(FO_GRID % 256 == 0, "k_fo_scan: 256 threads share a row evenly");
+constexpr int FO_HIST_UNROLL = 4;   // steps whose loads a histogram block issues together
+
+__device__ __forceinline__ uint32_t fo_bucket(uint32_t v, const uint32_t *dest_of, uint64_t dest_len,
+                                              uint32_t n_dests) {
+    uint32_t b = n_dests;
+    if (v < dest_len) {
+        const uint32_t d = dest_of[v];
+        if (d < n_dests) b = d;
+    }
+    return b;
+}
+
+// the positions block `blk` owns: [c0, c1) of [0, E)
+__device__ __forceinline__ void fo_chunk(const uint64_t *hit, uint64_t n, uint64_t cap, uint32_t blk, uint64_t &c0,
+                                         uint64_t &c1, uint64_t &E) {
+    const uint64_t total = hit[n];
+    E = total < cap ? total : cap;
+    const uint64_t chunk = ((E + FO_GRID - 1) / FO_GRID + 63) & ~63ull;
+    c0 = (uint64_t)blk * chunk;
+    c1 = c0 + chunk < E ? c0 + chunk : E;
+    if (c0 > c1) c0 = c1;
+}
+
+// The topic of position p: the last t with hit[t] <= p, i.e. (the first index u
+// of [lo, n] with hit[u] > p) - 1, found by the whole wave, 64 probes a round
+// (1M offsets: 4 rounds instead of a binary search's 20 dependent loads).
+// `lo` is a known lower bound of u.  Reads hit[0 .. n] only, and ends whatever
+// the offsets hold.
+__device__ __forceinline__ uint64_t fo_topic_at(const uint64_t *hit, uint64_t n, uint64_t p, uint64_t lo,
+                                                uint32_t lane) {
+    uint64_t hi = n + 1;
+    if (lo > hi) lo = hi;
+    while (lo < hi) {
+        const uint64_t step = (hi - lo + 63) / 64;
+        const uint64_t idx = lo + lane * step;
+        const bool in = idx < hi;
+        const bool gt = in && hit[idx] > p;
+        const uint64_t m_gt = __ballot(gt), m_in = __ballot(in);
+        if (!m_gt) {
+            lo = lo + ((uint64_t)__popcll(m_in) - 1) * step + 1;   // every probe <= p
+        } else {
+            const uint64_t f = (uint64_t)__builtin_ctzll(m_gt);
+            hi = lo + f * step;
+            if (f) lo = lo + (f - 1) * step + 1;
+        }
+    }
+    return lo ? lo - 1 : 0;
+}
+
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d, 64);
+        if (lane >= (uint32_t)d) x += y;
+    }
+    return x;
+}
+
+// SRC 0: the digit's source is the CSR's values (bucket = dest_of[value]);
+// SRC 1: the buckets a first pass stored
+template <int SRC>
+__global__ __launch_bounds__(64) void k_fo_hist(const uint64_t *hit, uint64_t n, uint64_t cap, const uint32_t *in,
+                                                const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests,
+                                                uint32_t shift, uint32_t bits, uint32_t *tab) {
+    __shared__ uint32_t s_h[FO_BINS];
+    const uint32_t lane = threadIdx.x, nb = 1u << bits, mask = nb - 1;
+    for (uint32_t i = lane; i < nb; i += 64) s_h[i] = 0;
+    __syncthreads();
+    uint64_t c0, c1, E;
+    fo_chunk(hit, n, cap, blockIdx.x, c0, c1, E);
+    for (uint64_t p0 = c0; p0 < c1; p0 += 64 * FO_HIST_UNROLL) {
+        uint32_t x[FO_HIST_UNROLL];
+#pragma unroll
+        for (int k = 0; k < FO_HIST_UNROLL; k++) {
+            const uint64_t p = p0 + (uint64_t)k * 64 + lane;
+            x[k] = p < c1 ? in[p] : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < FO_HIST_UNROLL; k++) {
+            const uint64_t p = p0 + (uint64_t)k * 64 + lane;
+            if (p < c1) {
+                const uint32_t b = SRC == 0 ? fo_bucket(x[k], dest_of, dest_len, n_dests) : x[k];
+                atomicAdd(&s_h[(b >> shift) & mask], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = lane; i < nb; i += 64) tab[(uint64_t)i * FO_GRID + blockIdx.x] = s_h[i];
+}
+
+// one block per bin: its row of FO_GRID block counts -> exclusive scan in place, the total into tot[bin]
+__global__ __launch_bounds__(256) void k_fo_scan(uint32_t *tab, uint32_t *tot) {
+    constexpr int PER = FO_GRID / 256;
+    __shared__ uint32_t s_w[4];
+    uint32_t *row = tab + (uint64_t)blockIdx.x * FO_GRID + threadIdx.x * PER;
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t x[PER], sum = 0;
+#pragma unroll
+    for (int k = 0; k < PER; k++) { x[k] = row[k]; sum += x[k]; }
+    const uint32_t inc = wave_incl_scan(sum, lane);
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    uint32_t base = inc - sum;
+    for (uint32_t q = 0; q < wv; q++) base += s_w[q];
+#pragma unroll
+    for (int k = 0; k < PER; k++) { row[k] = base; base += x[k]; }
+    if (threadIdx.x == 255) tot[blockIdx.x] = base;
+}
+
+// SRC 0: entries from the CSR (topic from the offsets, bucket from dest_of);
+// SRC 1: the triples a first pass stored.  LAST: (topic, value) into the
+// outputs; else the triple into the scratch for the next pass.
+template <int SRC, bool LAST>
+__global__ __launch_bounds__(64) void k_fo_scatter(const uint64_t *hit, uint64_t n, uint64_t cap, const uint32_t *in_v,
+                                                   const uint32_t *in_t, const uint32_t *in_b, const uint32_t *dest_of,
+                                                   uint64_t dest_len, uint32_t n_dests, uint32_t shift, uint32_t bits,
+                                                   const uint32_t *tab, const uint32_t *tot, uint32_t *out_t,
+                                                   uint32_t *out_v, uint32_t *out_b, uint64_t *dest_offsets) {
+    __shared__ uint32_t s_base[FO_BINS];
+    __shared__ uint64_t s_win[64];
+    const uint32_t lane = threadIdx.x, nb = 1u << bits, mask = nb - 1;
+    // every block scans the bins' totals itself (at most 8 rounds of one wave)
+    const bool offs_out = dest_offsets && blockIdx.x == 0;   // (one pass: the buckets are the bins)
+    uint32_t carry = 0;
+    for (uint32_t i0 = 0; i0 < nb; i0 += 64) {
+        const uint32_t i = i0 + lane;
+        const uint32_t x = i < nb ? tot[i] : 0u;
+        const uint32_t inc = wave_incl_scan(x, lane);
+        const uint32_t exc = carry + inc - x;
+        if (i < nb) {
+            s_base[i] = exc + tab[(uint64_t)i * FO_GRID + blockIdx.x];
+            if (offs_out && i <= n_dests + 1) dest_offsets[i] = exc;
+        }
+        carry += __shfl(inc, 63, 64);
+    }
+    if (offs_out && n_dests + 1 == nb && lane == 0) dest_offsets[nb] = carry;
+    __syncthreads();
+    uint64_t c0, c1, E;
+    fo_chunk(hit, n, cap, blockIdx.x, c0, c1, E);
+    uint64_t tcur = 0;   // hit[tcur] <= the step's first position
+    if (SRC == 0 && c0 < c1) tcur = fo_topic_at(hit, n, c0, 0, lane);
+    for (uint64_t p0 = c0; p0 < c1; p0 += 64) {
+        const uint64_t p = p0 + lane;
+        const bool ok = p < c1;
+        uint32_t v = 0, b = 0, t = 0;
+        if (SRC == 0) {
+            if (ok) {
+                v = in_v[p];
+                b = fo_bucket(v, dest_of, dest_len, n_dests);
+            }
+            bool found = !ok;
+            uint64_t tw = tcur;
+            for (;;) {
+                // the ends of topics tw .. tw + 63; a lane's topic is tw + (how many of them are <= p)
+                const uint64_t idx = tw + 1 + lane;
+                s_win[lane] = idx <= n ? hit[idx] : ~0ull;
+                __syncthreads();
+                if (!found && s_win[63] > p) {
+                    uint32_t c = 0;
+#pragma unroll
+                    for (uint32_t st = 32; st; st >>= 1)
+                        if (s_win[c + st - 1] <= p) c += st;
+                    t = (uint32_t)(tw + c);
+                    found = true;
+                }
+                __syncthreads();
+                const uint64_t left = __ballot(!found);
+                if (!left) break;
+                // a run of empty topics longer than the window: search again for the first lane left
+                const uint32_t fl = (uint32_t)__builtin_ctzll(left);
+                tw = fo_topic_at(hit, n, p0 + fl, tw + 65, lane);
+            }
+            const uint32_t last = c1 - p0 < 64 ? (uint32_t)(c1 - p0) - 1 : 63u;
+            tcur = __shfl(t, last, 64);
+        } else if (ok) {
+            v = in_v[p];
+            t = in_t[p];
+            b = in_b[p];
+        }
+        const uint32_t d = (b >> shift) & mask;
+        // the lanes of this step with my digit
+        uint64_t peers = __ballot(ok);
+        for (uint32_t k = 0; k < bits; k++) {
+            const bool bit = (d >> k) & 1u;
+            const uint64_t m = __ballot(ok && bit);
+            peers &= bit ? m : ~m;
+        }
+        uint32_t dst = 0;
+        if (ok) dst = s_base[d] + (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
+        __syncthreads();
+        if (ok && (peers >> lane) == 1ull) s_base[d] += (uint32_t)__popcll(peers);
+        __syncthreads();
+        // (dst < E whenever the histogram saw what this kernel sees; the test
+        // keeps a caller who rewrites an input in between inside the outputs)
+        if (ok && dst < E) {
+            out_t[dst] = t;
+            out_v[dst] = v;
+            if (!LAST) out_b[dst] = b;
+        }
+    }
+}
+
+// two passes: dest_offsets[b] = the first output position whose bucket is >= b
+__global__ __launch_bounds__(256) void k_fo_bounds(const uint64_t *hit, uint64_t n, uint64_t cap, const uint32_t *out_v,
+                                                   const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests,
+                                                   uint64_t *dest_offsets) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b > n_dests + 1) return;
+    const uint64_t total = hit[n], E = total < cap ? total : cap;
+    uint64_t lo = 0, hi = E;
+    if (b > n_dests) lo = E;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (fo_bucket(out_v[mid], dest_of, dest_len, n_dests) < b) lo = mid + 1;
+        else hi = mid;
+    }
+    dest_offsets[b] = lo;
+}
+
+}  // namespace
+
+bool fanout_two_pass(uint32_t n_dests) { return n_dests + 1 > 256; }
+
+hipError_t launch_fanout(const FanoutScratch &fs, uint64_t n, const uint64_t *hit, const uint32_t *values,
+                         uint64_t cap, const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests,
+                         uint64_t *dest_offsets, uint32_t *out_topic, uint32_t *out_value, hipStream_t s) {
+    if (!n_dests || n_dests > FO_MAX_DESTS) return hipErrorInvalidValue;
+    if (!dest_of) dest_len = 0;
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;
+    uint32_t w = 1;   // bits of the largest bucket id, n_dests
+    while ((n_dests >> w) != 0) w++;
+    const dim3 g(FO_GRID), b(64);
+    if (!fanout_two_pass(n_dests)) {
+        hipLaunchKernelGGL(k_fo_hist<0>, g, b, 0, s, hit, n, cap, values, dest_of, dest_len, n_dests, 0u, w, fs.tab);
+        hipLaunchKernelGGL(k_fo_scan, dim3(1u << w), dim3(256), 0, s, fs.tab, fs.tot);
+        hipLaunchKernelGGL((k_fo_scatter<0, true>), g, b, 0, s, hit, n, cap, values, (const uint32_t *)nullptr,
+                           (const uint32_t *)nullptr, dest_of, dest_len, n_dests, 0u, w, fs.tab, fs.tot, out_topic,
+                           out_value, (uint32_t *)nullptr, dest_offsets);
+        return hipGetLastError();
+    }
+    if (cap > fs.cap) return hipErrorInvalidValue;   // (the triples of the first pass)
+    const uint32_t lo = (w + 1) / 2, hi = w - lo;
+    hipLaunchKernelGGL(k_fo_hist<0>, g, b, 0, s, hit, n, cap, values, dest_of, dest_len, n_dests, 0u, lo, fs.tab);
+    hipLaunchKernelGGL(k_fo_scan, dim3(1u << lo), dim3(256), 0, s, fs.tab, fs.tot);
+    hipLaunchKernelGGL((k_fo_scatter<0, false>), g, b, 0, s, hit, n, cap, values, (const uint32_t *)nullptr,
+                       (const uint32_t *)nullptr, dest_of, dest_len, n_dests, 0u, lo, fs.tab, fs.tot, fs.t, fs.v, fs.b,
+                       (uint64_t *)nullptr);
+    hipLaunchKernelGGL(k_fo_hist<1>, g, b, 0, s, hit, n, cap, fs.b, dest_of, dest_len, n_dests, lo, hi, fs.tab);
+    hipLaunchKernelGGL(k_fo_scan, dim3(1u << hi), dim3(256), 0, s, fs.tab, fs.tot);
+    hipLaunchKernelGGL((k_fo_scatter<1, true>), g, b, 0, s, hit, n, cap, fs.v, fs.t, fs.b, dest_of, dest_len, n_dests, lo,
+                       hi, fs.tab, fs.tot, out_topic, out_value, (uint32_t *)nullptr, (uint64_t *)nullptr);
+    hipLaunchKernelGGL(k_fo_bounds, dim3((n_dests + 2 + 255) / 256), dim3(256), 0, s, hit, n, cap, out_value, dest_of,
+                       dest_len, n_dests, dest_offsets);
+    return hipGetLastError();
+}
+
+}  // namespace tmx

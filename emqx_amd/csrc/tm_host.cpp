@@ -116,6 +116,11 @@ struct Lane {
     uint32_t *pin_vals = nullptr, *pin_vals_dev = nullptr; uint64_t pin_vals_cap = 0;
     uint32_t *d_vals = nullptr; uint64_t d_vals_cap = 0;   // sorted output: values sorted in HBM first
     uint64_t *d_o64 = nullptr, *d_h64 = nullptr; uint64_t d_o64_cap = 0, d_h64_cap = 0;   // 32-bit device API: widened offsets
+    // route fan-out (tm_fanout_dev / tm_route_batch): the passes' tables and
+    // triples; tm_route_batch's device results (topics, values, bucket offsets)
+    FanoutScratch f{};
+    uint32_t *d_ft = nullptr, *d_fv = nullptr; uint64_t d_ft_cap = 0, d_fv_cap = 0;
+    uint64_t *d_fo = nullptr; uint64_t d_fo_cap = 0;
 };
 
 // Patch log: a ring of the last PATCH_RING patches (numbered 1, 2, ... in the
@@ -246,6 +251,21 @@ struct tm_index {
 
     std::vector<std::unique_ptr<Lane>> lanes;
     uint64_t tick = 0;
+
+    // value -> destination (tm_set_dests; NONE: never set, unrouted): the
+    // host array under `dst_mu` (taken after `mu`; tm_set_dests takes it alone)
+    // and one device copy per group (device entry), which takes the
+    // entries changed since its last upload -- [lo, hi) -- in stream order
+    // before the next fan-out that reads it (dest_upload)
+    std::mutex dst_mu;
+    std::vector<uint32_t> dest_h;
+    struct DestDev {
+        uint32_t *d = nullptr; uint64_t cap = 0, len = 0;   // allocated / valid entries
+        uint64_t lo = 0, hi = 0;                            // host entries newer than the device's
+        uint32_t *pin = nullptr; uint64_t pin_cap = 0;      // upload staging
+        hipEvent_t ev = nullptr; bool ev_set = false;       // after the last upload: other streams' fan-outs wait
+        hipStream_t ev_s = nullptr;
+    } dest[MAX_REPLICAS];
 
     // caller buffers from tm_host_alloc (host address -> size, device address;
     // vram: TM_ALLOC_VRAM device memory, the same address on both sides)
@@ -1651,7 +1671,7 @@ void free_workspace(Workspace &w) {
 
 void free_lane(Lane &l) {
     free_workspace(l.w);
-    void *dv[] = {l.d_in, l.d_res, l.d_vals, l.d_o64, l.d_h64};
+    void *dv[] = {l.d_in, l.d_res, l.d_vals, l.d_o64, l.d_h64, l.f.tab, l.f.tot, l.f.t, l.f.v, l.f.b, l.d_ft, l.d_fv, l.d_fo};
     for (void *p : dv) if (p) (void)hipFree(p);
     void *pins[] = {l.pin_in, l.pin_out, l.pin_vals};
     for (void *p : pins) if (p) (void)hipHostFree(p);
@@ -1884,7 +1904,7 @@ int drain_lanes(tm_index *ix) {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 10u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 11u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 
@@ -2000,6 +2020,14 @@ int tm_destroy(tm_index *ix) {
             if (R.pdone[i]) (void)hipEventDestroy(R.pdone[i]);
         }
         if (R.ps) (void)hipStreamDestroy(R.ps);
+    }
+    for (int g = 0; g < ix->ngroups; g++) {
+        auto &D = ix->dest[g];
+        for (int r = 0; r < ix->nrep; r++)
+            if (ix->rep[r].group == g) { (void)hipSetDevice(ix->rep[r].device); break; }
+        if (D.d) (void)hipFree(D.d);
+        if (D.pin) (void)hipHostFree(D.pin);
+        if (D.ev) (void)hipEventDestroy(D.ev);
     }
     (void)hipSetDevice(ix->rep[0].device);
     mf_free_keys(ix->mf);
@@ -2256,6 +2284,158 @@ int tm_sort_segments(tm_index *ix, uint64_t n, const uint64_t *hit_offs, uint32_
     if ((rc = dev_lane(ix, s, r, ln))) return rc;
     if ((rc = ensure_ws(ix, n, *ln))) return rc;
     HIPCHK(ix, launch_sort_segments(ln->w, n, hit_offs, vals, cap, order == TM_ORDER_UNIQUE, ucnt, s));
+    return batch_done(ix, *ln);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the fan-out's scratch on a lane: the tables always, the triples of a first
+// pass when n_dests needs two (grow-only; freed with the lane)
+int ensure_fanout(tm_index *ix, Lane &ln, uint32_t n_dests, uint64_t cap) {
+    FanoutScratch &f = ln.f;
+    if (!f.tab) {
+        HIPCHK(ix, hipMalloc(&f.tab, (uint64_t)FO_BINS * FO_GRID * 4));
+        HIPCHK(ix, hipMalloc(&f.tot, FO_BINS * 4));
+    }
+    if (!fanout_two_pass(n_dests) || (cap <= f.cap && f.t)) return TM_OK;
+    HIPCHK(ix, hipStreamSynchronize(ln.s));   // only this lane's stream uses them
+    for (uint32_t **p : {&f.t, &f.v, &f.b}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    f.cap = 0;
+    const uint64_t c = std::max<uint64_t>(std::min<uint64_t>(cap + cap / 4, 0xFFFFFFFFull), 1024);
+    for (uint32_t **p : {&f.t, &f.v, &f.b})
+        if (hipMalloc(p, c * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ix, TM_ENOMEM, "fan-out: no device memory for a two-pass batch's scratch (12 bytes x cap)");
+        }
+    f.cap = c;
+    return TM_OK;
+}
+
+// The index's own value -> destination table on group g, current as of now,
+// for a fan-out about to be queued on stream s (caller holds ix->mu, the
+// calling thread is on the group's device).  The entries tm_set_dests changed
+// since the group's last upload go up through pinned staging, in stream
+// order, after the fan-outs of other streams that may still read them; a
+// fan-out on another stream waits for the upload's event.
+int dest_upload(tm_index *ix, int g, hipStream_t s, const uint32_t *&d, uint64_t &len) {
+    auto &D = ix->dest[g];
+    std::lock_guard<std::mutex> dg(ix->dst_mu);
+    const uint64_t hl = ix->dest_h.size();
+    if (!D.ev) HIPCHK(ix, hipEventCreateWithFlags(&D.ev, hipEventDisableTiming));
+    if (D.ev_set && hipEventQuery(D.ev) == hipSuccess) D.ev_set = false;
+    if (hl > D.cap) {
+        // grows (by half: rare): no fan-out may still read the old copy, so
+        // wait for the group's lanes that have a batch in flight and for the
+        // last upload -- under both locks, but not for the rest of the device
+        for (auto &l : ix->lanes)
+            if (ix->rep[l->r].group == g && lane_busy(*l)) HIPCHK(ix, hipEventSynchronize(l->done));
+        if (D.ev_set) HIPCHK(ix, hipEventSynchronize(D.ev));
+        if (D.d) HIPCHK(ix, hipFree(D.d));
+        D.d = nullptr;
+        D.cap = D.len = 0;
+        const uint64_t c = std::max<uint64_t>(hl + hl / 2, 4096);
+        HIPCHK(ix, hipMalloc(&D.d, c * 4));
+        D.cap = c;
+        D.lo = 0;
+        D.hi = hl;
+        D.ev_set = false;
+    }
+    if (D.hi > D.lo) {
+        const uint64_t cnt = D.hi - D.lo;
+        if (D.ev_set) HIPCHK(ix, hipEventSynchronize(D.ev));   // the staging buffer's last copy
+        if (cnt > D.pin_cap) {
+            if (D.pin) HIPCHK(ix, hipHostFree(D.pin));
+            D.pin = nullptr;
+            D.pin_cap = 0;
+            const uint64_t c = std::max<uint64_t>(cnt + cnt / 4, 4096);
+            HIPCHK(ix, hipHostMalloc(&D.pin, c * 4, hipHostMallocDefault));
+            D.pin_cap = c;
+        }
+        std::memcpy(D.pin, ix->dest_h.data() + D.lo, cnt * 4);
+        for (auto &l : ix->lanes)
+            if (l->s != s && ix->rep[l->r].group == g && lane_busy(*l)) HIPCHK(ix, hipStreamWaitEvent(s, l->done, 0));
+        HIPCHK(ix, hipMemcpyAsync(D.d + D.lo, D.pin, cnt * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ix, hipEventRecord(D.ev, s));
+        D.ev_set = true;
+        D.ev_s = s;
+        D.lo = D.hi = 0;
+        D.len = hl;
+    } else if (D.ev_set && D.ev_s != s) {
+        HIPCHK(ix, hipStreamWaitEvent(s, D.ev, 0));
+    }
+    d = D.d;
+    len = D.len;
+    return TM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tm_set_dests(tm_index *ix, uint64_t n, const uint32_t *values, const uint32_t *dests) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_set_dests: null handle");
+    if (n && (!values || !dests)) return fail(ix, TM_EINVAL, "tm_set_dests: null buffer");
+    if (!n) return TM_OK;
+    std::lock_guard<std::mutex> dg(ix->dst_mu);
+    uint64_t lo = UINT64_MAX, hi = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        lo = std::min<uint64_t>(lo, values[i]);
+        hi = std::max<uint64_t>(hi, (uint64_t)values[i] + 1);
+    }
+    if (hi > ix->dest_h.size()) {
+        // the entries between the old end and the lowest new value become NONE
+        // on the host: they go up too, so no device entry below `len` is ever
+        // one the host never wrote
+        lo = std::min<uint64_t>(lo, ix->dest_h.size());
+        try {
+            ix->dest_h.resize(hi, NONE);
+        } catch (const std::bad_alloc &) {
+            return fail(ix, TM_ENOMEM, "tm_set_dests: out of host memory (the table has one entry per value up to the largest)");
+        }
+    }
+    for (uint64_t i = 0; i < n; i++) ix->dest_h[values[i]] = dests[i];
+    for (int g = 0; g < ix->ngroups; g++) {
+        auto &D = ix->dest[g];
+        if (D.hi > D.lo) {
+            D.lo = std::min(D.lo, lo);
+            D.hi = std::max(D.hi, hi);
+        } else {
+            D.lo = lo;
+            D.hi = hi;
+        }
+    }
+    return TM_OK;
+}
+
+int tm_fanout_dev(tm_index *ix, uint64_t n, const uint64_t *hit_offs, const uint32_t *vals, uint64_t cap,
+                  const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests, uint64_t *dest_offs,
+                  uint32_t *out_topic, uint32_t *out_value, void *stream) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_fanout_dev: null handle");
+    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_fanout_dev: n_dests must be 1 .. 65536");
+    if (!hit_offs || !dest_offs || (cap && (!vals || !out_topic || !out_value)))
+        return fail(ix, TM_EINVAL, "tm_fanout_dev: null buffer");
+    if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_fanout_dev: too many topics");
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
+    std::lock_guard<std::mutex> g(ix->mu);
+    hipStream_t s = pick_stream(ix, stream);
+    Lane *ln = nullptr;
+    int rc, grp = 0;
+    if ((rc = dev_group(ix, grp))) return rc;
+    for (auto &l : ix->lanes)   // the lane the stream's match batches use, if any
+        if (!l->owned && l->s == s && ix->rep[l->r].group == grp) { ln = l.get(); ln->tick = ++ix->tick; break; }
+    if (!ln) {
+        int r = 0;
+        while (ix->rep[r].group != grp) r++;
+        if ((rc = dev_lane(ix, s, r, ln))) return rc;
+    }
+    if ((rc = ensure_fanout(ix, *ln, n_dests, cap))) return rc;
+    if (!dest_of && (rc = dest_upload(ix, grp, s, dest_of, dest_len))) return rc;
+    HIPCHK(ix, launch_fanout(ln->f, n, hit_offs, vals, cap, dest_of, dest_len, n_dests, dest_offs, out_topic, out_value, s));
     return batch_done(ix, *ln);
 }
 
@@ -2799,6 +2979,87 @@ int tm_match_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *
     return tm_match_batch_ex(ix, n, tb, to, out_hit, out_vals, cap, out_err, TM_ORDER_TRAVERSAL, nullptr);
 }
 
+// The product path of a batched broker: match into device scratch (CSR,
+// traversal order), fan out with the index's own destination table, copy the
+// destination-major arrays back.  The lane's value scratch always holds the
+// whole batch (it grows and the batch runs again, as tm_match_batch's staging
+// does), so the bucket offsets are complete whatever `cap` is; cap only bounds
+// what is copied out.  Same lanes, locking and look-back retry as
+// match_batch_impl.
+int tm_route_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
+                   uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                   uint8_t *out_err) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_route_batch: null handle");
+    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_route_batch: n_dests must be 1 .. 65536");
+    if (!to || !out_dest_offsets || (n && !tb && to[n] != to[0]) || (cap && (!out_topic || !out_values)))
+        return fail(ix, TM_EINVAL, "tm_route_batch: null buffer");
+    if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch: batch too large");
+    std::unique_lock<std::mutex> g(ix->mu);
+    LaneLease lease{ix, g};
+    int rc;
+    if ((rc = host_lane(ix, g, lease.ln))) return rc;
+    Lane &ln = *lease.ln;
+    const hipStream_t s = ln.s;
+    if ((rc = sync_locked(ix, ln.r, s))) return rc;
+    if ((rc = ensure_ws(ix, n, ln))) return rc;
+    ix->rep[ln.r].batches++;
+    const uint8_t *dbytes;
+    const uint64_t *doffs;
+    if ((rc = stage_in(ix, ln, n, tb, to, nullptr, dbytes, doffs))) return rc;
+    const uint64_t rbytes = (n + 1) * 8 + n;   // hit offsets, then the err flags
+    uint8_t *dres;
+    if ((rc = stage_out(ix, ln, n, rbytes, dres))) return rc;
+    uint64_t *dhit = reinterpret_cast<uint64_t *>(dres);
+    uint8_t *derr = dres + (n + 1) * 8;
+    uint64_t total = 0, vcap = std::max<uint64_t>({ln.d_vals_cap, 4 * n, 1 << 16});
+    for (int attempt = 0, tries = 0;; attempt++) {
+        if (vcap > 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch: more than 2^32 - 1 hits in one batch");
+        if ((rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, vcap))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_ft, ln.d_ft_cap, vcap))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_fv, ln.d_fv_cap, vcap))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_fo, ln.d_fo_cap, (uint64_t)n_dests + 2))) return rc;
+        if ((rc = ensure_fanout(ix, ln, n_dests, vcap))) return rc;
+        const DevIndex d = dev_view(ix, ln.r);
+        uint32_t tag;
+        if ((rc = next_tag(ix, ln, s, tag))) return rc;
+        int path = PATH_PHASES;
+        HIPCHK(ix, launch_match(d, ln.w, n, dbytes, doffs, dhit, derr, ln.d_vals, vcap, tag, next_lb(ix), ix->dbg_phases,
+                                ix->small_kind, s, nullptr, nullptr, &path));
+        ix->path_batches[path]++;
+        const uint32_t *dtab = nullptr;
+        uint64_t dlen = 0;
+        if ((rc = dest_upload(ix, ix->rep[ln.r].group, s, dtab, dlen))) return rc;
+        HIPCHK(ix, launch_fanout(ln.f, n, dhit, ln.d_vals, vcap, dtab, dlen, n_dests, ln.d_fo, ln.d_ft, ln.d_fv, s));
+        if ((rc = fetch_out(ix, ln, n, rbytes))) return rc;
+        if ((rc = batch_done(ix, ln))) return rc;
+        g.unlock();
+        HIPCHK(ix, hipStreamSynchronize(s));
+        if (batch_failed(ix, ln)) {   // the look-back failed: run the batch again, once
+            if ((rc = retry_or_fail(ix, g, ln, tries++))) return rc;
+            attempt--;
+            continue;
+        }
+        std::memcpy(&total, ln.pin_out + n * 8, 8);
+        if (total <= vcap) break;
+        if (attempt >= 2) return fail(ix, TM_EDEVICE, "tm_route_batch: hit total kept growing past the value scratch");
+        vcap = total + total / 4;
+        g.lock();
+        HIPCHK(ix, hipSetDevice(ix->rep[ln.r].device));
+        if ((rc = sync_locked(ix, ln.r, s))) return rc;
+        if ((rc = ensure_ws(ix, n, ln))) return rc;
+    }
+    // (the lane is still checked out: its buffers are this caller's)
+    const uint64_t keep = std::min(total, cap);
+    HIPCHK(ix, hipMemcpyAsync(out_dest_offsets, ln.d_fo, ((uint64_t)n_dests + 2) * 8, hipMemcpyDeviceToHost, s));
+    if (keep) {
+        HIPCHK(ix, hipMemcpyAsync(out_topic, ln.d_ft, keep * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ix, hipMemcpyAsync(out_values, ln.d_fv, keep * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(ix, hipStreamSynchronize(s));
+    if (out_err && n) std::memcpy(out_err, ln.pin_out + (n + 1) * 8, n);
+    return total > cap ? TM_ECAP : TM_OK;
+}
+
 // 32-bit offsets (include/tmatch.h).  An in-place batch the one-launch small
 // kernel takes runs on 32-bit offsets end to end (k_walk_small<.., uint32_t>):
 // half the offset bytes cross PCIe in each direction.  Any other batch is
@@ -3097,6 +3358,7 @@ int tm_debug_get(tm_index *ix, uint32_t key, uint64_t *value) {
     case TM_DEBUG_COMMITS: *value = ix->commits.load(); break;
     case TM_DEBUG_SMALL_TICKET: *value = ix->small_ticket; break;
     case TM_DEBUG_PATCH_ZC: *value = ix->patch_zc; break;
+    case TM_DEBUG_FANOUT_GRID: *value = FO_GRID; break;
     case TM_DEBUG_COMMIT_WAITS: *value = ix->commit_waits.load(); break;
     case TM_DEBUG_COMMIT_FORCED: *value = ix->commit_forced.load(); break;
     case TM_DEBUG_COMBINED_LAUNCHES: *value = ix->cmb_launches.load(); break;

@@ -109,6 +109,26 @@ def event_key(event):
 
 ROUTER_COPIES = 2   # src/emqx_router_gpu.erl ?COPIES
 
+MAX_DEST_CLASSES = 65536   # tm_route_batch's n_dests bound; a later class stays unrouted on the device
+UNROUTED = 0xFFFFFFFF
+
+
+def dest_class(dest):
+    """What a batched broker sends one plan to: a plain node -> that node;
+    {Group, Node} -> the group, which aggre/1 reduces it to
+    (emqx_broker.erl:412-420); ("external", X) -> itself."""
+    if isinstance(dest, tuple) and len(dest) == 2:
+        return dest if dest[0] == "external" else dest[0]
+    return dest
+
+
+class ByDest(dict):
+    """{destination class: [(message index, Route)]}; .errors: {message index: exception} (errors="return")"""
+
+    def __init__(self):
+        super().__init__()
+        self.errors = {}
+
 
 class MirrorDown(RuntimeError):
     """No live device mirror: its process died and its successor has not booted
@@ -126,7 +146,11 @@ class Router:
         # emqx_router_gpu attaches it (?COPIES: the router takes the churn)
         self._device = device
         self._mirror_factory = mirror_factory or (lambda: ti.Tab(device=self._device, copies=ROUTER_COPIES))
-        self._mirror = mirror if mirror is not None else self._mirror_factory()
+        # destination classes interned to the u32 ids the device buckets by (tm_set_dests)
+        self._dest_ids: dict = {}
+        self._dest_classes: list = []
+        self._dest_lock = threading.Lock()
+        self._mirror = self._adopt(mirror if mirror is not None else self._mirror_factory())
         self._alive = True                       # the mirror process is running (its handle is served)
         self._mailbox: list = []                 # table events not yet drained by the event process
         self.mirror_calls = 0                    # tm_apply_deltas calls made for the mirror
@@ -178,6 +202,30 @@ class Router:
             self._bag_delete(topic, dest)
             self._mailbox.append(("delete", Route(topic, dest)))
         return None
+
+    # ------------------------------------------------- destination classes
+    def dest_id(self, dest) -> int:
+        """The u32 id of dest's class, interned on first sight; UNROUTED once
+        MAX_DEST_CLASSES classes exist (such a route is not an error: the
+        device leaves it in the unrouted bucket and match_routes_by_dest
+        resolves it on the host)."""
+        cls = dest_class(dest)
+        with self._dest_lock:
+            i = self._dest_ids.get(cls)
+            if i is None:
+                if len(self._dest_classes) >= MAX_DEST_CLASSES:
+                    return UNROUTED
+                i = self._dest_ids[cls] = len(self._dest_classes)
+                self._dest_classes.append(cls)
+            return i
+
+    def _adopt(self, mirror):
+        """A mirror that ships destinations (topic_index.Tab) learns each
+        inserted key's class id from here: mirror_sync's sync_keys then calls
+        tm_set_dests for the keys it inserts, before the delta inserting them."""
+        if hasattr(mirror, "dest_fn"):
+            mirror.dest_fn = lambda key: self.dest_id(ti.get_id(key))
+        return mirror
 
     # ------------------------------------------------------------ the mirror
     def mirror_sync(self, keys, commit: bool = False):
@@ -236,7 +284,7 @@ class Router:
         with self._cmt:
             while self._cmt_busy:
                 self._cmt.wait()
-            m = self._mirror_factory()
+            m = self._adopt(self._mirror_factory())
             with self._tables:
                 rows = list(self._filters.values())
                 self._mailbox = []
@@ -396,6 +444,75 @@ class Router:
 
     def match_routes(self, topic):
         return self.match_routes_batch([topic])[0]
+
+    def match_routes_by_dest(self, topics, errors: str = "raise") -> ByDest:
+        """match_routes/1 over a batch, regrouped by destination class on the
+        device (tm_route_batch): {class: [(message index, Route)]}, what
+        do_route2/2 (emqx_broker.erl:401-406) would visit hit by hit, as one
+        list per destination.  Each list is in message order; inside a message
+        its routes keep the order of match_routes_batch's list for that message
+        (the bag's rows, then the filter matches).  Routes the device leaves
+        unrouted (a class beyond MAX_DEST_CLASSES) are resolved here through
+        the same decode path.  errors as for match_routes_batch: "return"
+        collects a bad topic's exception in .errors[message index]."""
+        topics = [bytes(t) for t in topics]
+        mirror = self._live_mirror()
+        out = ByDest()
+        groups: dict = {}    # class -> {message index: [Route]}
+        ticket = mirror.read_begin()
+        try:
+            with self._dest_lock:
+                classes = list(self._dest_classes)
+            n_dests = max(len(classes), 1)
+            doff, tidx, kids, err = mirror.route_kids(topics, n_dests)
+            if len(err) and (err == 4).any():   # (the library returns TM_EDEVICE instead; never a client error)
+                raise ti.DeviceError(-3, "batch failed on the device (err flag 4)")
+            for i in map(int, err.nonzero()[0]):
+                e = ti.TopicTooDeep(len(topics[i])) if err[i] == 2 else ti.BadArg(topics[i])
+                if errors == "raise":
+                    raise e
+                out.errors[i] = e
+            for i, t in enumerate(topics):   # the bag's rows come first
+                if i in out.errors:
+                    continue
+                for r in self.lookup_route_tab(t):
+                    groups.setdefault(dest_class(r.dest), {}).setdefault(i, []).append(r)
+            tidx, doff = tidx.tolist(), doff.tolist()
+            mixed = set()
+            for b in range(n_dests + 1):
+                lo, hi = doff[b], doff[b + 1]
+                while lo < hi:   # one message's run
+                    i, e = tidx[lo], lo + 1
+                    while e < hi and tidx[e] == i:
+                        e += 1
+                    keys = mirror.decode(kids[lo:e])
+                    lo = e
+                    if b < len(classes):
+                        g = groups.setdefault(classes[b], {}).setdefault(("f", i), [])
+                        if g:
+                            mixed.add((classes[b], i))
+                        g.extend(keys)
+                    else:   # unrouted on the device: the class comes from the key
+                        for k in keys:
+                            cls = dest_class(ti.get_id(k))
+                            g = groups.setdefault(cls, {}).setdefault(("f", i), [])
+                            if g:
+                                mixed.add((cls, i))
+                            g.append(k)
+        finally:
+            mirror.read_end(ticket)
+        for cls, per_msg in groups.items():
+            rows = []
+            for i in sorted({m if isinstance(m, int) else m[1] for m in per_msg}):
+                rows.extend((i, r) for r in per_msg.get(i, ()))
+                keys = per_msg.get(("f", i), ())
+                if (cls, i) in mixed:   # from two buckets: back into traversal (term) order
+                    keys = sorted(keys, key=ti.key_order)
+                # matches/3's order, as match_routes_batch lists them: the reverse of the traversal
+                rows.extend((i, Route(ti.get_topic(k), ti.get_id(k))) for k in ti.traversal_order(list(keys))[::-1])
+            if rows:
+                out[cls] = rows
+        return out
 
     def topics(self):
         """topics/0 = list_topics_v2 (emqx_router.erl:627-630): the bag's topics,

@@ -60,6 +60,11 @@ class Tab:
         self._ops: list = []            # pending (op, filter_bytes, kid, flags)
         self._lock = threading.Lock()   # pending deltas and u32 bookkeeping (writer side)
         self._sorted = None             # (keys, order keys) in term order, for matches_filter/3
+        # route fan-out (include/tmatch.h): dest_fn(key) -> the u32 destination id of a
+        # key's value, set by the owner (Router); shipped with tm_set_dests ahead of the
+        # delta that inserts the key
+        self.dest_fn = None
+        self._dests: list = []          # pending (kid, destination id)
 
     # -- key <-> device encoding
     @staticmethod
@@ -99,6 +104,10 @@ class Tab:
             self._flush_locked(commit)
 
     def _flush_locked(self, commit: bool):
+        if self._dests:
+            d = np.array(self._dests, dtype=np.uint32).reshape(-1, 2)
+            self._dests = []
+            self._index.set_dests(d[:, 0], d[:, 1])
         if not self._ops:
             return
         ops = np.array([o[0] for o in self._ops], dtype=np.uint8)
@@ -139,6 +148,8 @@ class Tab:
             kid = self._take_kid()
             self._keys[kid] = key
             self._kid[key] = kid
+            if self.dest_fn is not None:
+                self._dests.append((kid, self.dest_fn(key)))
             self._queue(_native.TM_OP_INSERT, key, kid)
         self._records[key] = record
 
@@ -193,6 +204,16 @@ class Tab:
         blob, offs = _native.pack_strings(topics)
         hit, vals, err = self._index.match_batch(blob, offs)
         return [vals[hit[i]:hit[i + 1]] for i in range(len(topics))], err
+
+    def route_kids(self, topics, n_dests: int):
+        """tm_route_batch -> (dest_offsets u64[n_dests + 2], topic index u32[],
+        kid u32[], err u8[n]): destination b's (topic index, kid) pairs are
+        [dest_offsets[b], dest_offsets[b + 1]), in topic order and traversal
+        order inside a topic; bucket n_dests: kids without a destination
+        below n_dests.  Decoded like match_kids' results."""
+        self.flush()
+        blob, offs = _native.pack_strings(topics)
+        return self._index.route_batch(blob, offs, n_dests)
 
     def read_begin(self) -> int:
         return self._index.read_begin()

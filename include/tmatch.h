@@ -354,6 +354,63 @@ int tm_match_batch_dev_pairs(tm_index *h, uint64_t n, const uint8_t *d_topic_byt
 int tm_sort_segments(tm_index *h, uint64_t n, const uint64_t *d_hit_offsets, uint32_t *d_values, uint64_t cap,
                      uint32_t order, uint32_t *d_out_unique, void *stream);
 
+/* Route fan-out: hit lists bucketed by destination.
+ * emqx_broker:do_publish/1 is route(aggre(match_routes(Topic)), Delivery)
+ * (emqx_broker.erl:293-298): each hit is a route {To, Dest}, and do_route2/2
+ * (emqx_broker.erl:401-406) dispatches it locally, forwards it to
+ * get_dest_node(Dest) (emqx_router.erl:580-585) with forward/4
+ * (emqx_broker.erl:429), or hands it to a shared group -- once per hit.  A
+ * batched broker forwards once per destination per micro-batch, so it needs
+ * the batch's (topic, value) pairs grouped by the destination of the value.
+ *
+ * tm_set_dests: the index's value -> destination table (the caller's dense
+ * ids, e.g. one per node, per shared group and per external destination;
+ * get_dest_node/1 on the interned route).  A value never set is unrouted.
+ * Thread safe with every other call; a fan-out queued after it returns sees the
+ * new table (only the entries changed since a device's last fan-out are
+ * uploaded, in stream order before it), one already queued may see either
+ * state.  Set a value's destination before inserting its key; the reader
+ * epochs above already keep a freed value from being reused early.  The host
+ * table has one u32 per value up to the largest one set.
+ *
+ * tm_fanout_dev: device buffers, asynchronous on `stream`.  Input: any device
+ * CSR -- d_hit_offsets[n + 1] and d_values as tm_match_batch_dev or
+ * tm_merge_shards write them (NOT tm_match_batch_dev_pairs' pairs: its spans
+ * are not in topic order) -- and d_dest_of[dest_len] (NULL: the index's own
+ * table, dest_len ignored).  The entry at position p < min(d_hit_offsets[n],
+ * cap) has topic t (the segment holding p), value v = d_values[p] and bucket
+ * b = d_dest_of[v] if v < dest_len and d_dest_of[v] < n_dests, else b =
+ * n_dests: the unrouted bucket, so nothing is dropped.  Output:
+ * d_dest_offsets[n_dests + 2], the exclusive scan of the bucket sizes with
+ * the total last, and d_out_topic / d_out_value (u32): bucket b's entries at
+ * [d_dest_offsets[b], d_dest_offsets[b + 1]) in ascending input position
+ * (ascending topic, traversal order inside a topic) -- numpy.argsort(bucket,
+ * kind="stable") applied to (topic, value).  Entries at positions >= cap
+ * (clamped to 2^32 - 1) are neither counted nor written, and nothing past
+ * min(total, cap) is written in either array; the inputs are not modified.
+ * One pass over the entries for n_dests + 1 <= 256, two otherwise (then the
+ * stream's scratch holds 12 bytes x cap: TM_ENOMEM if that cannot be had).
+ * Scratch is kept per stream with the batch scratch (tm_stream_release).
+ *
+ * tm_route_batch: host buffers in and out, the product path -- the batch is
+ * matched into device scratch (CSR, traversal order), fanned out with the
+ * index's table, and the three arrays are copied back.  out_dest_offsets has
+ * n_dests + 2 entries, out_topic / out_values `cap`; out_err as for
+ * tm_match_batch (may be NULL).  Concurrency, lanes and the device-failure
+ * retry are tm_match_batch's.  TM_ECAP when the total exceeds cap: the first
+ * cap entries are written and out_dest_offsets still holds the full bucket
+ * sizes, so the caller sizes its retry from out_dest_offsets[n_dests + 1].
+ *
+ * TM_EINVAL (before any device work): a null required pointer, n_dests == 0
+ * or n_dests > 65536. */
+int tm_set_dests(tm_index *h, uint64_t n, const uint32_t *values, const uint32_t *dests);
+int tm_fanout_dev(tm_index *h, uint64_t n, const uint64_t *d_hit_offsets, const uint32_t *d_values, uint64_t cap,
+                  const uint32_t *d_dest_of, uint64_t dest_len, uint32_t n_dests,
+                  uint64_t *d_dest_offsets, uint32_t *d_out_topic, uint32_t *d_out_value, void *stream);
+int tm_route_batch(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint64_t *topic_offsets,
+                   uint32_t n_dests, uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
+                   uint64_t cap, uint8_t *out_err);
+
 /* Release the batch scratch kept for `stream` (after its batches finish);
  * a caller that retires a stream calls this.  No reference counterpart. */
 int tm_stream_release(tm_index *h, void *stream);
@@ -445,14 +502,15 @@ int tm_profile_read(tm_index *h, double *walk_ms, double *batch_ms, uint64_t *ba
  * TM_DEBUG_DENSE_WIDE: trie nodes with a child bitmap, and those of them
  * dense enough that the walk probes their child table without it.  (Keys
  * 9-11 named the round-4 one-pass kernel's hooks; 9 and 10 now name these,
- * 11 is retired.) */
+ * 11 is retired.)  TM_DEBUG_FANOUT_GRID (get only): the one-wave blocks of a
+ * fan-out pass (tm_fanout_dev), each owning an equal chunk of the entries. */
 enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES = 3, TM_DEBUG_PHASES = 4,
        TM_DEBUG_FAILED_BATCHES = 5, TM_DEBUG_RETRIED_BATCHES = 6, TM_DEBUG_PATH_PHASES = 7,
        TM_DEBUG_PATH_SMALL = 8, TM_DEBUG_PATH_LANE = 9, TM_DEBUG_SMALL_KERNEL = 10,
        TM_DEBUG_COMBINE = 12, TM_DEBUG_COMBINED_LAUNCHES = 13, TM_DEBUG_COMBINED_BATCHES = 14,
        TM_DEBUG_WIDE_NODES = 15, TM_DEBUG_DENSE_WIDE = 16, TM_DEBUG_CMB_GATHER = 17, TM_DEBUG_CMB_LAND = 18,
        TM_DEBUG_COMMITS = 19, TM_DEBUG_COMMIT_WAITS = 20, TM_DEBUG_COMMIT_FORCED = 21, TM_DEBUG_SMALL_TICKET = 22,
-       TM_DEBUG_CMB_SPIN = 23, TM_DEBUG_PATCH_ZC = 24 };
+       TM_DEBUG_CMB_SPIN = 23, TM_DEBUG_PATCH_ZC = 24, TM_DEBUG_FANOUT_GRID = 25 };
 int tm_debug_set(tm_index *h, uint32_t key, uint64_t value);
 int tm_debug_get(tm_index *h, uint32_t key, uint64_t *value);
 
