@@ -8,6 +8,8 @@ namespace tmx {
 
 // Read-only view of the HBM-resident index (one snapshot per batch; patches
 // are applied in stream order before the batch's kernels run).
+// tm_commit compares two views field by field (tm_host.cpp same_view): a new
+// field goes there as well.
 struct DevIndex {
     const VocabEntry *vocab; uint32_t vmask;
     const uint8_t *wpool;

@@ -2087,7 +2087,25 @@ int tm_apply_deltas(tm_index *ix, uint64_t n, const uint8_t *ops, const uint8_t 
 // drain, up to COMMIT_WAIT; past it -- or with one copy per group -- the
 // patch is published as tm_apply_deltas' are (batches take it in stream
 // order, behind the batches reading that copy).
+// The collect also refreshes every copy's cached view and may ship whole
+// tables to all of them, while a batch queued during that wait skips its own
+// collect (img_hold) and brings its copy up to the old pub_seq only: it would
+// walk with the new view (a smaller depth, a cleared xlen_mask bit, new table
+// pointers) over tables that lack the patch.  So a commit whose collect
+// changed a view or shipped a table whole never waits: it publishes before
+// the lock is released, as if past COMMIT_WAIT.
 constexpr auto COMMIT_WAIT = std::chrono::milliseconds(20);
+
+// what a launch reads of a copy's cached view, field by field (the struct has
+// padding); a field added to DevIndex belongs here too, or a change of it alone
+// would let a commit wait again
+static_assert(sizeof(DevIndex) == 120, "DevIndex changed: compare the new field in same_view");
+static bool same_view(const DevIndex &a, const DevIndex &b) {
+    return a.vocab == b.vocab && a.vmask == b.vmask && a.wpool == b.wpool && a.nodes == b.nodes && a.ctab == b.ctab &&
+           a.vals == b.vals && a.exact == b.exact && a.xmask == b.xmask && a.xfp == b.xfp && a.wseq == b.wseq &&
+           a.wbits == b.wbits && a.wcap == b.wcap && a.depth == b.depth && a.xlen_max == b.xlen_max &&
+           a.xlen_mask == b.xlen_mask && a.hdesc == b.hdesc;
+}
 
 int tm_commit(tm_index *ix, uint64_t n, const uint8_t *ops, const uint8_t *fb, const uint64_t *fo,
               const uint32_t *values, const uint8_t *key_flags, uint64_t *out_epoch) {
@@ -2103,17 +2121,24 @@ int tm_commit(tm_index *ix, uint64_t n, const uint8_t *ops, const uint8_t *fb, c
     const uint64_t tb = g_cmb_timing ? ns_now() : 0;
     std::unique_lock<std::mutex> g(ix->mu);
     const uint64_t tc = g_cmb_timing ? ns_now() : 0;
+    const bool had_view = ix->view_ok;
+    const uint64_t uploads0 = ix->uploads;
+    DevIndex view0[MAX_REPLICAS];
+    for (int r = 0; r < ix->nrep; r++) view0[r] = ix->view[r];
     if ((rc = collect_patch(ix, true))) return rc;
     const uint64_t q = ix->patch_seq;
     if (ix->pub_seq >= q) return TM_OK;   // (nothing to ship: the deltas changed no device word)
     ix->commits++;
+    // more than the one patch uploaded, or a view changed: old tables cannot serve the new views (see above)
+    bool no_wait = !had_view || ix->uploads - uploads0 > 1;
+    for (int r = 0; r < ix->nrep && !no_wait; r++) no_wait = !same_view(view0[r], ix->view[r]);
     const uint64_t td = g_cmb_timing ? ns_now() : 0;
     uint64_t t_idle = 0, t_ship = 0;
     const auto t0 = std::chrono::steady_clock::now();
     bool done[MAX_REPLICAS] = {}, waited = false;
     int left = ix->ngroups;
     for (;;) {
-        const bool late = std::chrono::steady_clock::now() - t0 > COMMIT_WAIT;
+        const bool late = no_wait || std::chrono::steady_clock::now() - t0 > COMMIT_WAIT;
         bool busy[MAX_REPLICAS] = {};   // copies with a batch still reading them (one event query per lane)
         for (auto &l : ix->lanes)
             if (!busy[l->r] && lane_busy(*l)) busy[l->r] = true;
@@ -2130,7 +2155,7 @@ int tm_commit(tm_index *ix, uint64_t n, const uint8_t *ops, const uint8_t *fb, c
                 if (!busy[r] && (pick < 0 || ix->rep[r].applied < ix->rep[pick].applied)) pick = r;
             }
             if (pick < 0 && copies > 1 && !late) continue;   // wait for a copy to drain
-            if (pick >= 0) {
+            if (pick >= 0 && copies > 1) {
                 const uint64_t t0s = g_cmb_timing ? ns_now() : 0;
                 if ((rc = bring_up(ix, pick, q, ix->rep[pick].ps, true))) return rc;
                 if (g_cmb_timing) t_ship += ns_now() - t0s;

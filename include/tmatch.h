@@ -181,8 +181,14 @@ int tm_apply_deltas_ex(tm_index *h, uint64_t n, const uint8_t *ops, const uint8_
  * does), but no batch waits on the GPU for the patch -- with tm_apply_deltas
  * every batch after a delta first waits for the batches still reading the
  * copy it patches.  While every copy has readers, tm_commit waits for one to
- * drain (bounded; past the bound, or with copies = 1, it publishes as
- * tm_apply_deltas does).  Batches do not collect these deltas before
+ * drain (bounded; past the bound, or with copies = 1 -- then whether the copy
+ * has readers or not -- it publishes as tm_apply_deltas does).  It never
+ * waits when the deltas changed more than logged words: a table shipped
+ * whole (growth, a rehash, more than half of it dirty) or a change of what a
+ * launch is told about the tables (their addresses and sizes, the trie's
+ * depth, the lengths binary keys have) reaches every copy at once, so such a
+ * commit publishes at once too, and every batch queued from then on first
+ * brings its copy up.  Batches do not collect these deltas before
  * tm_commit publishes them (they were queued before it returned); a
  * tm_apply_deltas running meanwhile is published with them. */
 int tm_commit(tm_index *h, uint64_t n, const uint8_t *ops, const uint8_t *filter_bytes, const uint64_t *filter_offsets,
@@ -493,7 +499,7 @@ int tm_profile_read(tm_index *h, double *walk_ms, double *batch_ms, uint64_t *ba
  *                           and removed): 0 only, TM_EINVAL otherwise
  * tm_debug_get: those settings; TM_DEBUG_COMMITS / _COMMIT_WAITS / _COMMIT_FORCED:
  * tm_commit patches, those that waited for a copy to drain, and those
- * published without an idle copy; TM_DEBUG_FAILED_BATCHES (one-launch batches whose look-back
+ * published without an idle copy (per device entry; always so with copies = 1); TM_DEBUG_FAILED_BATCHES (one-launch batches whose look-back
  * failed, host API), TM_DEBUG_RETRIED_BATCHES (of those, run again) and the
  * match launches per kernel path: TM_DEBUG_PATH_PHASES (walk, tails, scan,
  * emit), TM_DEBUG_PATH_SMALL (k_walk_small), TM_DEBUG_PATH_LANE (retired:
