@@ -27,7 +27,8 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_matches_filter", "tm_apply_deltas_ex", "tm_read_begin", "tm_read_end", "tm_epoch",
            "tm_create_replicas", "tm_replica_stats", "tm_debug_set", "tm_debug_get", "tm_match_batch32_ex",
            "tm_match_batch32_dev", "tm_matches_filter_ex", "tm_host_alloc_ex", "tm_commit",
-           "tm_match_batch32_pairs", "tm_match_batch_dev_pairs", "tm_set_dests", "tm_fanout_dev", "tm_route_batch")
+           "tm_match_batch32_pairs", "tm_match_batch_dev_pairs", "tm_set_dests", "tm_fanout_dev", "tm_route_batch",
+           "tm_fanout_dev_pairs")
 TM_ALLOC_VRAM = 1
 TM_DEBUG_LB_SPINS, TM_DEBUG_LB_FAIL_BLOCK, TM_DEBUG_LB_LAUNCHES, TM_DEBUG_PHASES = 1, 2, 3, 4
 TM_DEBUG_FAILED_BATCHES, TM_DEBUG_RETRIED_BATCHES = 5, 6
@@ -123,6 +124,7 @@ def load_library(path: Path | None = None):
         "tm_match_batch32_pairs": (i32, [vp, u64, vp, vp, vp, vp, u64, vp]),
         "tm_set_dests": (i32, [vp, u64, vp, vp]),
         "tm_fanout_dev": (i32, [vp, u64, vp, vp, u64, vp, u64, u32, vp, vp, vp, vp]),
+        "tm_fanout_dev_pairs": (i32, [vp, u64, vp, vp, u64, vp, u64, u32, vp, vp, vp, vp]),
         "tm_route_batch": (i32, [vp, u64, vp, vp, u32, vp, vp, vp, u64, vp]),
         "tm_debug_set": (i32, [vp, u32, u64]),
         "tm_debug_get": (i32, [vp, u32, C.POINTER(u64)]),
@@ -407,6 +409,16 @@ class Index:
         unrouted).  d_dest_of None: the table of set_dests."""
         self._check(self._lib.tm_fanout_dev(self._h, n, d_hit, d_vals, cap, d_dest_of, dest_len, n_dests, d_dest_offs,
                                             d_out_topic, d_out_value, stream))
+
+    def fanout_dev_pairs(self, n: int, d_pairs: int, d_vals: int, cap: int, n_dests: int, d_dest_offs: int,
+                         d_out_topic: int, d_out_value: int, d_dest_of: int | None = None, dest_len: int = 0,
+                         stream: int | None = None):
+        """tm_fanout_dev_pairs on device pointers: fanout_dev for a batch given as
+        per-topic (first position, count) u32 pairs (d_pairs 8-byte aligned,
+        [0, 2 n) read; match_batch_dev_pairs / match_batch32_pairs write them):
+        the same outputs as fanout_dev on the CSR the spans stand for."""
+        self._check(self._lib.tm_fanout_dev_pairs(self._h, n, d_pairs, d_vals, cap, d_dest_of, dest_len, n_dests,
+                                                  d_dest_offs, d_out_topic, d_out_value, stream))
 
     def route_batch(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, cap: int | None = None):
         """tm_route_batch -> (dest_offsets u64[n_dests+2], topic u32[total],

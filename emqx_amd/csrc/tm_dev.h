@@ -207,13 +207,27 @@ constexpr uint32_t FO_MAX_DESTS = 65536;
 struct FanoutScratch {
     uint32_t *tab;        // [FO_BINS * FO_GRID] per (bin, block) counts, then their scan per bin
     uint32_t *tot;        // [FO_BINS] the bins' totals
-    uint32_t *t, *v, *b;  // [cap] a first of two passes' (topic, value, bucket)
+    uint32_t *t, *v, *b;  // [cap] a first of two passes' (topic, value, bucket); the pairs form's resolved entries
     uint64_t cap;
+    // the pairs form only (launch_fanout_pairs)
+    uint64_t *voff;       // [voff_cap] the offsets of the CSR the spans stand for (n + 1 used)
+    uint64_t voff_cap;
+    uint64_t *sums;       // [FP_TILES] the topic tiles' entry counts
+    uint32_t *b2;         // [cap] two passes: the resolved entries' buckets (their topics and values wait in the outputs)
 };
+constexpr uint32_t FP_TILES = 1024;
 bool fanout_two_pass(uint32_t n_dests);
 hipError_t launch_fanout(const FanoutScratch &fs, uint64_t n, const uint64_t *hit, const uint32_t *values,
                          uint64_t cap, const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests,
                          uint64_t *dest_offsets, uint32_t *out_topic, uint32_t *out_value, hipStream_t s);
+// The same for per-topic (first position, count) pairs (u32, 8-byte aligned,
+// [0, 2 n) read): topic t's entries are values[pos_t .. pos_t + eff_t), eff_t =
+// min(cnt_t, cap - pos_t) or 0 for pos_t >= cap, in topic order.  Needs
+// fs.cap >= min(cap, 2^32 - 1), fs.voff_cap >= n + 1, fs.sums, and fs.b2 for
+// two passes.
+hipError_t launch_fanout_pairs(const FanoutScratch &fs, uint64_t n, const uint32_t *pairs, const uint32_t *values,
+                               uint64_t cap, const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests,
+                               uint64_t *dest_offsets, uint32_t *out_topic, uint32_t *out_value, hipStream_t s);
 // delta upload: run i copies runs[i].n u32 words from data + runs[i].src to
 // word (dst & PATCH_OFF) of table (dst >> 48), whose device address on the
 // replica being patched is bases.b[table] (the same runs patch every replica)

@@ -45,7 +45,16 @@
 // Bytes per entry and pass: 4 read twice (histogram, scatter) + 4 gathered
 // twice (dest_of) + 8 written -- (topic, value); a first of two passes writes
 // 12 and the second reads 4 + 12.
+//
+// The pairs form (tm_match_batch_dev_pairs' spans; launch_fanout_pairs): two
+// launches scan the spans' effective counts into the offsets of the CSR they
+// stand for, k_fo_resolve writes that CSR's entries as triples with the first
+// digit's histogram, and the scan / scatter kernels above run on the triples
+// (SRC 1) -- 8 B read (pair) + 8 written (offset) per topic, and per entry 4
+// gathered (value) + 4 (dest_of) + 12 written more than a CSR pass.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "tm_dev.h"
 
@@ -101,6 +110,42 @@ __device__ __forceinline__ uint64_t fo_topic_at(const uint64_t *hit, uint64_t n,
         }
     }
     return lo ? lo - 1 : 0;
+}
+
+// The topics of one step's positions p0 + lane (`ok`: below the chunk's end c1),
+// by the whole wave: a window of the next 64 offsets in LDS that each lane
+// searches; lanes whose topic lies beyond it (a run of more than 64 empty
+// topics) search again from the first of them.  tcur: hit[tcur] <= p0 on entry,
+// the step's last topic on return.
+__device__ __forceinline__ uint32_t fo_step_topics(const uint64_t *hit, uint64_t n, uint64_t p0, uint64_t c1, bool ok,
+                                                   uint64_t &tcur, uint64_t *s_win, uint32_t lane) {
+    const uint64_t p = p0 + lane;
+    uint32_t t = 0;
+    bool found = !ok;
+    uint64_t tw = tcur;
+    for (;;) {
+        // the ends of topics tw .. tw + 63; a lane's topic is tw + (how many of them are <= p)
+        const uint64_t idx = tw + 1 + lane;
+        s_win[lane] = idx <= n ? hit[idx] : ~0ull;
+        __syncthreads();
+        if (!found && s_win[63] > p) {
+            uint32_t c = 0;
+#pragma unroll
+            for (uint32_t st = 32; st; st >>= 1)
+                if (s_win[c + st - 1] <= p) c += st;
+            t = (uint32_t)(tw + c);
+            found = true;
+        }
+        __syncthreads();
+        const uint64_t left = __ballot(!found);
+        if (!left) break;
+        // a run of empty topics longer than the window: search again for the first lane left
+        const uint32_t fl = (uint32_t)__builtin_ctzll(left);
+        tw = fo_topic_at(hit, n, p0 + fl, tw + 65, lane);
+    }
+    const uint32_t last = c1 - p0 < 64 ? (uint32_t)(c1 - p0) - 1 : 63u;
+    tcur = __shfl(t, last, 64);
+    return t;
 }
 
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
@@ -204,30 +249,7 @@ __global__ __launch_bounds__(64) void k_fo_scatter(const uint64_t *hit, uint64_t
                 v = in_v[p];
                 b = fo_bucket(v, dest_of, dest_len, n_dests);
             }
-            bool found = !ok;
-            uint64_t tw = tcur;
-            for (;;) {
-                // the ends of topics tw .. tw + 63; a lane's topic is tw + (how many of them are <= p)
-                const uint64_t idx = tw + 1 + lane;
-                s_win[lane] = idx <= n ? hit[idx] : ~0ull;
-                __syncthreads();
-                if (!found && s_win[63] > p) {
-                    uint32_t c = 0;
-#pragma unroll
-                    for (uint32_t st = 32; st; st >>= 1)
-                        if (s_win[c + st - 1] <= p) c += st;
-                    t = (uint32_t)(tw + c);
-                    found = true;
-                }
-                __syncthreads();
-                const uint64_t left = __ballot(!found);
-                if (!left) break;
-                // a run of empty topics longer than the window: search again for the first lane left
-                const uint32_t fl = (uint32_t)__builtin_ctzll(left);
-                tw = fo_topic_at(hit, n, p0 + fl, tw + 65, lane);
-            }
-            const uint32_t last = c1 - p0 < 64 ? (uint32_t)(c1 - p0) - 1 : 63u;
-            tcur = __shfl(t, last, 64);
+            t = fo_step_topics(hit, n, p0, c1, ok, tcur, s_win, lane);
         } else if (ok) {
             v = in_v[p];
             t = in_t[p];
@@ -273,6 +295,115 @@ __global__ __launch_bounds__(256) void k_fo_bounds(const uint64_t *hit, uint64_t
     dest_offsets[b] = lo;
 }
 
+// ---- the pairs form (tm_fanout_dev_pairs): per-topic (first position, count)
+// spans of `values`, disjoint but in any order, with gaps, and cut by cap.
+// Topic t contributes eff_t = min(cnt_t, cap - pos_t) entries (0 for pos_t >=
+// cap); voff = the exclusive scan of eff (64-bit sums) is the CSR the spans
+// stand for, and entry p of it is values[pos_t + (p - voff[t])] for the last
+// t with voff[t] <= p.  k_fo_resolve turns the entries below E = min(voff[n],
+// cap) into (topic, value, bucket) triples in position order, with the first
+// digit's histogram, and the SRC 1 kernels above take it from there.
+
+__device__ __forceinline__ uint32_t fp_eff(uint2 pr, uint64_t cap) {   // (cap <= 2^32 - 1)
+    if (pr.x >= cap) return 0u;
+    const uint64_t room = cap - pr.x;
+    return pr.y < room ? pr.y : (uint32_t)room;
+}
+
+__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t x, uint32_t lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t y = __shfl_up(x, d, 64);
+        if (lane >= (uint32_t)d) x += y;
+    }
+    return x;
+}
+
+// the block's four waves' inclusive totals in s_w -> their sum (256 threads)
+__device__ __forceinline__ uint64_t fp_block_total(const uint64_t *s_w) { return s_w[0] + s_w[1] + s_w[2] + s_w[3]; }
+
+// The scan is tile sums, then every block scans the sums below its own tile
+// itself and adds them back: no block waits for another.  Block k owns the
+// topics [k * tile, (k + 1) * tile); at most FP_TILES blocks.
+__global__ __launch_bounds__(256) void k_fp_sums(const uint2 *pairs, uint64_t n, uint64_t cap, uint64_t tile,
+                                                 uint64_t *sums) {
+    __shared__ uint64_t s_w[4];
+    const uint64_t t0 = (uint64_t)blockIdx.x * tile, t1 = t0 + tile < n ? t0 + tile : n;
+    uint64_t sum = 0;
+    for (uint64_t t = t0 + threadIdx.x; t < t1; t += 256) sum += fp_eff(pairs[t], cap);
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint64_t inc = wave_incl_scan64(sum, lane);
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    if (threadIdx.x == 0) sums[blockIdx.x] = fp_block_total(s_w);
+}
+
+__global__ __launch_bounds__(256) void k_fp_offsets(const uint2 *pairs, uint64_t n, uint64_t cap, uint64_t tile,
+                                                    const uint64_t *sums, uint64_t *voff) {
+    __shared__ uint64_t s_w[4];
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint64_t x = 0;
+    for (uint32_t k = threadIdx.x; k < blockIdx.x; k += 256) x += sums[k];
+    uint64_t inc = wave_incl_scan64(x, lane);
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    uint64_t base = fp_block_total(s_w);   // the entries of the topics below t0
+    __syncthreads();
+    const uint64_t t0 = (uint64_t)blockIdx.x * tile, t1 = t0 + tile < n ? t0 + tile : n;
+    for (uint64_t r = t0; r < t1; r += 256) {
+        const uint64_t t = r + threadIdx.x;
+        const uint64_t e = t < t1 ? fp_eff(pairs[t], cap) : 0u;
+        inc = wave_incl_scan64(e, lane);
+        if (lane == 63) s_w[wv] = inc;
+        __syncthreads();
+        uint64_t exc = base + inc - e;
+        for (uint32_t q = 0; q < wv; q++) exc += s_w[q];
+        if (t < t1) voff[t] = exc;
+        base += fp_block_total(s_w);
+        __syncthreads();
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) voff[n] = base;   // (the last tile is never empty, or n == 0)
+}
+
+// Block k's chunk of [0, E), as in the passes above: each entry's topic from
+// voff (the search of a first CSR pass), its value through the topic's pair,
+// the triple to position p of out_t / out_v / out_b, and the block's histogram
+// of the digit's low `bits` bits into tab -- k_fo_hist<1> on out_b would
+// count the same.
+__global__ __launch_bounds__(64) void k_fo_resolve(const uint64_t *voff, uint64_t n, uint64_t cap, const uint2 *pairs,
+                                                   const uint32_t *values, const uint32_t *dest_of, uint64_t dest_len,
+                                                   uint32_t n_dests, uint32_t bits, uint32_t *tab, uint32_t *out_t,
+                                                   uint32_t *out_v, uint32_t *out_b) {
+    __shared__ uint32_t s_h[FO_BINS];
+    __shared__ uint64_t s_win[64];
+    const uint32_t lane = threadIdx.x, nb = 1u << bits, mask = nb - 1;
+    for (uint32_t i = lane; i < nb; i += 64) s_h[i] = 0;
+    __syncthreads();
+    uint64_t c0, c1, E;
+    fo_chunk(voff, n, cap, blockIdx.x, c0, c1, E);
+    uint64_t tcur = 0;
+    if (c0 < c1) tcur = fo_topic_at(voff, n, c0, 0, lane);
+    for (uint64_t p0 = c0; p0 < c1; p0 += 64) {
+        const uint64_t p = p0 + lane;
+        const bool ok = p < c1;
+        const uint32_t t = fo_step_topics(voff, n, p0, c1, ok, tcur, s_win, lane);
+        if (ok) {
+            uint32_t v = 0;
+            if (t < n) {   // (always: p < voff[n])
+                const uint64_t at = (uint64_t)pairs[t].x + (p - voff[t]);
+                if (at < cap) v = values[at];   // (always: p - voff[t] < eff_t <= cap - pos_t)
+            }
+            const uint32_t b = fo_bucket(v, dest_of, dest_len, n_dests);
+            out_t[p] = t;
+            out_v[p] = v;
+            out_b[p] = b;
+            atomicAdd(&s_h[b & mask], 1u);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = lane; i < nb; i += 64) tab[(uint64_t)i * FO_GRID + blockIdx.x] = s_h[i];
+}
+
 }  // namespace
 
 bool fanout_two_pass(uint32_t n_dests) { return n_dests + 1 > 256; }
@@ -301,6 +432,50 @@ hipError_t launch_fanout(const FanoutScratch &fs, uint64_t n, const uint64_t *hi
     hipLaunchKernelGGL((k_fo_scatter<0, false>), g, b, 0, s, hit, n, cap, values, (const uint32_t *)nullptr,
                        (const uint32_t *)nullptr, dest_of, dest_len, n_dests, 0u, lo, fs.tab, fs.tot, fs.t, fs.v, fs.b,
                        (uint64_t *)nullptr);
+    hipLaunchKernelGGL(k_fo_hist<1>, g, b, 0, s, hit, n, cap, fs.b, dest_of, dest_len, n_dests, lo, hi, fs.tab);
+    hipLaunchKernelGGL(k_fo_scan, dim3(1u << hi), dim3(256), 0, s, fs.tab, fs.tot);
+    hipLaunchKernelGGL((k_fo_scatter<1, true>), g, b, 0, s, hit, n, cap, fs.v, fs.t, fs.b, dest_of, dest_len, n_dests, lo,
+                       hi, fs.tab, fs.tot, out_topic, out_value, (uint32_t *)nullptr, (uint64_t *)nullptr);
+    hipLaunchKernelGGL(k_fo_bounds, dim3((n_dests + 2 + 255) / 256), dim3(256), 0, s, hit, n, cap, out_value, dest_of,
+                       dest_len, n_dests, dest_offsets);
+    return hipGetLastError();
+}
+
+hipError_t launch_fanout_pairs(const FanoutScratch &fs, uint64_t n, const uint32_t *pairs, const uint32_t *values,
+                               uint64_t cap, const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests,
+                               uint64_t *dest_offsets, uint32_t *out_topic, uint32_t *out_value, hipStream_t s) {
+    if (!n_dests || n_dests > FO_MAX_DESTS) return hipErrorInvalidValue;
+    if (!dest_of) dest_len = 0;
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;
+    const bool two = fanout_two_pass(n_dests);
+    if (cap > fs.cap || n + 1 > fs.voff_cap || (two && !fs.b2)) return hipErrorInvalidValue;
+    uint32_t w = 1;
+    while ((n_dests >> w) != 0) w++;
+    // the topics' tiles: at most FP_TILES of them, a multiple of the block each
+    const uint64_t want = std::min<uint64_t>(std::max<uint64_t>((n + FP_TILES - 1) / FP_TILES, 1), FP_TILES);
+    const uint64_t tile = std::max<uint64_t>(((n + want - 1) / want + 255) / 256 * 256, 256);
+    const uint32_t tiles = (uint32_t)std::max<uint64_t>((n + tile - 1) / tile, 1);
+    const uint2 *pr = reinterpret_cast<const uint2 *>(pairs);
+    hipLaunchKernelGGL(k_fp_sums, dim3(tiles), dim3(256), 0, s, pr, n, cap, tile, fs.sums);
+    hipLaunchKernelGGL(k_fp_offsets, dim3(tiles), dim3(256), 0, s, pr, n, cap, tile, fs.sums, fs.voff);
+    const uint64_t *hit = fs.voff;
+    const dim3 g(FO_GRID), b(64);
+    if (!two) {
+        hipLaunchKernelGGL(k_fo_resolve, g, b, 0, s, hit, n, cap, pr, values, dest_of, dest_len, n_dests, w, fs.tab, fs.t,
+                           fs.v, fs.b);
+        hipLaunchKernelGGL(k_fo_scan, dim3(1u << w), dim3(256), 0, s, fs.tab, fs.tot);
+        hipLaunchKernelGGL((k_fo_scatter<1, true>), g, b, 0, s, hit, n, cap, fs.v, fs.t, fs.b, dest_of, dest_len, n_dests,
+                           0u, w, fs.tab, fs.tot, out_topic, out_value, (uint32_t *)nullptr, dest_offsets);
+        return hipGetLastError();
+    }
+    // two passes: the resolved entries wait in the outputs (positions below E
+    // only) and fs.b2, the first pass moves them into the triples
+    const uint32_t lo = (w + 1) / 2, hi = w - lo;
+    hipLaunchKernelGGL(k_fo_resolve, g, b, 0, s, hit, n, cap, pr, values, dest_of, dest_len, n_dests, lo, fs.tab,
+                       out_topic, out_value, fs.b2);
+    hipLaunchKernelGGL(k_fo_scan, dim3(1u << lo), dim3(256), 0, s, fs.tab, fs.tot);
+    hipLaunchKernelGGL((k_fo_scatter<1, false>), g, b, 0, s, hit, n, cap, out_value, out_topic, fs.b2, dest_of, dest_len,
+                       n_dests, 0u, lo, fs.tab, fs.tot, fs.t, fs.v, fs.b, (uint64_t *)nullptr);
     hipLaunchKernelGGL(k_fo_hist<1>, g, b, 0, s, hit, n, cap, fs.b, dest_of, dest_len, n_dests, lo, hi, fs.tab);
     hipLaunchKernelGGL(k_fo_scan, dim3(1u << hi), dim3(256), 0, s, fs.tab, fs.tot);
     hipLaunchKernelGGL((k_fo_scatter<1, true>), g, b, 0, s, hit, n, cap, fs.v, fs.t, fs.b, dest_of, dest_len, n_dests, lo,

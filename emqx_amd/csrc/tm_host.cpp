@@ -1671,7 +1671,8 @@ void free_workspace(Workspace &w) {
 
 void free_lane(Lane &l) {
     free_workspace(l.w);
-    void *dv[] = {l.d_in, l.d_res, l.d_vals, l.d_o64, l.d_h64, l.f.tab, l.f.tot, l.f.t, l.f.v, l.f.b, l.d_ft, l.d_fv, l.d_fo};
+    void *dv[] = {l.d_in, l.d_res, l.d_vals, l.d_o64, l.d_h64, l.f.tab, l.f.tot, l.f.t, l.f.v, l.f.b, l.f.voff, l.f.sums, l.f.b2,
+                  l.d_ft, l.d_fv, l.d_fo};
     for (void *p : dv) if (p) (void)hipFree(p);
     void *pins[] = {l.pin_in, l.pin_out, l.pin_vals};
     for (void *p : pins) if (p) (void)hipHostFree(p);
@@ -1904,7 +1905,7 @@ int drain_lanes(tm_index *ix) {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 11u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 12u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 
@@ -2317,28 +2318,61 @@ int tm_sort_segments(tm_index *ix, uint64_t n, const uint64_t *hit_offs, uint32_
 namespace {
 
 // the fan-out's scratch on a lane: the tables always, the triples of a first
-// pass when n_dests needs two (grow-only; freed with the lane)
-int ensure_fanout(tm_index *ix, Lane &ln, uint32_t n_dests, uint64_t cap) {
+// pass when n_dests needs two (grow-only; freed with the lane).  pairs (a batch
+// of n topics given as spans, tm_fanout_dev_pairs): the triples for every
+// n_dests, the virtual offsets and the tile sums, and a second bucket array
+// when n_dests needs two passes.
+int ensure_fanout(tm_index *ix, Lane &ln, uint32_t n_dests, uint64_t cap, bool pairs = false, uint64_t n = 0) {
     FanoutScratch &f = ln.f;
     if (!f.tab) {
         HIPCHK(ix, hipMalloc(&f.tab, (uint64_t)FO_BINS * FO_GRID * 4));
         HIPCHK(ix, hipMalloc(&f.tot, FO_BINS * 4));
     }
-    if (!fanout_two_pass(n_dests) || (cap <= f.cap && f.t)) return TM_OK;
-    HIPCHK(ix, hipStreamSynchronize(ln.s));   // only this lane's stream uses them
-    for (uint32_t **p : {&f.t, &f.v, &f.b}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    f.cap = 0;
-    const uint64_t c = std::max<uint64_t>(std::min<uint64_t>(cap + cap / 4, 0xFFFFFFFFull), 1024);
-    for (uint32_t **p : {&f.t, &f.v, &f.b})
-        if (hipMalloc(p, c * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ix, TM_ENOMEM, "fan-out: no device memory for a two-pass batch's scratch (12 bytes x cap)");
+    const bool two = fanout_two_pass(n_dests);
+    if (pairs) {
+        if (!f.sums) HIPCHK(ix, hipMalloc(&f.sums, FP_TILES * 8));
+        if (n + 1 > f.voff_cap) {
+            HIPCHK(ix, hipStreamSynchronize(ln.s));
+            if (f.voff) (void)hipFree(f.voff);
+            f.voff = nullptr;
+            f.voff_cap = 0;
+            const uint64_t c = std::max<uint64_t>(n + 1 + n / 4, 1024);
+            if (hipMalloc(&f.voff, c * 8) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(ix, TM_ENOMEM, "fan-out: no device memory for a pairs batch's offsets (8 bytes x n)");
+            }
+            f.voff_cap = c;
         }
-    f.cap = c;
+    }
+    if ((two || pairs) && !(cap <= f.cap && f.t)) {
+        HIPCHK(ix, hipStreamSynchronize(ln.s));   // only this lane's stream uses them
+        for (uint32_t **p : {&f.t, &f.v, &f.b, &f.b2}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        f.cap = 0;
+        const uint64_t c = std::max<uint64_t>(std::min<uint64_t>(cap + cap / 4, 0xFFFFFFFFull), 1024);
+        for (uint32_t **p : {&f.t, &f.v, &f.b})
+            if (hipMalloc(p, c * 4) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(ix, TM_ENOMEM, "fan-out: no device memory for the batch's scratch (12 bytes x cap)");
+            }
+        f.cap = c;
+    }
+    if (two && pairs && !f.b2 && hipMalloc(&f.b2, f.cap * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ix, TM_ENOMEM, "fan-out: no device memory for a two-pass pairs batch's scratch (16 bytes x cap)");
+    }
     return TM_OK;
+}
+
+// the lane a fan-out on stream s uses: the one the stream's match batches use, if any
+int fanout_lane(tm_index *ix, hipStream_t s, int grp, Lane *&ln) {
+    for (auto &l : ix->lanes)
+        if (!l->owned && l->s == s && ix->rep[l->r].group == grp) { ln = l.get(); ln->tick = ++ix->tick; return TM_OK; }
+    int r = 0;
+    while (ix->rep[r].group != grp) r++;
+    return dev_lane(ix, s, r, ln);
 }
 
 // The index's own value -> destination table on group g, current as of now,
@@ -2451,16 +2485,32 @@ int tm_fanout_dev(tm_index *ix, uint64_t n, const uint64_t *hit_offs, const uint
     Lane *ln = nullptr;
     int rc, grp = 0;
     if ((rc = dev_group(ix, grp))) return rc;
-    for (auto &l : ix->lanes)   // the lane the stream's match batches use, if any
-        if (!l->owned && l->s == s && ix->rep[l->r].group == grp) { ln = l.get(); ln->tick = ++ix->tick; break; }
-    if (!ln) {
-        int r = 0;
-        while (ix->rep[r].group != grp) r++;
-        if ((rc = dev_lane(ix, s, r, ln))) return rc;
-    }
+    if ((rc = fanout_lane(ix, s, grp, ln))) return rc;
     if ((rc = ensure_fanout(ix, *ln, n_dests, cap))) return rc;
     if (!dest_of && (rc = dest_upload(ix, grp, s, dest_of, dest_len))) return rc;
     HIPCHK(ix, launch_fanout(ln->f, n, hit_offs, vals, cap, dest_of, dest_len, n_dests, dest_offs, out_topic, out_value, s));
+    return batch_done(ix, *ln);
+}
+
+int tm_fanout_dev_pairs(tm_index *ix, uint64_t n, const uint32_t *pairs, const uint32_t *vals, uint64_t cap,
+                        const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests, uint64_t *dest_offs,
+                        uint32_t *out_topic, uint32_t *out_value, void *stream) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_fanout_dev_pairs: null handle");
+    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_fanout_dev_pairs: n_dests must be 1 .. 65536");
+    if (!pairs || !dest_offs || (cap && (!vals || !out_topic || !out_value)))
+        return fail(ix, TM_EINVAL, "tm_fanout_dev_pairs: null buffer");
+    if ((uintptr_t)pairs & 7) return fail(ix, TM_EINVAL, "tm_fanout_dev_pairs: d_pairs must be 8-byte aligned");
+    if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_fanout_dev_pairs: too many topics");
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
+    std::lock_guard<std::mutex> g(ix->mu);
+    hipStream_t s = pick_stream(ix, stream);
+    Lane *ln = nullptr;
+    int rc, grp = 0;
+    if ((rc = dev_group(ix, grp))) return rc;
+    if ((rc = fanout_lane(ix, s, grp, ln))) return rc;
+    if ((rc = ensure_fanout(ix, *ln, n_dests, cap, true, n))) return rc;
+    if (!dest_of && (rc = dest_upload(ix, grp, s, dest_of, dest_len))) return rc;
+    HIPCHK(ix, launch_fanout_pairs(ln->f, n, pairs, vals, cap, dest_of, dest_len, n_dests, dest_offs, out_topic, out_value, s));
     return batch_done(ix, *ln);
 }
 

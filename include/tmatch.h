@@ -381,7 +381,8 @@ int tm_sort_segments(tm_index *h, uint64_t n, const uint64_t *d_hit_offsets, uin
  *
  * tm_fanout_dev: device buffers, asynchronous on `stream`.  Input: any device
  * CSR -- d_hit_offsets[n + 1] and d_values as tm_match_batch_dev or
- * tm_merge_shards write them (NOT tm_match_batch_dev_pairs' pairs: its spans
+ * tm_merge_shards write them (tm_match_batch_dev_pairs' and
+ * tm_match_batch32_pairs' pairs go to tm_fanout_dev_pairs below: their spans
  * are not in topic order) -- and d_dest_of[dest_len] (NULL: the index's own
  * table, dest_len ignored).  The entry at position p < min(d_hit_offsets[n],
  * cap) has topic t (the segment holding p), value v = d_values[p] and bucket
@@ -407,12 +408,41 @@ int tm_sort_segments(tm_index *h, uint64_t n, const uint64_t *d_hit_offsets, uin
  * cap entries are written and out_dest_offsets still holds the full bucket
  * sizes, so the caller sizes its retry from out_dest_offsets[n_dests + 1].
  *
- * TM_EINVAL (before any device work): a null required pointer, n_dests == 0
- * or n_dests > 65536. */
+ * tm_fanout_dev_pairs (ABI minor 12): tm_fanout_dev for a batch given as
+ * per-topic (first position, count) pairs, as tm_match_batch_dev_pairs and
+ * tm_match_batch32_pairs write them; everything else (buffers, stream, lanes,
+ * scratch, thread safety, d_dest_of == NULL) as tm_fanout_dev.  d_pairs is u32
+ * and 8-byte aligned; for topic t, pos_t = d_pairs[2 t] and cnt_t =
+ * d_pairs[2 t + 1].  Only entries [0, 2 n) are read (the producers' totals and
+ * extent after them are neither trusted nor needed).  cap (clamped to
+ * 2^32 - 1) is the size of d_values and of both output arrays.  Definition:
+ *   eff_t = 0 if pos_t >= cap, else min(cnt_t, cap - pos_t);
+ *   the virtual CSR is hit'[t] = the sum of eff_u for u < t (64-bit sums: no
+ *   input wraps) and vals'[hit'[t] + j] = d_values[pos_t + j];
+ *   the outputs are exactly what tm_fanout_dev(n, hit', vals', cap, ...)
+ *   writes: E = min(hit'[n], cap) entries, bucket b at [d_dest_offsets[b],
+ *   d_dest_offsets[b + 1]) in ascending topic order, traversal order inside a
+ *   topic, d_dest_offsets[n_dests + 1] = E, bucket n_dests the values without
+ *   a destination; nothing at or past E is written in either output array,
+ *   nothing past d_dest_offsets[n_dests + 1].
+ * So no d_values word at or past cap is ever read; overlapping or repeated
+ * spans are defined (read twice, dropped once the virtual position reaches
+ * cap) and can never make the kernels write outside the outputs; the inputs
+ * are not modified.  Three launches more than tm_fanout_dev (two scan the
+ * effective counts, no block waiting for another; one resolves the entries),
+ * and the stream's scratch holds 8 bytes x n and 12 bytes x cap for every
+ * n_dests, 16 x cap for two passes (TM_ENOMEM if that cannot be had).
+ *
+ * TM_EINVAL (before any device work): a null handle, a null required pointer,
+ * n_dests == 0 or n_dests > 65536, n >= 2^32 - 1, d_pairs not 8-byte
+ * aligned. */
 int tm_set_dests(tm_index *h, uint64_t n, const uint32_t *values, const uint32_t *dests);
 int tm_fanout_dev(tm_index *h, uint64_t n, const uint64_t *d_hit_offsets, const uint32_t *d_values, uint64_t cap,
                   const uint32_t *d_dest_of, uint64_t dest_len, uint32_t n_dests,
                   uint64_t *d_dest_offsets, uint32_t *d_out_topic, uint32_t *d_out_value, void *stream);
+int tm_fanout_dev_pairs(tm_index *h, uint64_t n, const uint32_t *d_pairs, const uint32_t *d_values, uint64_t cap,
+                        const uint32_t *d_dest_of, uint64_t dest_len, uint32_t n_dests,
+                        uint64_t *d_dest_offsets, uint32_t *d_out_topic, uint32_t *d_out_value, void *stream);
 int tm_route_batch(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint64_t *topic_offsets,
                    uint32_t n_dests, uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
                    uint64_t cap, uint8_t *out_err);

@@ -18,6 +18,22 @@ warm-up, then --reps repetitions, the two interleaved; median and spread
 4 read (value) + 4 gathered (dest_of) + 8 written (topic, value), plus the
 n + 1 offsets read and the n_dests + 2 written.  One JSON line per destination
 count on stdout.
+
+--form csr|pairs|both (default csr: the lines above, unchanged).  pairs / both
+add, per destination count, the same batch matched with
+tm_match_batch_dev_pairs (its cap sized in an untimed pass: the CSR's total +
+4096 x the most hits of one topic, the extent checked against it) and
+
+  fanout_call  tm_fanout_dev on the CSR against tm_fanout_dev_pairs on the
+               pairs, outputs compared first (they must be identical)
+  pipeline     match + fan-out on one stream: tm_match_batch_dev +
+               tm_fanout_dev against tm_match_batch_dev_pairs +
+               tm_fanout_dev_pairs
+
+timed the same way (the two forms alternating), and one synthetic line with
+no index (synthetic_skew): the same number of entries over the same number of
+topics once spread evenly and once with 64 topics holding half of them, both
+calls on each -- what skew costs.  --form pairs leaves the torch line out.
 """
 import argparse
 import json
@@ -50,6 +66,125 @@ def stats(ms):
             "max_ms": round(float(a[-1]), 4)}
 
 
+def timed_pair(torch, fa, fb, warmup, reps):
+    """fa and fb alternating, HIP events around each -> (ms of fa, ms of fb)"""
+    for _ in range(warmup):
+        fa()
+        fb()
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    for _ in range(reps):
+        ev[0].record()
+        fa()
+        ev[1].record()
+        fb()
+        ev[2].record()
+        torch.cuda.synchronize()
+        ta.append(ev[0].elapsed_time(ev[1]))
+        tb.append(ev[1].elapsed_time(ev[2]))
+    return ta, tb
+
+
+def both_forms(torch, ix, a, s, n, d_blob, d_offs, d_hit, d_vals, cap, d_err, total, most, n_dests, dest_of, nvals, fs_len):
+    """the fanout_call and pipeline lines of one destination count"""
+    dev = d_vals.device
+    cap_p = total + 4096 * most
+    d_pairs = torch.zeros(2 * n + 2, dtype=torch.int32, device=dev)
+    d_pv = torch.zeros(cap_p, dtype=torch.int32, device=dev)
+    outs = [(torch.zeros(n_dests + 2, dtype=torch.int64, device=dev), torch.zeros(total, dtype=torch.int32, device=dev),
+             torch.zeros(total, dtype=torch.int32, device=dev)) for _ in range(2)]
+
+    def m_csr():
+        ix.match_batch_dev(n, d_blob.data_ptr(), d_offs.data_ptr(), d_hit.data_ptr(), d_vals.data_ptr(), cap,
+                           d_err.data_ptr(), s)
+
+    def m_pairs():
+        ix.match_batch_dev_pairs(n, d_blob.data_ptr(), d_offs.data_ptr(), d_pairs.data_ptr(), d_pv.data_ptr(), cap_p,
+                                 d_err.data_ptr(), s)
+
+    def f_csr():
+        o = outs[0]
+        ix.fanout_dev(n, d_hit.data_ptr(), d_vals.data_ptr(), total, n_dests, o[0].data_ptr(), o[1].data_ptr(),
+                      o[2].data_ptr(), dest_of.data_ptr(), nvals, s)
+
+    def f_pairs():
+        o = outs[1]
+        ix.fanout_dev_pairs(n, d_pairs.data_ptr(), d_pv.data_ptr(), cap_p, n_dests, o[0].data_ptr(), o[1].data_ptr(),
+                            o[2].data_ptr(), dest_of.data_ptr(), nvals, s)
+
+    m_pairs()
+    torch.cuda.synchronize()
+    assert int(d_pairs[2 * n]) & 0xFFFFFFFF == total and int(d_pairs[2 * n + 1]) & 0xFFFFFFFF <= cap_p, \
+        "pairs: total differs or values dropped"
+    f_csr()
+    f_pairs()
+    torch.cuda.synchronize()
+    assert all(torch.equal(x, y) for x, y in zip(*outs)), f"n_dests {n_dests}: the two forms' outputs differ"
+    passes = 1 if n_dests + 1 <= 256 else 2
+    base = {"tool": "fanout_bench", "filters": fs_len, "topics": n, "entries": total, "n_dests": n_dests,
+            "passes": passes, "reps": a.reps, "pairs_cap": cap_p}
+    tc, tp = timed_pair(torch, f_csr, f_pairs, a.warmup, a.reps)
+    c, q = stats(tc), stats(tp)
+    print(json.dumps({**base, "kind": "fanout_call", "csr": c, "pairs": q,
+                      "pairs_over_csr": round(q["median_ms"] / c["median_ms"], 3), "identical": True}), flush=True)
+    tc, tp = timed_pair(torch, lambda: (m_csr(), f_csr()), lambda: (m_pairs(), f_pairs()), a.warmup, a.reps)
+    torch.cuda.synchronize()
+    assert all(torch.equal(x, y) for x, y in zip(*outs)), f"n_dests {n_dests}: the two pipelines' outputs differ"
+    c, q = stats(tc), stats(tp)
+    print(json.dumps({**base, "kind": "pipeline", "csr": c, "pairs": q,
+                      "pairs_over_csr": round(q["median_ms"] / c["median_ms"], 3),
+                      "csr_topics_per_s": round(n / (c["median_ms"] * 1e-3), 1),
+                      "pairs_topics_per_s": round(n / (q["median_ms"] * 1e-3), 1), "identical": True}), flush=True)
+
+
+def synthetic_skew(torch, ix, a, s, n, total, n_dests=16):
+    """no index: `total` entries over n topics, spread evenly / 64 topics holding half of them; both calls on each"""
+    dev = torch.device("cuda")
+    rng = np.random.default_rng(11)
+    nvals = 1 << 20
+    dest_of = torch.from_numpy(rng.integers(0, n_dests, nvals, dtype=np.int64).astype(np.int32)).to(dev)
+    res = {}
+    for name in ("even", "skewed"):
+        lens = np.full(n, total // n, np.int64)
+        lens[: total - int(lens.sum())] += 1
+        if name == "skewed":
+            lens = np.full(n, (total // 2) // n, np.int64)
+            heavy = np.arange(64) * (n // 64)
+            lens[heavy] += (total - int(lens.sum())) // 64
+            lens[0] += total - int(lens.sum())
+        hit = np.zeros(n + 1, np.int64)
+        hit[1:] = np.cumsum(lens)
+        vals = rng.integers(0, nvals, total, dtype=np.int64).astype(np.int32)
+        d_hit = torch.from_numpy(hit).to(dev)
+        d_vals = torch.from_numpy(vals).to(dev)
+        d_pairs = torch.from_numpy(np.stack([hit[:-1], lens], axis=1).astype(np.uint32).view(np.int32).reshape(-1)).to(dev)
+        outs = [(torch.zeros(n_dests + 2, dtype=torch.int64, device=dev), torch.zeros(total, dtype=torch.int32, device=dev),
+                 torch.zeros(total, dtype=torch.int32, device=dev)) for _ in range(2)]
+
+        def f_csr():
+            o = outs[0]
+            ix.fanout_dev(n, d_hit.data_ptr(), d_vals.data_ptr(), total, n_dests, o[0].data_ptr(), o[1].data_ptr(),
+                          o[2].data_ptr(), dest_of.data_ptr(), nvals, s)
+
+        def f_pairs():
+            o = outs[1]
+            ix.fanout_dev_pairs(n, d_pairs.data_ptr(), d_vals.data_ptr(), total, n_dests, o[0].data_ptr(), o[1].data_ptr(),
+                                o[2].data_ptr(), dest_of.data_ptr(), nvals, s)
+
+        f_csr()
+        f_pairs()
+        torch.cuda.synchronize()
+        assert all(torch.equal(x, y) for x, y in zip(*outs)), f"synthetic {name}: the two forms' outputs differ"
+        tc, tp = timed_pair(torch, f_csr, f_pairs, a.warmup, a.reps)
+        res[name] = {"most_hits": int(lens.max()), "csr": stats(tc), "pairs": stats(tp)}
+    print(json.dumps({"tool": "fanout_bench", "kind": "synthetic_skew", "topics": n, "entries": total, "n_dests": n_dests,
+                      "reps": a.reps, **res,
+                      "skew_cost_csr": round(res["skewed"]["csr"]["median_ms"] / res["even"]["csr"]["median_ms"], 3),
+                      "skew_cost_pairs": round(res["skewed"]["pairs"]["median_ms"] / res["even"]["pairs"]["median_ms"], 3)}),
+          flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--filters", type=int, default=1_000_000)
@@ -57,6 +192,7 @@ def main():
     p.add_argument("--reps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--dests", type=int, nargs="+", default=[16, 4096])
+    p.add_argument("--form", choices=["csr", "pairs", "both"], default="csr")
     a = p.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -82,10 +218,16 @@ def main():
     assert 0 < total <= cap, f"hit total {total} against cap {cap}"
     nvals = int(fs.vals.max()) + 1
     assert int(d_vals[:total].max()) < nvals and int(d_vals[:total].min()) >= 0
+    most = int((d_hit[1:] - d_hit[:-1]).max())
     rng = np.random.default_rng(7)
     for n_dests in a.dests:
         # every value routed, the destinations uniform: a cluster's nodes / a deployment's groups
         dest_of = torch.from_numpy(rng.integers(0, n_dests, nvals, dtype=np.int64).astype(np.uint32).view(np.int32)).to(dev)
+        if a.form != "csr":
+            both_forms(torch, ix, a, s, n, d_blob, d_offs, d_hit, d_vals, cap, d_err, total, most, n_dests, dest_of, nvals,
+                       len(fs))
+            if a.form == "pairs":
+                continue
         o_offs = torch.zeros(n_dests + 2, dtype=torch.int64, device=dev)
         o_topic = torch.zeros(total, dtype=torch.int32, device=dev)
         o_value = torch.zeros(total, dtype=torch.int32, device=dev)
@@ -128,6 +270,8 @@ def main():
                           "hip_algorithmic_GBps": round(nbytes / (h["median_ms"] * 1e-3) / 1e9, 1),
                           "identical": True}), flush=True)
         assert h["median_ms"] < t["median_ms"], f"n_dests {n_dests}: the HIP path is not faster than the torch composition"
+    if a.form != "csr":
+        synthetic_skew(torch, ix, a, s, n, total)
 
 
 if __name__ == "__main__":
