@@ -31,6 +31,8 @@ typedef struct { void *p; uint64_t cap; uint32_t flags; } tmn_buf;   /* flags: w
 typedef struct tmn_set {         /* one caller's batch buffers (tm_host_alloc: the batch runs in place) */
     tmn_buf blob, offs, hit, vals, err, uniq;   /* offs, hit: u32 (tm_match_batch32_ex) */
     tmn_buf offs64;                              /* tm_first_batch's u64 offsets */
+    tmn_buf rdoff, rtopic;                       /* tmn_route (tmatch_nif_route.h): bucket offsets, topic indices (u32) */
+    uint32_t route_dests;                        /* n_dests of the set's last tmn_route */
     uint32_t in_flags;           /* the pool's input placement (tmn_pool.in_flags) */
     uint64_t reruns;             /* batches rerun after TM_ECAP (diagnostics) */
     struct tmn_set *next;

@@ -28,7 +28,7 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_create_replicas", "tm_replica_stats", "tm_debug_set", "tm_debug_get", "tm_match_batch32_ex",
            "tm_match_batch32_dev", "tm_matches_filter_ex", "tm_host_alloc_ex", "tm_commit",
            "tm_match_batch32_pairs", "tm_match_batch_dev_pairs", "tm_set_dests", "tm_fanout_dev", "tm_route_batch",
-           "tm_fanout_dev_pairs")
+           "tm_fanout_dev_pairs", "tm_route_batch32")
 TM_ALLOC_VRAM = 1
 TM_DEBUG_LB_SPINS, TM_DEBUG_LB_FAIL_BLOCK, TM_DEBUG_LB_LAUNCHES, TM_DEBUG_PHASES = 1, 2, 3, 4
 TM_DEBUG_FAILED_BATCHES, TM_DEBUG_RETRIED_BATCHES = 5, 6
@@ -43,6 +43,7 @@ TM_DEBUG_SMALL_TICKET = 22
 TM_DEBUG_CMB_SPIN = 23
 TM_DEBUG_PATCH_ZC = 24
 TM_DEBUG_FANOUT_GRID = 25   # (get only) one-wave blocks of a fan-out pass
+TM_DEBUG_ROUTE_ONE, TM_DEBUG_ROUTE_GRID = 26, 27   # (get only) route_batch32 calls per fan-out path
 MAX_DESTS = 65536           # tm_fanout_dev / tm_route_batch: n_dests is 1 .. MAX_DESTS
 
 
@@ -126,6 +127,7 @@ def load_library(path: Path | None = None):
         "tm_fanout_dev": (i32, [vp, u64, vp, vp, u64, vp, u64, u32, vp, vp, vp, vp]),
         "tm_fanout_dev_pairs": (i32, [vp, u64, vp, vp, u64, vp, u64, u32, vp, vp, vp, vp]),
         "tm_route_batch": (i32, [vp, u64, vp, vp, u32, vp, vp, vp, u64, vp]),
+        "tm_route_batch32": (i32, [vp, u64, vp, vp, u32, vp, vp, vp, u64, vp]),
         "tm_debug_set": (i32, [vp, u32, u64]),
         "tm_debug_get": (i32, [vp, u32, C.POINTER(u64)]),
     }
@@ -445,6 +447,29 @@ class Index:
             self._check(rc)
             total = int(doff[-1])
             return doff, topic[:total], vals[:total], err[:n]
+
+    def route_batch32(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, out, cap: int | None = None):
+        """tm_route_batch32: route_batch with u32 topic offsets in and u32 bucket
+        offsets out.  out = (dest_offsets u32[>= n_dests+2], topic u32[cap],
+        values u32[cap], err u8[>= n]) -> (dest_offsets[:n_dests+2],
+        topic[:total], values[:total], err[:n]) as views; in place (no staging,
+        one fan-out launch) when every array comes from host_array() and the
+        batch is a micro-batch (include/tmatch.h).  cap: use only that many
+        entries of topic / values (default: all).  Raises TmError(TM_ECAP) when
+        the entries do not fit (the offsets are valid: the total is the last)."""
+        n = len(offs) - 1
+        doff, topic, vals, err = out
+        if offs.dtype != np.uint32 or doff.dtype != np.uint32 or topic.dtype != np.uint32 or vals.dtype != np.uint32 \
+                or err.dtype != np.uint8 or len(doff) < n_dests + 2 or len(err) < n:
+            raise ValueError("route_batch32: u32 offsets and large enough outputs of the right dtype expected")
+        if cap is None:
+            cap = min(len(topic), len(vals))
+        if cap > min(len(topic), len(vals)):
+            raise ValueError("route_batch32: cap exceeds the output arrays")
+        self._check(self._lib.tm_route_batch32(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff), _ptr(topic),
+                                               _ptr(vals), cap, _ptr(err)))
+        total = int(doff[n_dests + 1])
+        return doff[: n_dests + 2], topic[:total], vals[:total], err[:n]
 
     def release_stream(self, stream: int | None):
         """Drop the batch scratch the library keeps for `stream`."""

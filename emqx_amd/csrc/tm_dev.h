@@ -228,6 +228,25 @@ hipError_t launch_fanout(const FanoutScratch &fs, uint64_t n, const uint64_t *hi
 hipError_t launch_fanout_pairs(const FanoutScratch &fs, uint64_t n, const uint32_t *pairs, const uint32_t *values,
                                uint64_t cap, const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests,
                                uint64_t *dest_offsets, uint32_t *out_topic, uint32_t *out_value, hipStream_t s);
+// A micro-batch's fan-out in ONE launch of ONE workgroup (k_fo_one;
+// tm_route_batch32): launch_fanout_pairs' definition with `vcap` bounding the
+// spans (eff_t = min(cnt_t, vcap - pos_t)) and `cap` only what is stored --
+// entries whose slot is >= cap are counted in dest_offsets but not written.
+// dest_offsets (u32[n_dests + 2]), out_topic and out_value may be mapped host
+// memory.  status[FO1_ST_STATE] = FO1_DONE, or FO1_TOO_LARGE when n >
+// FO1_TOPICS, n_dests + 1 > 256 or the spans hold more than FO1_ENTRIES
+// entries: nothing but the status words is written then, and the caller takes
+// launch_fanout_pairs.  status[FO1_ST_TOTAL] = pairs[2 n] either way (0 for
+// n == 0): the matcher's total, for the caller's capacity checks.
+constexpr uint32_t FO1_TOPICS = 8192;
+constexpr uint32_t FO1_ENTRIES = 16384;
+constexpr uint32_t FO1_BLOCK = 1024;
+constexpr uint32_t FO1_MAX_DESTS = 255;        // n_dests + 1 <= 256 buckets: one digit
+enum { FO1_ST_STATE = 0, FO1_ST_TOTAL = 1, FO1_ST_WORDS = 2 };
+enum : uint32_t { FO1_DONE = 1, FO1_TOO_LARGE = 2 };
+hipError_t launch_fanout_one(uint64_t n, const uint32_t *pairs, const uint32_t *values, uint64_t vcap,
+                             const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests, uint32_t *dest_offsets,
+                             uint32_t *out_topic, uint32_t *out_value, uint64_t cap, uint32_t *status, hipStream_t s);
 // delta upload: run i copies runs[i].n u32 words from data + runs[i].src to
 // word (dst & PATCH_OFF) of table (dst >> 48), whose device address on the
 // replica being patched is bases.b[table] (the same runs patch every replica)

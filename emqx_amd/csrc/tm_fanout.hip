@@ -404,7 +404,226 @@ __global__ __launch_bounds__(64) void k_fo_resolve(const uint64_t *voff, uint64_
     for (uint32_t i = lane; i < nb; i += 64) tab[(uint64_t)i * FO_GRID + blockIdx.x] = s_h[i];
 }
 
+// ---- a micro-batch in one launch (tm_route_batch32): ONE workgroup of
+// FO1_BLOCK threads does the whole pairs-form fan-out of up to FO1_TOPICS
+// topics and FO1_ENTRIES entries, so no block waits for another and nothing
+// passes through global scratch:
+//   1. the scan of eff_t (FO1_TPT topics a thread) into s_voff, each non-empty
+//      topic's head (its index) marked at its first position; a batch whose
+//      spans hold more than FO1_ENTRIES entries ends here with FO1_TOO_LARGE;
+//   2. wave w owns the positions [w * C, (w + 1) * C) of [0, E), C = ceil(E /
+//      16) rounded up to 64: per entry the topic (the last head at or before
+//      it: a wave max-scan), the value through the topic's pair and the
+//      bucket, kept in registers (FO1_STEPS entries a lane) and counted into
+//      the wave's own 256-bin row (fo1_partition: steps 2 to 4);
+//   3. per bin the exclusive scan over the waves, then over the bins: the
+//      bucket offsets (written out) and every wave's running bases;
+//   4. k_fo_scatter's peer-mask step per wave into the LDS image of the two
+//      output arrays -- stable because waves, steps and lanes are in position
+//      order; only waves synchronise, each on its own row;
+//   5. the image's first min(E, cap) entries to the outputs, coalesced: mapped
+//      host memory takes whole lines instead of 4-byte scattered stores.
+constexpr uint32_t FO1_WAVES = FO1_BLOCK / 64;
+constexpr uint32_t FO1_STEPS = FO1_ENTRIES / FO1_BLOCK;   // 64-entry steps of a wave, at most
+constexpr uint32_t FO1_TPT = FO1_TOPICS / FO1_BLOCK;      // topics per thread of the scan
+constexpr uint32_t FO1_BINS = FO1_MAX_DESTS + 1;
+static_assert(FO1_ENTRIES % FO1_BLOCK == 0 && FO1_TOPICS % FO1_BLOCK == 0, "k_fo_one: whole steps");
+static_assert(FO1_TOPICS <= 65536, "k_fo_one: topics are staged as 16 bits");
+static_assert(FO1_BINS == 256 && FO1_BINS <= FO1_BLOCK, "k_fo_one: one thread per bin, four waves of them");
+
+__device__ __forceinline__ void fo_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Steps 2 to 4 of k_fo_one for waves of at most S 64-entry steps.  Each
+// sub-step runs over all S steps before the next begins, so a lane's S loads
+// of each level (pair, value, destination) are in flight together: three
+// memory latencies a wave, not three a step.
+template <uint32_t S>
+__device__ __forceinline__ void fo1_partition(const uint2 *pairs, uint32_t n, const uint32_t *values, uint64_t vcap,
+                                              const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests,
+                                              uint32_t bits, uint32_t *dest_offsets, uint32_t E, uint32_t C,
+                                              const uint32_t *s_voff, uint32_t *s_h, uint32_t *s_bw, uint32_t *s_ov,
+                                              uint16_t *s_ot) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t c0 = wv * C < E ? wv * C : E, c1 = c0 + C < E ? c0 + C : E;
+    uint32_t *my_h = s_h + wv * FO1_BINS;
+    // 2. the wave's entries into registers, counted per bucket
+    uint32_t rt[S], rv[S], rb[S];   // topic, then its span's first position / the value, bucket
+    // The topic of the chunk's first position: the last t of [0, n) with
+    // s_voff[t] <= c0 (s_voff[0] = 0), 13 branch-free probes, the same in every
+    // lane.  From there the heads in s_ot (the topic at the first position of
+    // every non-empty topic, zero elsewhere) carry it forward: a position's
+    // topic is the last head at or before it, a running maximum since the heads
+    // ascend -- one wave scan a step instead of a search per entry.
+    uint32_t carry = 0;
+    for (uint32_t st = FO1_TOPICS / 2; st; st >>= 1) {
+        const uint32_t m = carry + st;
+        if (m < n && s_voff[m] <= c0) carry = m;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < S; k++) {
+        const uint32_t p = c0 + k * 64 + lane;
+        uint32_t x = p < c1 ? s_ot[p] : 0u;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t y = __shfl_up(x, d, 64);
+            if (lane >= (uint32_t)d && y > x) x = y;
+        }
+        if (carry > x) x = carry;
+        carry = __shfl(x, 63, 64);
+        rt[k] = x;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < S; k++) {
+        const bool ok = c0 + k * 64 + lane < c1;
+        rv[k] = ok ? pairs[rt[k]].x : 0u;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < S; k++) {
+        const uint32_t p = c0 + k * 64 + lane;
+        const uint64_t at = (uint64_t)rv[k] + (p - s_voff[rt[k]]);
+        rv[k] = p < c1 && at < vcap ? values[at] : 0u;   // (at < vcap always: p - voff[t] < eff_t <= vcap - pos_t)
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < S; k++) {
+        const bool ok = c0 + k * 64 + lane < c1;
+        rb[k] = ok ? fo_bucket(rv[k], dest_of, dest_len, n_dests) : 0u;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < S; k++)
+        if (c0 + k * 64 + lane < c1) atomicAdd(&my_h[rb[k]], 1u);
+    __syncthreads();
+    // 3. bin b: its counts' exclusive scan over the waves, then over the bins
+    uint32_t tot = 0;
+    if (tid < FO1_BINS)
+        for (uint32_t q = 0; q < FO1_WAVES; q++) {
+            const uint32_t x = s_h[q * FO1_BINS + tid];
+            s_h[q * FO1_BINS + tid] = tot;
+            tot += x;
+        }
+    const uint32_t binc = wave_incl_scan(tot, lane);
+    if (tid < FO1_BINS && lane == 63) s_bw[wv] = binc;
+    __syncthreads();
+    if (tid < FO1_BINS) {
+        uint32_t exc = binc - tot;
+        for (uint32_t q = 0; q < wv; q++) exc += s_bw[q];
+        for (uint32_t q = 0; q < FO1_WAVES; q++) s_h[q * FO1_BINS + tid] += exc;
+        if (tid <= n_dests) dest_offsets[tid] = exc;
+    }
+    if (tid == 0) dest_offsets[n_dests + 1] = E;
+    __syncthreads();
+    // 4. the stable scatter, into the outputs' image
+#pragma unroll
+    for (uint32_t k = 0; k < S; k++) {
+        if (k * 64 >= C) break;   // (block-uniform)
+        const bool ok = c0 + k * 64 + lane < c1;
+        const uint32_t d = rb[k];
+        uint64_t peers = __ballot(ok);
+        for (uint32_t q = 0; q < bits; q++) {
+            const bool bit = (d >> q) & 1u;
+            const uint64_t m = __ballot(ok && bit);
+            peers &= bit ? m : ~m;
+        }
+        uint32_t dst = 0;
+        if (ok) dst = my_h[d] + (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
+        fo_wave_sync();
+        if (ok && (peers >> lane) == 1ull) my_h[d] += (uint32_t)__popcll(peers);
+        fo_wave_sync();
+        if (ok && dst < E) {   // (always, as in k_fo_scatter)
+            s_ov[dst] = rv[k];
+            s_ot[dst] = (uint16_t)rt[k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(FO1_BLOCK) void k_fo_one(const uint2 *pairs, uint64_t n, const uint32_t *values,
+                                                      uint64_t vcap, const uint32_t *dest_of, uint64_t dest_len,
+                                                      uint32_t n_dests, uint32_t bits, uint32_t *dest_offsets,
+                                                      uint32_t *out_t, uint32_t *out_v, uint64_t cap,
+                                                      uint32_t *status) {
+    __shared__ uint32_t s_voff[FO1_TOPICS + 1];
+    __shared__ uint32_t s_h[FO1_WAVES * FO1_BINS];
+    __shared__ uint32_t s_ov[FO1_ENTRIES];
+    __shared__ __attribute__((aligned(4))) uint16_t s_ot[FO1_ENTRIES];   // the topics' heads, then the image
+    __shared__ uint64_t s_w[FO1_WAVES];
+    __shared__ uint32_t s_bw[FO1_BINS / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t total = n ? reinterpret_cast<const uint32_t *>(pairs)[2 * n] : 0u;
+    if (n > FO1_TOPICS || n_dests > FO1_MAX_DESTS) {
+        if (tid == 0) { status[FO1_ST_TOTAL] = total; status[FO1_ST_STATE] = FO1_TOO_LARGE; }
+        return;
+    }
+    // 1. the virtual CSR's offsets
+    uint32_t e[FO1_TPT];
+    uint64_t sum = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < FO1_TPT; k++) {
+        const uint32_t t = tid * FO1_TPT + k;
+        e[k] = t < n ? fp_eff(pairs[t], vcap) : 0u;
+        sum += e[k];
+    }
+    const uint64_t inc = wave_incl_scan64(sum, lane);
+    if (lane == 63) s_w[wv] = inc;
+    for (uint32_t i = tid; i < FO1_WAVES * FO1_BINS; i += FO1_BLOCK) s_h[i] = 0;
+    for (uint32_t i = tid; i < FO1_ENTRIES / 2; i += FO1_BLOCK) reinterpret_cast<uint32_t *>(s_ot)[i] = 0;
+    __syncthreads();
+    uint64_t base = inc - sum, Ev = 0;
+    for (uint32_t q = 0; q < FO1_WAVES; q++) {
+        if (q < wv) base += s_w[q];
+        Ev += s_w[q];
+    }
+    if (Ev > FO1_ENTRIES) {   // (block-uniform)
+        if (tid == 0) { status[FO1_ST_TOTAL] = total; status[FO1_ST_STATE] = FO1_TOO_LARGE; }
+        return;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < FO1_TPT; k++) {   // (every offset <= Ev <= FO1_ENTRIES from here)
+        const uint32_t t = tid * FO1_TPT + k;
+        if (t < n) s_voff[t] = (uint32_t)base;
+        if (e[k]) s_ot[base] = (uint16_t)t;   // the topic's head (base + e[k] <= Ev: inside the image)
+        base += e[k];
+    }
+    if (tid == 0) s_voff[n] = (uint32_t)Ev;
+    const uint32_t E = Ev < vcap ? (uint32_t)Ev : (uint32_t)vcap;
+    __syncthreads();
+    // 2.-4. with the wave's steps as a compile-time bound: a micro-batch of a
+    // few hundred entries pays for one step, not FO1_STEPS
+    const uint32_t C = ((E + FO1_WAVES - 1) / FO1_WAVES + 63) & ~63u;   // (<= 64 * FO1_STEPS)
+#define FO1_PARTITION(S)                                                                                         \
+    fo1_partition<S>(pairs, (uint32_t)n, values, vcap, dest_of, dest_len, n_dests, bits, dest_offsets, E, C, s_voff, \
+                     s_h, s_bw, s_ov, s_ot)
+    if (C <= 64) FO1_PARTITION(1);
+    else if (C <= 256) FO1_PARTITION(4);
+    else FO1_PARTITION(FO1_STEPS);
+#undef FO1_PARTITION
+    __syncthreads();
+    // 5. what the caller has room for
+    const uint32_t keep = E < cap ? E : (uint32_t)cap;
+    for (uint32_t i = tid; i < keep; i += FO1_BLOCK) {
+        out_v[i] = s_ov[i];
+        out_t[i] = s_ot[i];
+    }
+    if (tid == 0) { status[FO1_ST_TOTAL] = total; status[FO1_ST_STATE] = FO1_DONE; }
+}
+
 }  // namespace
+
+hipError_t launch_fanout_one(uint64_t n, const uint32_t *pairs, const uint32_t *values, uint64_t vcap,
+                             const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests, uint32_t *dest_offsets,
+                             uint32_t *out_topic, uint32_t *out_value, uint64_t cap, uint32_t *status, hipStream_t s) {
+    if (!n_dests || n_dests > FO_MAX_DESTS || n >= 0xFFFFFFFFull || ((uintptr_t)pairs & 7)) return hipErrorInvalidValue;
+    if (!dest_of) dest_len = 0;
+    if (vcap > 0xFFFFFFFFull) vcap = 0xFFFFFFFFull;
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;
+    uint32_t w = 1;   // bits of the largest bucket id, n_dests
+    while ((n_dests >> w) != 0) w++;
+    hipLaunchKernelGGL(k_fo_one, dim3(1), dim3(FO1_BLOCK), 0, s, reinterpret_cast<const uint2 *>(pairs), n, values, vcap,
+                       dest_of, dest_len, n_dests, w, dest_offsets, out_topic, out_value, cap, status);
+    return hipGetLastError();
+}
 
 bool fanout_two_pass(uint32_t n_dests) { return n_dests + 1 > 256; }
 

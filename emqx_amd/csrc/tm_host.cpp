@@ -121,6 +121,10 @@ struct Lane {
     FanoutScratch f{};
     uint32_t *d_ft = nullptr, *d_fv = nullptr; uint64_t d_ft_cap = 0, d_fv_cap = 0;
     uint64_t *d_fo = nullptr; uint64_t d_fo_cap = 0;
+    // tm_route_batch32 in place: the match's pairs (its values go to d_vals) and
+    // the one-launch fan-out's status words (mapped pinned, FO1_ST_WORDS)
+    uint32_t *d_pr = nullptr; uint64_t d_pr_cap = 0;
+    uint32_t *fo1_h = nullptr, *fo1_d = nullptr;
 };
 
 // Patch log: a ring of the last PATCH_RING patches (numbered 1, 2, ... in the
@@ -302,6 +306,8 @@ struct tm_index {
     int small_kind = SMALL_AUTO;    // TM_DEBUG_SMALL_KERNEL: which one-launch kernel takes small batches
     std::atomic<uint64_t> failed_batches{0}, retried_batches{0};   // one-launch look-back failures seen / retried
     std::atomic<uint64_t> path_batches[PATH_COUNT] = {};             // match launches per kernel path
+    // tm_route_batch32 batches whose fan-out k_fo_one completed / that the grid kernels or the staged path finished
+    std::atomic<uint64_t> route_one{0}, route_grid{0};
     // The host-batch combiner (small_combined): small in-place 32-bit batches
     // of concurrent callers queue here; up to cmb_leaders callers at a time
     // each take what is queued and run it as ONE k_walk_small launch
@@ -1672,9 +1678,9 @@ void free_workspace(Workspace &w) {
 void free_lane(Lane &l) {
     free_workspace(l.w);
     void *dv[] = {l.d_in, l.d_res, l.d_vals, l.d_o64, l.d_h64, l.f.tab, l.f.tot, l.f.t, l.f.v, l.f.b, l.f.voff, l.f.sums, l.f.b2,
-                  l.d_ft, l.d_fv, l.d_fo};
+                  l.d_ft, l.d_fv, l.d_fo, l.d_pr};
     for (void *p : dv) if (p) (void)hipFree(p);
-    void *pins[] = {l.pin_in, l.pin_out, l.pin_vals};
+    void *pins[] = {l.pin_in, l.pin_out, l.pin_vals, l.fo1_h};
     for (void *p : pins) if (p) (void)hipHostFree(p);
     if (l.done) (void)hipEventDestroy(l.done);
     if (l.owned && l.s) (void)hipStreamDestroy(l.s);
@@ -1905,7 +1911,7 @@ int drain_lanes(tm_index *ix) {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 12u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 13u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 
@@ -3266,6 +3272,150 @@ int tm_match_batch32_pairs(tm_index *ix, uint64_t n, const uint8_t *tb, const ui
     return rc;
 }
 
+// tm_route_batch32 in place (include/tmatch.h): the batch matched as ONE
+// pairs segment of the one-launch kernel (launch_small_segs, no combiner) into
+// the lane's HBM scratch, the flags into the caller's out_err, then k_fo_one
+// fans out into the caller's mapped outputs -- two launches, one
+// synchronisation, no copy.  ROUTE32_OTHER: the batch is not eligible (the
+// caller takes tm_route_batch).  A batch k_fo_one reports as too large is
+// finished here by launch_fanout_pairs on the pairs already matched.
+constexpr int ROUTE32_OTHER = 1;   // (not a TM_ code)
+
+static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint64_t nbytes,
+                            uint32_t n_dests, uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
+                            uint64_t cap, uint8_t *out_err) {
+    std::unique_lock<std::mutex> g(ix->mu);
+    uint8_t *db = nbytes ? pinned_dev(ix, tb, nbytes) : nullptr;
+    uint8_t *dof = pinned_dev(ix, to, (n + 1) * 4);
+    uint8_t *dfo = pinned_dev(ix, out_dest_offsets, ((uint64_t)n_dests + 2) * 4);
+    uint8_t *dt = cap ? pinned_dev(ix, out_topic, cap * 4) : nullptr;
+    uint8_t *dv = cap ? pinned_dev(ix, out_values, cap * 4) : nullptr;
+    uint8_t *de = pinned_dev(ix, out_err, n);
+    if (!((db || !nbytes) && dof && dfo && (!cap || (dt && dv)) && de)) return ROUTE32_OTHER;
+    LaneLease lease{ix, g};
+    int rc;
+    if ((rc = host_lane(ix, g, lease.ln))) return rc;
+    Lane &ln = *lease.ln;
+    const hipStream_t s = ln.s;
+    if ((rc = sync_locked(ix, ln.r, s))) return rc;
+    if ((rc = ensure_ws(ix, n + (uint64_t)SMALL_SEGS * SM_TOPICS, ln))) return rc;
+    if (n && !small_path_ok(dev_view(ix, ln.r), n)) return ROUTE32_OTHER;
+    ix->rep[ln.r].batches++;
+    if (!ln.fo1_h) {
+        HIPCHK(ix, hipHostMalloc(&ln.fo1_h, FO1_ST_WORDS * 4, hipHostMallocMapped));
+        HIPCHK(ix, hipHostGetDevicePointer(reinterpret_cast<void **>(&ln.fo1_d), ln.fo1_h, 0));
+    }
+    volatile uint32_t *st = ln.fo1_h;
+    uint64_t total = 0, vcap = std::max<uint64_t>({ln.d_vals_cap, 4 * n, 1 << 16});
+    for (int attempt = 0, tries = 0;; attempt++) {
+        if (vcap > 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch32: more than 2^32 - 1 hits in one batch");
+        if ((rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, vcap))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_pr, ln.d_pr_cap, 2 * n + 2))) return rc;
+        if (n) {
+            const DevIndex d = dev_view(ix, ln.r);
+            uint32_t tag;
+            if ((rc = next_tag(ix, ln, s, tag))) return rc;
+            SmallSegs sg{};
+            sg.count = 1;
+            sg.pairs = 1;
+            sg.s[0] = SmallSeg{db ? db : dof, dof, ln.d_pr, de, ln.d_vals, vcap, (uint32_t)n, 0};
+            int path = PATH_SMALL;
+            HIPCHK(ix, launch_small_segs(d, ln.w, sg, true, tag, next_lb(ix), ix->small_kind, s, &path));
+            ix->path_batches[path]++;
+        }
+        const uint32_t *dtab = nullptr;
+        uint64_t dlen = 0;
+        if ((rc = dest_upload(ix, ix->rep[ln.r].group, s, dtab, dlen))) return rc;
+        st[FO1_ST_STATE] = 0;   // (the lane's stream is idle: nothing else writes the words)
+        HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, reinterpret_cast<uint32_t *>(dfo),
+                                     reinterpret_cast<uint32_t *>(dt), reinterpret_cast<uint32_t *>(dv), cap, ln.fo1_d, s));
+        if ((rc = batch_done(ix, ln))) return rc;
+        g.unlock();
+        HIPCHK(ix, hipStreamSynchronize(s));
+        if (batch_failed(ix, ln)) {   // (as tm_route_batch: run the batch again, once)
+            if ((rc = retry_or_fail(ix, g, ln, tries++))) return rc;
+            attempt--;
+            continue;
+        }
+        total = st[FO1_ST_TOTAL];
+        if (total <= vcap) break;
+        if (attempt >= 2) return fail(ix, TM_EDEVICE, "tm_route_batch32: hit total kept growing past the value scratch");
+        vcap = total + total / 4;
+        g.lock();
+        HIPCHK(ix, hipSetDevice(ix->rep[ln.r].device));
+        if ((rc = sync_locked(ix, ln.r, s))) return rc;
+        if ((rc = ensure_ws(ix, n + (uint64_t)SMALL_SEGS * SM_TOPICS, ln))) return rc;
+    }
+    const uint32_t state = st[FO1_ST_STATE];
+    if (state == FO1_DONE) {
+        ix->route_one++;
+        return total > cap ? TM_ECAP : TM_OK;
+    }
+    if (state != FO1_TOO_LARGE) return fail(ix, TM_EDEVICE, "tm_route_batch32: the fan-out kernel left no status");
+    // more entries than k_fo_one takes: the grid kernels on the same pairs (no
+    // second walk), into the lane's scratch, copied out and narrowed
+    g.lock();
+    HIPCHK(ix, hipSetDevice(ix->rep[ln.r].device));
+    if ((rc = grow_dev(ix, s, ln.d_ft, ln.d_ft_cap, vcap))) return rc;
+    if ((rc = grow_dev(ix, s, ln.d_fv, ln.d_fv_cap, vcap))) return rc;
+    if ((rc = grow_dev(ix, s, ln.d_fo, ln.d_fo_cap, (uint64_t)n_dests + 2))) return rc;
+    if ((rc = ensure_fanout(ix, ln, n_dests, vcap, true, n))) return rc;
+    const uint32_t *dtab = nullptr;
+    uint64_t dlen = 0;
+    if ((rc = dest_upload(ix, ix->rep[ln.r].group, s, dtab, dlen))) return rc;
+    HIPCHK(ix, launch_fanout_pairs(ln.f, n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, ln.d_fo, ln.d_ft, ln.d_fv, s));
+    if ((rc = batch_done(ix, ln))) return rc;
+    g.unlock();
+    std::vector<uint64_t> fo;
+    try {
+        fo.resize((uint64_t)n_dests + 2);
+    } catch (const std::bad_alloc &) {
+        return fail(ix, TM_ENOMEM, "tm_route_batch32: out of host memory");
+    }
+    const uint64_t keep = std::min(total, cap);
+    HIPCHK(ix, hipMemcpyAsync(fo.data(), ln.d_fo, fo.size() * 8, hipMemcpyDeviceToHost, s));
+    if (keep) {
+        HIPCHK(ix, hipMemcpyAsync(out_topic, ln.d_ft, keep * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ix, hipMemcpyAsync(out_values, ln.d_fv, keep * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(ix, hipStreamSynchronize(s));
+    for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
+    ix->route_grid++;
+    return total > cap ? TM_ECAP : TM_OK;
+}
+
+int tm_route_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint32_t n_dests,
+                     uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                     uint8_t *out_err) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_route_batch32: null handle");
+    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_route_batch32: n_dests must be 1 .. 65536");
+    if (!to || !out_dest_offsets || !out_err || (cap && (!out_topic || !out_values)))
+        return fail(ix, TM_EINVAL, "tm_route_batch32: null buffer");
+    if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch32: batch too large");
+    const uint64_t nbytes = n ? to[n] : 0;   // (before the lock: in TM_ALLOC_VRAM memory a host read is a PCIe round trip)
+    if (n && !tb && nbytes != to[0]) return fail(ix, TM_EINVAL, "tm_route_batch32: null buffer");
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
+    if (n <= FO1_TOPICS && n_dests <= FO1_MAX_DESTS && ((uintptr_t)tb & 15) == 0) {
+        const int rc = route32_in_place(ix, n, tb, to, nbytes, n_dests, out_dest_offsets, out_topic, out_values, cap,
+                                        out_err);
+        if (rc != ROUTE32_OTHER) return rc;
+    }
+    // every other batch: widened, tm_route_batch, narrowed (the buffers kept per
+    // thread: a fresh 128 KB vector per call is an mmap and its page faults)
+    static thread_local std::vector<uint64_t> o64, fo;
+    try {
+        o64.assign(to, to + n + 1);
+        fo.resize((uint64_t)n_dests + 2);
+    } catch (const std::bad_alloc &) {
+        return fail(ix, TM_ENOMEM, "tm_route_batch32: out of host memory");
+    }
+    const int rc = tm_route_batch(ix, n, tb, o64.data(), n_dests, fo.data(), out_topic, out_values, cap, out_err);
+    if (rc != TM_OK && rc != TM_ECAP) return rc;
+    for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
+    ix->route_grid++;
+    return rc;
+}
+
 int tm_match_batch32_dev(tm_index *ix, uint64_t n, const uint8_t *bytes, const uint32_t *offs, uint32_t *hit_offs,
                          uint32_t *out, uint64_t cap, uint8_t *err, void *stream) {
     if (!ix) return fail(nullptr, TM_EINVAL, "tm_match_batch32_dev: null handle");
@@ -3434,6 +3584,8 @@ int tm_debug_get(tm_index *ix, uint32_t key, uint64_t *value) {
     case TM_DEBUG_SMALL_TICKET: *value = ix->small_ticket; break;
     case TM_DEBUG_PATCH_ZC: *value = ix->patch_zc; break;
     case TM_DEBUG_FANOUT_GRID: *value = FO_GRID; break;
+    case TM_DEBUG_ROUTE_ONE: *value = ix->route_one.load(); break;
+    case TM_DEBUG_ROUTE_GRID: *value = ix->route_grid.load(); break;
     case TM_DEBUG_COMMIT_WAITS: *value = ix->commit_waits.load(); break;
     case TM_DEBUG_COMMIT_FORCED: *value = ix->commit_forced.load(); break;
     case TM_DEBUG_COMBINED_LAUNCHES: *value = ix->cmb_launches.load(); break;

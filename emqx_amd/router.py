@@ -137,8 +137,13 @@ class MirrorDown(RuntimeError):
 
 
 class Router:
-    def __init__(self, node="node", device: int = -1, mirror=None, mirror_factory=None):
+    def __init__(self, node="node", device: int = -1, mirror=None, mirror_factory=None,
+                 route_in_place: bool = False):
+        """route_in_place: match_routes_by_dest goes through the mirror's
+        route_kids32 (tm_route_batch32 on pooled pinned buffers: a micro-batch
+        is matched and fanned out in place) instead of route_kids."""
         self.node = node
+        self._route_in_place = route_in_place
         self._bag: dict[bytes, dict] = {}        # emqx_route: Topic -> {Dest: seq} (insertion order)
         self._seq = 0
         self._filters: dict = {}                 # emqx_route_filters: Key -> RouteIdx
@@ -464,7 +469,8 @@ class Router:
             with self._dest_lock:
                 classes = list(self._dest_classes)
             n_dests = max(len(classes), 1)
-            doff, tidx, kids, err = mirror.route_kids(topics, n_dests)
+            route = mirror.route_kids32 if self._route_in_place else mirror.route_kids
+            doff, tidx, kids, err = route(topics, n_dests)
             if len(err) and (err == 4).any():   # (the library returns TM_EDEVICE instead; never a client error)
                 raise ti.DeviceError(-3, "batch failed on the device (err flag 4)")
             for i in map(int, err.nonzero()[0]):

@@ -42,6 +42,9 @@ from .trie_search import (BadArg, HASH, PLUS, filter_words, get_id, get_topic, k
                           make_key, term_key, topic_words)
 
 
+ROUTE_POOL_SETS = 4   # pinned buffer sets route_kids32 keeps (concurrent callers beyond them allocate their own)
+
+
 class Tab:
     """An index table: records + the device-resident mirror of its keys."""
 
@@ -65,6 +68,7 @@ class Tab:
         # delta that inserts the key
         self.dest_fn = None
         self._dests: list = []          # pending (kid, destination id)
+        self._route_pool: list = []     # route_kids32: idle sets of pinned batch buffers (host_array)
 
     # -- key <-> device encoding
     @staticmethod
@@ -214,6 +218,60 @@ class Tab:
         self.flush()
         blob, offs = _native.pack_strings(topics)
         return self._index.route_batch(blob, offs, n_dests)
+
+    def _route_set(self, n: int, nbytes: int, n_dests: int, cap: int) -> dict:
+        """A set of pinned buffers (host_array) large enough for the batch, from
+        the pool or new -- what a NIF keeps per scheduler.  Arrays too small are
+        replaced; the set goes back with _route_put."""
+        with self._lock:
+            s = self._route_pool.pop() if self._route_pool else {}
+        want = {"blob": (nbytes + 16, np.uint8), "offs": (n + 1, np.uint32), "doff": (n_dests + 2, np.uint32),
+                "topic": (cap, np.uint32), "vals": (cap, np.uint32), "err": (max(n, 1), np.uint8)}
+        for name, (need, dt) in want.items():
+            if name not in s or len(s[name]) < need:
+                if name in s:
+                    self._index.host_free(s.pop(name))
+                s[name] = self._index.host_array(need + need // 4, dt)
+        return s
+
+    def _route_put(self, s: dict):
+        with self._lock:
+            if len(self._route_pool) < ROUTE_POOL_SETS:
+                self._route_pool.append(s)
+                return
+        for a in s.values():
+            self._index.host_free(a)
+
+    def route_kids32(self, topics, n_dests: int):
+        """route_kids through tm_route_batch32 on pooled pinned buffers: a
+        micro-batch is matched and fanned out in place (two launches, no
+        staging copy).  One retry on TM_ECAP, sized from the bucket offsets.
+        Returns what route_kids returns (copies: the buffers go back to the
+        pool)."""
+        self.flush()
+        blob, offs = _native.pack_strings(topics)
+        n, nbytes = len(offs) - 1, int(offs[-1])
+        if nbytes >= 1 << 32:
+            return self._index.route_batch(blob, offs, n_dests)
+        s = self._route_set(n, nbytes, n_dests, max(4 * n, 1024))
+        try:
+            s["blob"][:nbytes] = blob[:nbytes]
+            s["offs"][: n + 1] = offs
+            for attempt in (0, 1):
+                out = (s["doff"], s["topic"], s["vals"], s["err"])
+                try:
+                    doff, tidx, kids, err = self._index.route_batch32(s["blob"], s["offs"][: n + 1], n_dests, out)
+                    break
+                except _native.TmError as e:
+                    if e.code != _native.TM_ECAP or attempt:
+                        raise
+                    total = int(s["doff"][n_dests + 1])
+                    for name in ("topic", "vals"):   # the offsets hold the full bucket sizes
+                        self._index.host_free(s.pop(name))
+                        s[name] = self._index.host_array(total + total // 4, np.uint32)
+            return doff.astype(np.uint64), tidx.copy(), kids.copy(), err.copy()
+        finally:
+            self._route_put(s)
 
     def read_begin(self) -> int:
         return self._index.read_begin()

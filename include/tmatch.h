@@ -433,9 +433,35 @@ int tm_sort_segments(tm_index *h, uint64_t n, const uint64_t *d_hit_offsets, uin
  * and the stream's scratch holds 8 bytes x n and 12 bytes x cap for every
  * n_dests, 16 x cap for two passes (TM_ENOMEM if that cannot be had).
  *
+ * tm_route_batch32 (ABI minor 13): tm_route_batch with 32-bit offsets in and
+ * out, for a NIF's micro-batches.  The outputs are exactly those
+ * tm_route_batch writes for the same index state, topics, n_dests and cap:
+ * out_dest_offsets (u32, n_dests + 2 entries) holds the full bucket sizes even
+ * under TM_ECAP, the first min(total, cap) entries of out_topic / out_values
+ * are written and nothing at or past that in either array; TM_ECAP when
+ * total > cap.  out_err is required.  Thread safety, lanes, read-your-writes
+ * and the device-failure retry are tm_route_batch's.
+ * In place -- no staging copy in, no copy out, one synchronisation -- when
+ * n <= 8192 and n_dests <= 255 (the one-launch fan-out kernel's bounds), the
+ * topic bytes are 16-byte aligned, every buffer (the inputs, which may be
+ * TM_ALLOC_VRAM, the three outputs and out_err) lies in this index's
+ * tm_host_alloc memory, and the index allows the one-launch walk (as
+ * tm_match_batch32_pairs).  Then the batch is matched by the one-launch pairs
+ * kernel, on the call's own lane, into the lane's scratch (8 bytes x n of pairs
+ * and the values: at least 65536 and 4 n words, grown and the batch run again
+ * when the total exceeds them; the flags go straight to out_err), and ONE
+ * launch of one workgroup fans it out into the caller's buffers: no block
+ * waits for another.  A batch with more than 16384 entries is finished on the
+ * same lane by tm_fanout_dev_pairs' kernels on the pairs already matched (no
+ * second walk; 12 bytes x total of scratch more) and copied out.  Every other
+ * batch is widened on the host, run by tm_route_batch, and narrowed.
+ * TM_DEBUG_ROUTE_ONE / TM_DEBUG_ROUTE_GRID (tm_debug_get) count the calls the
+ * one-launch kernel completed / the grid kernels or the staged path finished.
+ *
  * TM_EINVAL (before any device work): a null handle, a null required pointer,
  * n_dests == 0 or n_dests > 65536, n >= 2^32 - 1, d_pairs not 8-byte
- * aligned. */
+ * aligned; tm_route_batch and tm_route_batch32 also when the batch's total
+ * exceeds 2^32 - 1 (found on the device). */
 int tm_set_dests(tm_index *h, uint64_t n, const uint32_t *values, const uint32_t *dests);
 int tm_fanout_dev(tm_index *h, uint64_t n, const uint64_t *d_hit_offsets, const uint32_t *d_values, uint64_t cap,
                   const uint32_t *d_dest_of, uint64_t dest_len, uint32_t n_dests,
@@ -446,6 +472,9 @@ int tm_fanout_dev_pairs(tm_index *h, uint64_t n, const uint32_t *d_pairs, const 
 int tm_route_batch(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint64_t *topic_offsets,
                    uint32_t n_dests, uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
                    uint64_t cap, uint8_t *out_err);
+int tm_route_batch32(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint32_t *topic_offsets,
+                     uint32_t n_dests, uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
+                     uint64_t cap, uint8_t *out_err);
 
 /* Release the batch scratch kept for `stream` (after its batches finish);
  * a caller that retires a stream calls this.  No reference counterpart. */
@@ -539,14 +568,18 @@ int tm_profile_read(tm_index *h, double *walk_ms, double *batch_ms, uint64_t *ba
  * dense enough that the walk probes their child table without it.  (Keys
  * 9-11 named the round-4 one-pass kernel's hooks; 9 and 10 now name these,
  * 11 is retired.)  TM_DEBUG_FANOUT_GRID (get only): the one-wave blocks of a
- * fan-out pass (tm_fanout_dev), each owning an equal chunk of the entries. */
+ * fan-out pass (tm_fanout_dev), each owning an equal chunk of the entries.
+ * TM_DEBUG_ROUTE_ONE / TM_DEBUG_ROUTE_GRID (get only): tm_route_batch32 calls
+ * whose fan-out the one-launch kernel completed / that the grid kernels or the
+ * staged path finished. */
 enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES = 3, TM_DEBUG_PHASES = 4,
        TM_DEBUG_FAILED_BATCHES = 5, TM_DEBUG_RETRIED_BATCHES = 6, TM_DEBUG_PATH_PHASES = 7,
        TM_DEBUG_PATH_SMALL = 8, TM_DEBUG_PATH_LANE = 9, TM_DEBUG_SMALL_KERNEL = 10,
        TM_DEBUG_COMBINE = 12, TM_DEBUG_COMBINED_LAUNCHES = 13, TM_DEBUG_COMBINED_BATCHES = 14,
        TM_DEBUG_WIDE_NODES = 15, TM_DEBUG_DENSE_WIDE = 16, TM_DEBUG_CMB_GATHER = 17, TM_DEBUG_CMB_LAND = 18,
        TM_DEBUG_COMMITS = 19, TM_DEBUG_COMMIT_WAITS = 20, TM_DEBUG_COMMIT_FORCED = 21, TM_DEBUG_SMALL_TICKET = 22,
-       TM_DEBUG_CMB_SPIN = 23, TM_DEBUG_PATCH_ZC = 24, TM_DEBUG_FANOUT_GRID = 25 };
+       TM_DEBUG_CMB_SPIN = 23, TM_DEBUG_PATCH_ZC = 24, TM_DEBUG_FANOUT_GRID = 25,
+       TM_DEBUG_ROUTE_ONE = 26, TM_DEBUG_ROUTE_GRID = 27 };
 int tm_debug_set(tm_index *h, uint32_t key, uint64_t value);
 int tm_debug_get(tm_index *h, uint32_t key, uint64_t *value);
 

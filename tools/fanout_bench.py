@@ -34,6 +34,19 @@ timed the same way (the two forms alternating), and one synthetic line with
 no index (synthetic_skew): the same number of entries over the same number of
 topics once spread evenly and once with 64 topics holding half of them, both
 calls on each -- what skew costs.  --form pairs leaves the torch line out.
+
+--small: the NIF's micro-batches instead (nothing of the above runs): the same
+index with 16 destinations set through tm_set_dests, batches of 64, 1,024,
+4,096 and 16,384 topics in host_array buffers, timed host to host
+(perf_counter around the call: 20 warm-up and 200 timed repetitions, the legs
+interleaved), one JSON line per batch size with three legs:
+
+  route_batch      (a) tm_route_batch, the staged product path
+  match32_pairs    (b) tm_match_batch32_pairs alone: the match with no fan-out
+  route_batch32    (c) tm_route_batch32, in place
+
+(a)'s and (c)'s outputs are compared first (they must be identical); the line
+also says which fan-out (c) took (TM_DEBUG_ROUTE_ONE / _GRID).
 """
 import argparse
 import json
@@ -185,6 +198,69 @@ def synthetic_skew(torch, ix, a, s, n, total, n_dests=16):
           flush=True)
 
 
+def small_batches(a, sizes=(64, 1024, 4096, 16384), n_dests=16, warmup=20, reps=200):
+    """--small: host-to-host latency of a micro-batch's route fan-out, three legs interleaved"""
+    import time
+    fs = wl.filters(3, a.filters)
+    ix = _native.Index(hint_keys=len(fs))
+    rng = np.random.default_rng(7)
+    nvals = int(fs.vals.max()) + 1
+    ix.set_dests(np.arange(nvals, dtype=np.uint32), rng.integers(0, n_dests, nvals).astype(np.uint32))
+    ix.apply(np.ones(len(fs), np.uint8), fs.blob, fs.offs, fs.vals)
+    ix.sync(None)
+    P = _native._ptr
+    lib, h = ix._lib, ix._h
+    for n in sizes:
+        tp = wl.topics(3, a.filters, n)
+        assert len(tp) == n
+        nb = int(tp.offs[-1])
+        cap = 16 * n + 1024
+        blob, offs32 = ix.host_array(nb + 16, np.uint8), ix.host_array(n + 1, np.uint32)
+        blob[:nb] = tp.blob[:nb]
+        offs32[:] = tp.offs.astype(np.uint32)
+        offs64 = ix.host_array(n + 1, np.uint64)
+        offs64[:] = tp.offs
+        err = ix.host_array(n, np.uint8)
+        pairs, pvals = ix.host_array(2 * n + 1, np.uint32), ix.host_array(cap, np.uint32)
+        o32 = (ix.host_array(n_dests + 2, np.uint32), ix.host_array(cap, np.uint32), ix.host_array(cap, np.uint32))
+        o64 = (ix.host_array(n_dests + 2, np.uint64), ix.host_array(cap, np.uint32), ix.host_array(cap, np.uint32))
+
+        def leg_a():
+            return lib.tm_route_batch(h, n, P(blob), P(offs64), n_dests, P(o64[0]), P(o64[1]), P(o64[2]), cap, P(err))
+
+        def leg_b():
+            return lib.tm_match_batch32_pairs(h, n, P(blob), P(offs32), P(pairs), P(pvals), cap, P(err))
+
+        def leg_c():
+            return lib.tm_route_batch32(h, n, P(blob), P(offs32), n_dests, P(o32[0]), P(o32[1]), P(o32[2]), cap, P(err))
+
+        one0, grid0 = ix.debug_get(_native.TM_DEBUG_ROUTE_ONE), ix.debug_get(_native.TM_DEBUG_ROUTE_GRID)
+        assert leg_a() == 0 and leg_c() == 0 and leg_b() == 0, "a leg failed (or cap too small)"
+        path = "one_launch" if ix.debug_get(_native.TM_DEBUG_ROUTE_ONE) > one0 else "grid"
+        assert ix.debug_get(_native.TM_DEBUG_ROUTE_ONE) + ix.debug_get(_native.TM_DEBUG_ROUTE_GRID) == one0 + grid0 + 1
+        total = int(o64[0][n_dests + 1])
+        assert total == int(pairs[2 * n]) and np.array_equal(o64[0], o32[0].astype(np.uint64)) and \
+            np.array_equal(o64[1][:total], o32[1][:total]) and np.array_equal(o64[2][:total], o32[2][:total]), \
+            f"n {n}: tm_route_batch and tm_route_batch32 differ"
+        legs = (leg_a, leg_b, leg_c)
+        ms = ([], [], [])
+        for r in range(warmup + reps):
+            for k, f in enumerate(legs):
+                t0 = time.perf_counter_ns()
+                f()
+                t1 = time.perf_counter_ns()
+                if r >= warmup:
+                    ms[k].append((t1 - t0) * 1e-6)
+        sa, sb, sc = stats(ms[0]), stats(ms[1]), stats(ms[2])
+        print(json.dumps({"tool": "fanout_bench", "kind": "small", "filters": len(fs), "topics": n, "entries": total,
+                          "n_dests": n_dests, "warmup": warmup, "reps": reps, "route32_fanout": path,
+                          "route_batch": sa, "match32_pairs": sb, "route_batch32": sc,
+                          "c_minus_b_ms": round(sc["median_ms"] - sb["median_ms"], 4),
+                          "a_minus_c_ms": round(sa["median_ms"] - sc["median_ms"], 4), "identical": True}), flush=True)
+        for x in (blob, offs32, offs64, err, pairs, pvals, *o32, *o64):
+            ix.host_free(x)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--filters", type=int, default=1_000_000)
@@ -193,10 +269,14 @@ def main():
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--dests", type=int, nargs="+", default=[16, 4096])
     p.add_argument("--form", choices=["csr", "pairs", "both"], default="csr")
+    p.add_argument("--small", action="store_true", help="the NIF's micro-batches, host to host (see above)")
     a = p.parse_args()
     import torch
     if not torch.cuda.is_available():
         sys.exit("fanout_bench: no HIP device (this measurement has no CPU form)")
+    if a.small:
+        small_batches(a)
+        return
     dev = torch.device("cuda")
     fs = wl.filters(3, a.filters)
     ix = _native.Index(hint_keys=len(fs))
