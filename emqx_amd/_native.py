@@ -28,8 +28,11 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_create_replicas", "tm_replica_stats", "tm_debug_set", "tm_debug_get", "tm_match_batch32_ex",
            "tm_match_batch32_dev", "tm_matches_filter_ex", "tm_host_alloc_ex", "tm_commit",
            "tm_match_batch32_pairs", "tm_match_batch_dev_pairs", "tm_set_dests", "tm_fanout_dev", "tm_route_batch",
-           "tm_fanout_dev_pairs", "tm_route_batch32")
+           "tm_fanout_dev_pairs", "tm_route_batch32", "tm_set_route_filters", "tm_aggre_dev", "tm_route_batch_ex",
+           "tm_route_batch32_ex")
 TM_ALLOC_VRAM = 1
+TM_ROUTE_AGGRE = 1          # tm_route_batch_ex / tm_route_batch32_ex: aggre/1 applied to the buckets
+NO_FILTER = 0xFFFFFFFF      # tm_set_route_filters: no filter known (equal to nothing)
 TM_DEBUG_LB_SPINS, TM_DEBUG_LB_FAIL_BLOCK, TM_DEBUG_LB_LAUNCHES, TM_DEBUG_PHASES = 1, 2, 3, 4
 TM_DEBUG_FAILED_BATCHES, TM_DEBUG_RETRIED_BATCHES = 5, 6
 TM_DEBUG_PATH_PHASES, TM_DEBUG_PATH_SMALL, TM_DEBUG_PATH_LANE = 7, 8, 9
@@ -128,6 +131,10 @@ def load_library(path: Path | None = None):
         "tm_fanout_dev_pairs": (i32, [vp, u64, vp, vp, u64, vp, u64, u32, vp, vp, vp, vp]),
         "tm_route_batch": (i32, [vp, u64, vp, vp, u32, vp, vp, vp, u64, vp]),
         "tm_route_batch32": (i32, [vp, u64, vp, vp, u32, vp, vp, vp, u64, vp]),
+        "tm_set_route_filters": (i32, [vp, u64, vp, vp]),
+        "tm_aggre_dev": (i32, [vp, u32, vp, vp, vp, u64, vp, u64, vp, vp, vp, vp]),
+        "tm_route_batch_ex": (i32, [vp, u64, vp, vp, u32, vp, vp, vp, u64, vp, u32]),
+        "tm_route_batch32_ex": (i32, [vp, u64, vp, vp, u32, vp, vp, vp, u64, vp, u32]),
         "tm_debug_set": (i32, [vp, u32, u64]),
         "tm_debug_get": (i32, [vp, u32, C.POINTER(u64)]),
     }
@@ -422,13 +429,36 @@ class Index:
         self._check(self._lib.tm_fanout_dev_pairs(self._h, n, d_pairs, d_vals, cap, d_dest_of, dest_len, n_dests,
                                                   d_dest_offs, d_out_topic, d_out_value, stream))
 
-    def route_batch(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, cap: int | None = None):
+    def set_route_filters(self, values, filter_ids):
+        """tm_set_route_filters: filter_ids[i] becomes the filter id (the To) of the
+        route values[i] names (u32 each; NO_FILTER: none known)."""
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        filter_ids = np.ascontiguousarray(filter_ids, dtype=np.uint32)
+        if len(values) != len(filter_ids):
+            raise ValueError("set_route_filters: one filter id per value")
+        self._check(self._lib.tm_set_route_filters(self._h, len(values), _ptr(values), _ptr(filter_ids)))
+
+    def aggre_dev(self, n_dests: int, d_dest_offs: int, d_topic: int, d_value: int, cap: int, d_out_dest_offs: int,
+                  d_out_topic: int, d_out_value: int, d_filter_of: int | None = None, filter_len: int = 0,
+                  stream: int | None = None):
+        """tm_aggre_dev on device pointers: a fan-out's output (d_dest_offs
+        u64[n_dests+2], d_topic, d_value) without the entries whose predecessor
+        in the same routed bucket has the same topic and the same filter, into
+        d_out_* (which must not overlap the inputs); d_out_dest_offs
+        u64[n_dests+2], the kept total last.  d_filter_of None: the table of
+        set_route_filters."""
+        self._check(self._lib.tm_aggre_dev(self._h, n_dests, d_dest_offs, d_topic, d_value, cap, d_filter_of, filter_len,
+                                           d_out_dest_offs, d_out_topic, d_out_value, stream))
+
+    def route_batch(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, cap: int | None = None,
+                    aggre: bool = False):
         """tm_route_batch -> (dest_offsets u64[n_dests+2], topic u32[total],
         values u32[total], err u8[n]): destination b's (topic index, value)
         pairs are [dest_offsets[b], dest_offsets[b+1]), in topic order and
         traversal order inside a topic; bucket n_dests holds the values
         without a destination.  A cap that proves too small is retried once,
-        sized from the returned bucket sizes."""
+        sized from the returned bucket sizes.  aggre: TM_ROUTE_AGGRE -- the
+        buckets after aggre/1 (set_route_filters), the kept total last."""
         n = len(offs) - 1
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
@@ -439,8 +469,12 @@ class Index:
         while True:
             topic = np.empty(max(cap, 1), dtype=np.uint32)
             vals = np.empty(max(cap, 1), dtype=np.uint32)
-            rc = self._lib.tm_route_batch(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff), _ptr(topic),
-                                          _ptr(vals), cap, _ptr(err))
+            if aggre:
+                rc = self._lib.tm_route_batch_ex(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff), _ptr(topic),
+                                                 _ptr(vals), cap, _ptr(err), TM_ROUTE_AGGRE)
+            else:
+                rc = self._lib.tm_route_batch(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff), _ptr(topic),
+                                              _ptr(vals), cap, _ptr(err))
             if rc == TM_ECAP and int(doff[-1]) > cap:
                 cap = int(doff[-1])
                 continue
@@ -448,7 +482,8 @@ class Index:
             total = int(doff[-1])
             return doff, topic[:total], vals[:total], err[:n]
 
-    def route_batch32(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, out, cap: int | None = None):
+    def route_batch32(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, out, cap: int | None = None,
+                      aggre: bool = False):
         """tm_route_batch32: route_batch with u32 topic offsets in and u32 bucket
         offsets out.  out = (dest_offsets u32[>= n_dests+2], topic u32[cap],
         values u32[cap], err u8[>= n]) -> (dest_offsets[:n_dests+2],
@@ -456,7 +491,9 @@ class Index:
         one fan-out launch) when every array comes from host_array() and the
         batch is a micro-batch (include/tmatch.h).  cap: use only that many
         entries of topic / values (default: all).  Raises TmError(TM_ECAP) when
-        the entries do not fit (the offsets are valid: the total is the last)."""
+        the entries do not fit (the offsets are valid: the total is the last).
+        aggre: TM_ROUTE_AGGRE -- the buckets after aggre/1; TM_ECAP then when
+        the entries BEFORE aggregation do not fit (the offsets are those sizes)."""
         n = len(offs) - 1
         doff, topic, vals, err = out
         if offs.dtype != np.uint32 or doff.dtype != np.uint32 or topic.dtype != np.uint32 or vals.dtype != np.uint32 \
@@ -466,8 +503,12 @@ class Index:
             cap = min(len(topic), len(vals))
         if cap > min(len(topic), len(vals)):
             raise ValueError("route_batch32: cap exceeds the output arrays")
-        self._check(self._lib.tm_route_batch32(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff), _ptr(topic),
-                                               _ptr(vals), cap, _ptr(err)))
+        if aggre:
+            self._check(self._lib.tm_route_batch32_ex(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff),
+                                                      _ptr(topic), _ptr(vals), cap, _ptr(err), TM_ROUTE_AGGRE))
+        else:
+            self._check(self._lib.tm_route_batch32(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff), _ptr(topic),
+                                                   _ptr(vals), cap, _ptr(err)))
         total = int(doff[n_dests + 1])
         return doff[: n_dests + 2], topic[:total], vals[:total], err[:n]
 

@@ -52,8 +52,12 @@ def aggre(routes):
 
 class Broker:
     def __init__(self, router, node=None, dispatch=None, forward=None, share_dispatch=None,
-                 max_batch: int = 4096, max_wait_ms: float = 0.2, start: bool = False):
+                 max_batch: int = 4096, max_wait_ms: float = 0.2, start: bool = False,
+                 aggre_on_device: bool = False):
+        """aggre_on_device: publish_batch_by_dest asks the router for buckets
+        the device has already applied aggre/1 to (TM_ROUTE_AGGRE)."""
         self.router = router
+        self.aggre_on_device = aggre_on_device
         self.node = router.node if node is None else node
         self.dispatch = dispatch or (lambda to, msg: 0)
         self.forward = forward or (lambda node, to, msg: "ok")
@@ -116,10 +120,18 @@ class Broker:
         by its name only, so a node and a group must not share one (a class
         is taken for a group when its first route's dest is a pair).  The
         deliveries are the same
-        (destination, To, message) multiset as publish_batch's."""
+        (destination, To, message) multiset as publish_batch's.
+        With aggre_on_device the filter matches of a group arrive deduplicated;
+        the host check stays only for what the device cannot see: the bag's
+        rows (by_dest.host_rows names them) and the plan "external", which
+        merges several device classes."""
         if not msgs:
             return {}, {}
-        by_dest = self.router.match_routes_by_dest([m.topic for m in msgs], errors="return")
+        on_dev = self.aggre_on_device
+        if on_dev:
+            by_dest = self.router.match_routes_by_dest([m.topic for m in msgs], errors="return", aggre=True)
+        else:
+            by_dest = self.router.match_routes_by_dest([m.topic for m in msgs], errors="return")
         self.batches += 1
         plans: dict = {}
         seen = set()
@@ -127,8 +139,10 @@ class Broker:
             node = not isinstance(rows[0][1].dest, tuple)
             dest = cls[0] if isinstance(cls, tuple) else cls   # aggre/1: {Group, _Node} -> Group, whatever the pair
             plan = plans.setdefault(dest, [])
-            for i, r in rows:
-                if not node:
+            # rows the device has aggregated need no check: all but the bag's, unless classes merge here
+            check = None if not on_dev or isinstance(cls, tuple) else by_dest.host_rows.get(cls, ())
+            for at, (i, r) in enumerate(rows):
+                if not node and (check is None or at in check):
                     if (i, r.topic, dest) in seen:
                         continue
                     seen.add((i, r.topic, dest))

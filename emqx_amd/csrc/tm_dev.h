@@ -214,6 +214,10 @@ struct FanoutScratch {
     uint64_t voff_cap;
     uint64_t *sums;       // [FP_TILES] the topic tiles' entry counts
     uint32_t *b2;         // [cap] two passes: the resolved entries' buckets (their topics and values wait in the outputs)
+    // aggre (launch_aggre): a bitmap word and a base per 64 positions below ag_cap, the FO_GRID block counts + their total
+    uint64_t *ag_bits;
+    uint32_t *ag_pre, *ag_cnt;
+    uint64_t ag_cap;
 };
 constexpr uint32_t FP_TILES = 1024;
 bool fanout_two_pass(uint32_t n_dests);
@@ -247,6 +251,25 @@ enum : uint32_t { FO1_DONE = 1, FO1_TOO_LARGE = 2 };
 hipError_t launch_fanout_one(uint64_t n, const uint32_t *pairs, const uint32_t *values, uint64_t vcap,
                              const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests, uint32_t *dest_offsets,
                              uint32_t *out_topic, uint32_t *out_value, uint64_t cap, uint32_t *status, hipStream_t s);
+// aggre/1 on a fan-out's output (tm_aggre.hip): the entries below E =
+// min(dest_offsets[n_dests + 1], cap) without those whose predecessor in the
+// same bucket (the unrouted bucket excepted) has the same topic and the same
+// filter (filter_of[value] for value < filter_len, else none: equal to
+// nothing), in input order, with the kept entries' bucket bounds and the total
+// in out_dest_offsets[n_dests + 2].  Needs fs.ag_cap >= min(cap, 2^32 - 1).
+// The outputs must not overlap the inputs.
+hipError_t launch_aggre(const FanoutScratch &fs, uint32_t n_dests, const uint64_t *dest_offsets, const uint32_t *in_topic,
+                        const uint32_t *in_value, uint64_t cap, const uint32_t *filter_of, uint64_t filter_len,
+                        uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_value, hipStream_t s);
+// The same for what launch_fanout_one left in device memory (u32 offsets, the
+// entries, its status words), in ONE workgroup, into buffers that may be
+// mapped host memory.  status_in[FO1_ST_STATE] != FO1_DONE is passed on to
+// `status` and nothing else is written; more than `cap` entries before the
+// compaction: out_dest_offsets = dest_offsets, no entry written.
+hipError_t launch_aggre_one(const uint32_t *status_in, const uint32_t *dest_offsets, uint32_t n_dests,
+                            const uint32_t *in_topic, const uint32_t *in_value, const uint32_t *filter_of,
+                            uint64_t filter_len, uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_value,
+                            uint64_t cap, uint32_t *status, hipStream_t s);
 // delta upload: run i copies runs[i].n u32 words from data + runs[i].src to
 // word (dst & PATCH_OFF) of table (dst >> 48), whose device address on the
 // replica being patched is bases.b[table] (the same runs patch every replica)

@@ -125,6 +125,11 @@ struct Lane {
     // the one-launch fan-out's status words (mapped pinned, FO1_ST_WORDS)
     uint32_t *d_pr = nullptr; uint64_t d_pr_cap = 0;
     uint32_t *fo1_h = nullptr, *fo1_d = nullptr;
+    // TM_ROUTE_AGGRE: the aggregated device results of the grid kernels, and the
+    // one-launch fan-out's status words in device memory (k_ag_one passes them on)
+    uint32_t *d_at = nullptr, *d_av = nullptr; uint64_t d_at_cap = 0, d_av_cap = 0;
+    uint64_t *d_ao = nullptr; uint64_t d_ao_cap = 0;
+    uint32_t *fo1_s = nullptr;
 };
 
 // Patch log: a ring of the last PATCH_RING patches (numbered 1, 2, ... in the
@@ -270,6 +275,11 @@ struct tm_index {
         hipEvent_t ev = nullptr; bool ev_set = false;       // after the last upload: other streams' fan-outs wait
         hipStream_t ev_s = nullptr;
     } dest[MAX_REPLICAS];
+    // value -> the caller's id of the route's topic filter (tm_set_route_filters;
+    // NONE: no filter known, equal to nothing): kept exactly as the
+    // destinations are, under the same lock (table_upload)
+    std::vector<uint32_t> filt_h;
+    DestDev filt[MAX_REPLICAS];
 
     // caller buffers from tm_host_alloc (host address -> size, device address;
     // vram: TM_ALLOC_VRAM device memory, the same address on both sides)
@@ -1678,7 +1688,7 @@ void free_workspace(Workspace &w) {
 void free_lane(Lane &l) {
     free_workspace(l.w);
     void *dv[] = {l.d_in, l.d_res, l.d_vals, l.d_o64, l.d_h64, l.f.tab, l.f.tot, l.f.t, l.f.v, l.f.b, l.f.voff, l.f.sums, l.f.b2,
-                  l.d_ft, l.d_fv, l.d_fo, l.d_pr};
+                  l.d_ft, l.d_fv, l.d_fo, l.d_pr, l.f.ag_bits, l.f.ag_pre, l.f.ag_cnt, l.d_at, l.d_av, l.d_ao, l.fo1_s};
     for (void *p : dv) if (p) (void)hipFree(p);
     void *pins[] = {l.pin_in, l.pin_out, l.pin_vals, l.fo1_h};
     for (void *p : pins) if (p) (void)hipHostFree(p);
@@ -1911,7 +1921,7 @@ int drain_lanes(tm_index *ix) {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 13u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 14u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 
@@ -2029,12 +2039,13 @@ int tm_destroy(tm_index *ix) {
         if (R.ps) (void)hipStreamDestroy(R.ps);
     }
     for (int g = 0; g < ix->ngroups; g++) {
-        auto &D = ix->dest[g];
         for (int r = 0; r < ix->nrep; r++)
             if (ix->rep[r].group == g) { (void)hipSetDevice(ix->rep[r].device); break; }
-        if (D.d) (void)hipFree(D.d);
-        if (D.pin) (void)hipHostFree(D.pin);
-        if (D.ev) (void)hipEventDestroy(D.ev);
+        for (auto *D : {&ix->dest[g], &ix->filt[g]}) {
+            if (D->d) (void)hipFree(D->d);
+            if (D->pin) (void)hipHostFree(D->pin);
+            if (D->ev) (void)hipEventDestroy(D->ev);
+        }
     }
     (void)hipSetDevice(ix->rep[0].device);
     mf_free_keys(ix->mf);
@@ -2387,10 +2398,10 @@ int fanout_lane(tm_index *ix, hipStream_t s, int grp, Lane *&ln) {
 // since the group's last upload go up through pinned staging, in stream
 // order, after the fan-outs of other streams that may still read them; a
 // fan-out on another stream waits for the upload's event.
-int dest_upload(tm_index *ix, int g, hipStream_t s, const uint32_t *&d, uint64_t &len) {
-    auto &D = ix->dest[g];
+int table_upload(tm_index *ix, const std::vector<uint32_t> &host, tm_index::DestDev &D, int g, hipStream_t s,
+                 const uint32_t *&d, uint64_t &len) {
     std::lock_guard<std::mutex> dg(ix->dst_mu);
-    const uint64_t hl = ix->dest_h.size();
+    const uint64_t hl = host.size();
     if (!D.ev) HIPCHK(ix, hipEventCreateWithFlags(&D.ev, hipEventDisableTiming));
     if (D.ev_set && hipEventQuery(D.ev) == hipSuccess) D.ev_set = false;
     if (hl > D.cap) {
@@ -2421,7 +2432,7 @@ int dest_upload(tm_index *ix, int g, hipStream_t s, const uint32_t *&d, uint64_t
             HIPCHK(ix, hipHostMalloc(&D.pin, c * 4, hipHostMallocDefault));
             D.pin_cap = c;
         }
-        std::memcpy(D.pin, ix->dest_h.data() + D.lo, cnt * 4);
+        std::memcpy(D.pin, host.data() + D.lo, cnt * 4);
         for (auto &l : ix->lanes)
             if (l->s != s && ix->rep[l->r].group == g && lane_busy(*l)) HIPCHK(ix, hipStreamWaitEvent(s, l->done, 0));
         HIPCHK(ix, hipMemcpyAsync(D.d + D.lo, D.pin, cnt * 4, hipMemcpyHostToDevice, s));
@@ -2438,34 +2449,39 @@ int dest_upload(tm_index *ix, int g, hipStream_t s, const uint32_t *&d, uint64_t
     return TM_OK;
 }
 
-}  // namespace
+int dest_upload(tm_index *ix, int g, hipStream_t s, const uint32_t *&d, uint64_t &len) {
+    return table_upload(ix, ix->dest_h, ix->dest[g], g, s, d, len);
+}
 
-extern "C" {
+// the same for the index's value -> filter id table (tm_set_route_filters)
+int filter_upload(tm_index *ix, int g, hipStream_t s, const uint32_t *&d, uint64_t &len) {
+    return table_upload(ix, ix->filt_h, ix->filt[g], g, s, d, len);
+}
 
-int tm_set_dests(tm_index *ix, uint64_t n, const uint32_t *values, const uint32_t *dests) {
-    if (!ix) return fail(nullptr, TM_EINVAL, "tm_set_dests: null handle");
-    if (n && (!values || !dests)) return fail(ix, TM_EINVAL, "tm_set_dests: null buffer");
-    if (!n) return TM_OK;
+// tm_set_dests / tm_set_route_filters: n entries into a host table and every
+// group's dirty range
+int table_set(tm_index *ix, std::vector<uint32_t> &host, tm_index::DestDev *dev, uint64_t n, const uint32_t *values,
+              const uint32_t *what, const char *oom) {
     std::lock_guard<std::mutex> dg(ix->dst_mu);
     uint64_t lo = UINT64_MAX, hi = 0;
     for (uint64_t i = 0; i < n; i++) {
         lo = std::min<uint64_t>(lo, values[i]);
         hi = std::max<uint64_t>(hi, (uint64_t)values[i] + 1);
     }
-    if (hi > ix->dest_h.size()) {
+    if (hi > host.size()) {
         // the entries between the old end and the lowest new value become NONE
         // on the host: they go up too, so no device entry below `len` is ever
         // one the host never wrote
-        lo = std::min<uint64_t>(lo, ix->dest_h.size());
+        lo = std::min<uint64_t>(lo, host.size());
         try {
-            ix->dest_h.resize(hi, NONE);
+            host.resize(hi, NONE);
         } catch (const std::bad_alloc &) {
-            return fail(ix, TM_ENOMEM, "tm_set_dests: out of host memory (the table has one entry per value up to the largest)");
+            return fail(ix, TM_ENOMEM, oom);
         }
     }
-    for (uint64_t i = 0; i < n; i++) ix->dest_h[values[i]] = dests[i];
+    for (uint64_t i = 0; i < n; i++) host[values[i]] = what[i];
     for (int g = 0; g < ix->ngroups; g++) {
-        auto &D = ix->dest[g];
+        auto &D = dev[g];
         if (D.hi > D.lo) {
             D.lo = std::min(D.lo, lo);
             D.hi = std::max(D.hi, hi);
@@ -2475,6 +2491,75 @@ int tm_set_dests(tm_index *ix, uint64_t n, const uint32_t *values, const uint32_
         }
     }
     return TM_OK;
+}
+
+// the aggre pass's scratch on a lane (grow-only; freed with the lane): a
+// bitmap word and a base per 64 positions below cap, the block counts
+int ensure_aggre(tm_index *ix, Lane &ln, uint64_t cap) {
+    FanoutScratch &f = ln.f;
+    if (!f.ag_cnt && hipMalloc(&f.ag_cnt, ((uint64_t)FO_GRID + 1) * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        f.ag_cnt = nullptr;
+        return fail(ix, TM_ENOMEM, "aggre: no device memory for the pass's block counts (16 KiB)");
+    }
+    if (cap <= f.ag_cap && f.ag_bits) return TM_OK;
+    HIPCHK(ix, hipStreamSynchronize(ln.s));   // only this lane's stream uses them
+    if (f.ag_bits) (void)hipFree(f.ag_bits);
+    if (f.ag_pre) (void)hipFree(f.ag_pre);
+    f.ag_bits = nullptr;
+    f.ag_pre = nullptr;
+    f.ag_cap = 0;
+    const uint64_t c = std::max<uint64_t>(std::min<uint64_t>(cap + cap / 4, 0xFFFFFFFFull), 4096);
+    const uint64_t words = (c + 63) / 64;
+    if (hipMalloc(&f.ag_bits, words * 8) != hipSuccess || hipMalloc(&f.ag_pre, words * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        if (f.ag_bits) (void)hipFree(f.ag_bits);
+        f.ag_bits = nullptr;
+        return fail(ix, TM_ENOMEM, "aggre: no device memory for the pass's scratch (12 bytes x cap / 64)");
+    }
+    f.ag_cap = c;
+    return TM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tm_set_dests(tm_index *ix, uint64_t n, const uint32_t *values, const uint32_t *dests) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_set_dests: null handle");
+    if (n && (!values || !dests)) return fail(ix, TM_EINVAL, "tm_set_dests: null buffer");
+    if (!n) return TM_OK;
+    return table_set(ix, ix->dest_h, ix->dest, n, values, dests,
+                     "tm_set_dests: out of host memory (the table has one entry per value up to the largest)");
+}
+
+int tm_set_route_filters(tm_index *ix, uint64_t n, const uint32_t *values, const uint32_t *filter_ids) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_set_route_filters: null handle");
+    if (n && (!values || !filter_ids)) return fail(ix, TM_EINVAL, "tm_set_route_filters: null buffer");
+    if (!n) return TM_OK;
+    return table_set(ix, ix->filt_h, ix->filt, n, values, filter_ids,
+                     "tm_set_route_filters: out of host memory (the table has one entry per value up to the largest)");
+}
+
+int tm_aggre_dev(tm_index *ix, uint32_t n_dests, const uint64_t *dest_offs, const uint32_t *topic, const uint32_t *value,
+                 uint64_t cap, const uint32_t *filter_of, uint64_t filter_len, uint64_t *out_dest_offs,
+                 uint32_t *out_topic, uint32_t *out_value, void *stream) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_aggre_dev: null handle");
+    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_aggre_dev: n_dests must be 1 .. 65536");
+    if (!dest_offs || !out_dest_offs || (cap && (!topic || !value || !out_topic || !out_value)))
+        return fail(ix, TM_EINVAL, "tm_aggre_dev: null buffer");
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
+    std::lock_guard<std::mutex> g(ix->mu);
+    hipStream_t s = pick_stream(ix, stream);
+    Lane *ln = nullptr;
+    int rc, grp = 0;
+    if ((rc = dev_group(ix, grp))) return rc;
+    if ((rc = fanout_lane(ix, s, grp, ln))) return rc;
+    if ((rc = ensure_aggre(ix, *ln, cap))) return rc;
+    if (!filter_of && (rc = filter_upload(ix, grp, s, filter_of, filter_len))) return rc;
+    HIPCHK(ix, launch_aggre(ln->f, n_dests, dest_offs, topic, value, cap, filter_of, filter_len, out_dest_offs, out_topic,
+                            out_value, s));
+    return batch_done(ix, *ln);
 }
 
 int tm_fanout_dev(tm_index *ix, uint64_t n, const uint64_t *hit_offs, const uint32_t *vals, uint64_t cap,
@@ -3067,10 +3152,14 @@ int tm_match_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *
 // does), so the bucket offsets are complete whatever `cap` is; cap only bounds
 // what is copied out.  Same lanes, locking and look-back retry as
 // match_batch_impl.
-int tm_route_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
-                   uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
-                   uint8_t *out_err) {
+// TM_ROUTE_AGGRE: the aggre pass runs on the fan-out's results in the lane's
+// scratch, and only the kept entries are copied back.
+int tm_route_batch_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
+                      uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                      uint8_t *out_err, uint32_t flags) {
     if (!ix) return fail(nullptr, TM_EINVAL, "tm_route_batch: null handle");
+    if (flags & ~(uint32_t)TM_ROUTE_AGGRE) return fail(ix, TM_EINVAL, "tm_route_batch: unknown flag");
+    const bool aggre = flags & TM_ROUTE_AGGRE;
     if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_route_batch: n_dests must be 1 .. 65536");
     if (!to || !out_dest_offsets || (n && !tb && to[n] != to[0]) || (cap && (!out_topic || !out_values)))
         return fail(ix, TM_EINVAL, "tm_route_batch: null buffer");
@@ -3100,6 +3189,12 @@ int tm_route_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *
         if ((rc = grow_dev(ix, s, ln.d_fv, ln.d_fv_cap, vcap))) return rc;
         if ((rc = grow_dev(ix, s, ln.d_fo, ln.d_fo_cap, (uint64_t)n_dests + 2))) return rc;
         if ((rc = ensure_fanout(ix, ln, n_dests, vcap))) return rc;
+        if (aggre) {
+            if ((rc = grow_dev(ix, s, ln.d_at, ln.d_at_cap, vcap))) return rc;
+            if ((rc = grow_dev(ix, s, ln.d_av, ln.d_av_cap, vcap))) return rc;
+            if ((rc = grow_dev(ix, s, ln.d_ao, ln.d_ao_cap, (uint64_t)n_dests + 2))) return rc;
+            if ((rc = ensure_aggre(ix, ln, vcap))) return rc;
+        }
         const DevIndex d = dev_view(ix, ln.r);
         uint32_t tag;
         if ((rc = next_tag(ix, ln, s, tag))) return rc;
@@ -3111,6 +3206,12 @@ int tm_route_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *
         uint64_t dlen = 0;
         if ((rc = dest_upload(ix, ix->rep[ln.r].group, s, dtab, dlen))) return rc;
         HIPCHK(ix, launch_fanout(ln.f, n, dhit, ln.d_vals, vcap, dtab, dlen, n_dests, ln.d_fo, ln.d_ft, ln.d_fv, s));
+        if (aggre) {
+            const uint32_t *ftab = nullptr;
+            uint64_t flen = 0;
+            if ((rc = filter_upload(ix, ix->rep[ln.r].group, s, ftab, flen))) return rc;
+            HIPCHK(ix, launch_aggre(ln.f, n_dests, ln.d_fo, ln.d_ft, ln.d_fv, vcap, ftab, flen, ln.d_ao, ln.d_at, ln.d_av, s));
+        }
         if ((rc = fetch_out(ix, ln, n, rbytes))) return rc;
         if ((rc = batch_done(ix, ln))) return rc;
         g.unlock();
@@ -3130,7 +3231,20 @@ int tm_route_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *
         if ((rc = ensure_ws(ix, n, ln))) return rc;
     }
     // (the lane is still checked out: its buffers are this caller's)
-    const uint64_t keep = std::min(total, cap);
+    if (aggre && total <= cap) {
+        HIPCHK(ix, hipMemcpyAsync(out_dest_offsets, ln.d_ao, ((uint64_t)n_dests + 2) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ix, hipStreamSynchronize(s));
+        const uint64_t kept = std::min(out_dest_offsets[n_dests + 1], cap);   // (K <= total <= cap)
+        if (kept) {
+            HIPCHK(ix, hipMemcpyAsync(out_topic, ln.d_at, kept * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipMemcpyAsync(out_values, ln.d_av, kept * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipStreamSynchronize(s));
+        }
+        if (out_err && n) std::memcpy(out_err, ln.pin_out + (n + 1) * 8, n);
+        return TM_OK;
+    }
+    // (aggre and no room for the fan-out: the un-aggregated sizes, no entries)
+    const uint64_t keep = aggre ? 0 : std::min(total, cap);
     HIPCHK(ix, hipMemcpyAsync(out_dest_offsets, ln.d_fo, ((uint64_t)n_dests + 2) * 8, hipMemcpyDeviceToHost, s));
     if (keep) {
         HIPCHK(ix, hipMemcpyAsync(out_topic, ln.d_ft, keep * 4, hipMemcpyDeviceToHost, s));
@@ -3139,6 +3253,12 @@ int tm_route_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *
     HIPCHK(ix, hipStreamSynchronize(s));
     if (out_err && n) std::memcpy(out_err, ln.pin_out + (n + 1) * 8, n);
     return total > cap ? TM_ECAP : TM_OK;
+}
+
+int tm_route_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
+                   uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                   uint8_t *out_err) {
+    return tm_route_batch_ex(ix, n, tb, to, n_dests, out_dest_offsets, out_topic, out_values, cap, out_err, 0);
 }
 
 // 32-bit offsets (include/tmatch.h).  An in-place batch the one-launch small
@@ -3283,7 +3403,7 @@ constexpr int ROUTE32_OTHER = 1;   // (not a TM_ code)
 
 static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint64_t nbytes,
                             uint32_t n_dests, uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
-                            uint64_t cap, uint8_t *out_err) {
+                            uint64_t cap, uint8_t *out_err, bool aggre) {
     std::unique_lock<std::mutex> g(ix->mu);
     uint8_t *db = nbytes ? pinned_dev(ix, tb, nbytes) : nullptr;
     uint8_t *dof = pinned_dev(ix, to, (n + 1) * 4);
@@ -3305,12 +3425,18 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
         HIPCHK(ix, hipHostMalloc(&ln.fo1_h, FO1_ST_WORDS * 4, hipHostMallocMapped));
         HIPCHK(ix, hipHostGetDevicePointer(reinterpret_cast<void **>(&ln.fo1_d), ln.fo1_h, 0));
     }
+    if (aggre && !ln.fo1_s) HIPCHK(ix, hipMalloc(&ln.fo1_s, FO1_ST_WORDS * 4));
     volatile uint32_t *st = ln.fo1_h;
     uint64_t total = 0, vcap = std::max<uint64_t>({ln.d_vals_cap, 4 * n, 1 << 16});
     for (int attempt = 0, tries = 0;; attempt++) {
         if (vcap > 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch32: more than 2^32 - 1 hits in one batch");
         if ((rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, vcap))) return rc;
         if ((rc = grow_dev(ix, s, ln.d_pr, ln.d_pr_cap, 2 * n + 2))) return rc;
+        if (aggre) {   // k_fo_one's results stay on the device: k_ag_one writes the caller's buffers
+            if ((rc = grow_dev(ix, s, ln.d_ft, ln.d_ft_cap, FO1_ENTRIES))) return rc;
+            if ((rc = grow_dev(ix, s, ln.d_fv, ln.d_fv_cap, FO1_ENTRIES))) return rc;
+            if ((rc = grow_dev(ix, s, ln.d_fo, ln.d_fo_cap, (uint64_t)n_dests + 2))) return rc;
+        }
         if (n) {
             const DevIndex d = dev_view(ix, ln.r);
             uint32_t tag;
@@ -3327,8 +3453,20 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
         uint64_t dlen = 0;
         if ((rc = dest_upload(ix, ix->rep[ln.r].group, s, dtab, dlen))) return rc;
         st[FO1_ST_STATE] = 0;   // (the lane's stream is idle: nothing else writes the words)
-        HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, reinterpret_cast<uint32_t *>(dfo),
-                                     reinterpret_cast<uint32_t *>(dt), reinterpret_cast<uint32_t *>(dv), cap, ln.fo1_d, s));
+        if (!aggre) {
+            HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, reinterpret_cast<uint32_t *>(dfo),
+                                         reinterpret_cast<uint32_t *>(dt), reinterpret_cast<uint32_t *>(dv), cap, ln.fo1_d, s));
+        } else {
+            const uint32_t *ftab = nullptr;
+            uint64_t flen = 0;
+            if ((rc = filter_upload(ix, ix->rep[ln.r].group, s, ftab, flen))) return rc;
+            uint32_t *fo32 = reinterpret_cast<uint32_t *>(ln.d_fo);
+            HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, fo32, ln.d_ft, ln.d_fv,
+                                         FO1_ENTRIES, ln.fo1_s, s));
+            HIPCHK(ix, launch_aggre_one(ln.fo1_s, fo32, n_dests, ln.d_ft, ln.d_fv, ftab, flen,
+                                        reinterpret_cast<uint32_t *>(dfo), reinterpret_cast<uint32_t *>(dt),
+                                        reinterpret_cast<uint32_t *>(dv), cap, ln.fo1_d, s));
+        }
         if ((rc = batch_done(ix, ln))) return rc;
         g.unlock();
         HIPCHK(ix, hipStreamSynchronize(s));
@@ -3364,6 +3502,17 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     uint64_t dlen = 0;
     if ((rc = dest_upload(ix, ix->rep[ln.r].group, s, dtab, dlen))) return rc;
     HIPCHK(ix, launch_fanout_pairs(ln.f, n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, ln.d_fo, ln.d_ft, ln.d_fv, s));
+    const bool ag = aggre && total <= cap;   // (else TM_ECAP: the un-aggregated sizes, no entries)
+    if (ag) {
+        if ((rc = grow_dev(ix, s, ln.d_at, ln.d_at_cap, vcap))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_av, ln.d_av_cap, vcap))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_ao, ln.d_ao_cap, (uint64_t)n_dests + 2))) return rc;
+        if ((rc = ensure_aggre(ix, ln, vcap))) return rc;
+        const uint32_t *ftab = nullptr;
+        uint64_t flen = 0;
+        if ((rc = filter_upload(ix, ix->rep[ln.r].group, s, ftab, flen))) return rc;
+        HIPCHK(ix, launch_aggre(ln.f, n_dests, ln.d_fo, ln.d_ft, ln.d_fv, vcap, ftab, flen, ln.d_ao, ln.d_at, ln.d_av, s));
+    }
     if ((rc = batch_done(ix, ln))) return rc;
     g.unlock();
     std::vector<uint64_t> fo;
@@ -3372,7 +3521,20 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     } catch (const std::bad_alloc &) {
         return fail(ix, TM_ENOMEM, "tm_route_batch32: out of host memory");
     }
-    const uint64_t keep = std::min(total, cap);
+    if (ag) {
+        HIPCHK(ix, hipMemcpyAsync(fo.data(), ln.d_ao, fo.size() * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ix, hipStreamSynchronize(s));
+        const uint64_t kept = std::min(fo[n_dests + 1], cap);   // (K <= total <= cap)
+        if (kept) {
+            HIPCHK(ix, hipMemcpyAsync(out_topic, ln.d_at, kept * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipMemcpyAsync(out_values, ln.d_av, kept * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipStreamSynchronize(s));
+        }
+        for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
+        ix->route_grid++;
+        return TM_OK;
+    }
+    const uint64_t keep = aggre ? 0 : std::min(total, cap);
     HIPCHK(ix, hipMemcpyAsync(fo.data(), ln.d_fo, fo.size() * 8, hipMemcpyDeviceToHost, s));
     if (keep) {
         HIPCHK(ix, hipMemcpyAsync(out_topic, ln.d_ft, keep * 4, hipMemcpyDeviceToHost, s));
@@ -3384,10 +3546,11 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     return total > cap ? TM_ECAP : TM_OK;
 }
 
-int tm_route_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint32_t n_dests,
-                     uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
-                     uint8_t *out_err) {
+int tm_route_batch32_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint32_t n_dests,
+                        uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                        uint8_t *out_err, uint32_t flags) {
     if (!ix) return fail(nullptr, TM_EINVAL, "tm_route_batch32: null handle");
+    if (flags & ~(uint32_t)TM_ROUTE_AGGRE) return fail(ix, TM_EINVAL, "tm_route_batch32: unknown flag");
     if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_route_batch32: n_dests must be 1 .. 65536");
     if (!to || !out_dest_offsets || !out_err || (cap && (!out_topic || !out_values)))
         return fail(ix, TM_EINVAL, "tm_route_batch32: null buffer");
@@ -3397,7 +3560,7 @@ int tm_route_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t
     if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
     if (n <= FO1_TOPICS && n_dests <= FO1_MAX_DESTS && ((uintptr_t)tb & 15) == 0) {
         const int rc = route32_in_place(ix, n, tb, to, nbytes, n_dests, out_dest_offsets, out_topic, out_values, cap,
-                                        out_err);
+                                        out_err, flags & TM_ROUTE_AGGRE);
         if (rc != ROUTE32_OTHER) return rc;
     }
     // every other batch: widened, tm_route_batch, narrowed (the buffers kept per
@@ -3409,11 +3572,17 @@ int tm_route_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t
     } catch (const std::bad_alloc &) {
         return fail(ix, TM_ENOMEM, "tm_route_batch32: out of host memory");
     }
-    const int rc = tm_route_batch(ix, n, tb, o64.data(), n_dests, fo.data(), out_topic, out_values, cap, out_err);
+    const int rc = tm_route_batch_ex(ix, n, tb, o64.data(), n_dests, fo.data(), out_topic, out_values, cap, out_err, flags);
     if (rc != TM_OK && rc != TM_ECAP) return rc;
     for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
     ix->route_grid++;
     return rc;
+}
+
+int tm_route_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint32_t n_dests,
+                     uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                     uint8_t *out_err) {
+    return tm_route_batch32_ex(ix, n, tb, to, n_dests, out_dest_offsets, out_topic, out_values, cap, out_err, 0);
 }
 
 int tm_match_batch32_dev(tm_index *ix, uint64_t n, const uint8_t *bytes, const uint32_t *offs, uint32_t *hit_offs,

@@ -111,6 +111,7 @@ ROUTER_COPIES = 2   # src/emqx_router_gpu.erl ?COPIES
 
 MAX_DEST_CLASSES = 65536   # tm_route_batch's n_dests bound; a later class stays unrouted on the device
 UNROUTED = 0xFFFFFFFF
+NO_FILTER = 0xFFFFFFFF     # tm_set_route_filters: never a filter's id
 
 
 def dest_class(dest):
@@ -123,11 +124,14 @@ def dest_class(dest):
 
 
 class ByDest(dict):
-    """{destination class: [(message index, Route)]}; .errors: {message index: exception} (errors="return")"""
+    """{destination class: [(message index, Route)]}; .errors: {message index: exception} (errors="return");
+    .host_rows: {destination class: positions in its list of the rows aggre/1 on the device did not
+    see -- the bag's rows} (filled when the buckets were asked for with aggre=True)"""
 
     def __init__(self):
         super().__init__()
         self.errors = {}
+        self.host_rows = {}
 
 
 class MirrorDown(RuntimeError):
@@ -155,6 +159,11 @@ class Router:
         self._dest_ids: dict = {}
         self._dest_classes: list = []
         self._dest_lock = threading.Lock()
+        # wildcard filters interned to the u32 ids the device compares (tm_set_route_filters):
+        # filter -> [id, live keys]; an id is never handed out again while it is live
+        self._filter_ids: dict = {}
+        self._filter_live: set = set()
+        self._filter_next = 0
         self._mirror = self._adopt(mirror if mirror is not None else self._mirror_factory())
         self._alive = True                       # the mirror process is running (its handle is served)
         self._mailbox: list = []                 # table events not yet drained by the event process
@@ -230,7 +239,44 @@ class Router:
         tm_set_dests for the keys it inserts, before the delta inserting them."""
         if hasattr(mirror, "dest_fn"):
             mirror.dest_fn = lambda key: self.dest_id(ti.get_id(key))
+        if hasattr(mirror, "filter_fn"):
+            # a fresh mirror is a fresh device table: it takes every key anew
+            with self._dest_lock:
+                self._filter_ids, self._filter_live = {}, set()
+            mirror.filter_fn = self.filter_id
+            mirror.filter_release = self.filter_release
         return mirror
+
+    # ------------------------------------------------------- filter interning
+    def filter_id(self, key) -> int:
+        """The u32 id of key's filter for one more live key of it: interned on
+        the filter's first key, from a counter that skips ids still live and
+        NO_FILTER.  The mirror ships it (tm_set_route_filters) ahead of the
+        delta that inserts the key."""
+        f = key[0]
+        with self._dest_lock:
+            e = self._filter_ids.get(f)
+            if e is None:
+                i = self._filter_next
+                while i in self._filter_live or i == NO_FILTER:
+                    i = (i + 1) & 0xFFFFFFFF
+                self._filter_next = (i + 1) & 0xFFFFFFFF
+                self._filter_live.add(i)
+                e = self._filter_ids[f] = [i, 0]
+            e[1] += 1
+            return e[0]
+
+    def filter_release(self, key):
+        """One live key of key's filter is gone; with the last one its id."""
+        f = key[0]
+        with self._dest_lock:
+            e = self._filter_ids.get(f)
+            if e is None:
+                return
+            e[1] -= 1
+            if e[1] <= 0:
+                del self._filter_ids[f]
+                self._filter_live.discard(e[0])
 
     # ------------------------------------------------------------ the mirror
     def mirror_sync(self, keys, commit: bool = False):
@@ -450,7 +496,7 @@ class Router:
     def match_routes(self, topic):
         return self.match_routes_batch([topic])[0]
 
-    def match_routes_by_dest(self, topics, errors: str = "raise") -> ByDest:
+    def match_routes_by_dest(self, topics, errors: str = "raise", aggre: bool = False) -> ByDest:
         """match_routes/1 over a batch, regrouped by destination class on the
         device (tm_route_batch): {class: [(message index, Route)]}, what
         do_route2/2 (emqx_broker.erl:401-406) would visit hit by hit, as one
@@ -459,7 +505,14 @@ class Router:
         (the bag's rows, then the filter matches).  Routes the device leaves
         unrouted (a class beyond MAX_DEST_CLASSES) are resolved here through
         the same decode path.  errors as for match_routes_batch: "return"
-        collects a bad topic's exception in .errors[message index]."""
+        collects a bad topic's exception in .errors[message index].
+        aggre: the device also applies aggre/1 to its buckets (TM_ROUTE_AGGRE):
+        a class's filter matches then hold one route per (message, filter) --
+        the first in traversal order -- where a group has members on several
+        nodes.  The device copies the unrouted bucket whole, so its keys get
+        the same rule here, per class, when they are resolved.  The bag's rows
+        are as without it; .host_rows names their positions, for a caller that
+        still has to deduplicate them (Broker.publish_batch_by_dest)."""
         topics = [bytes(t) for t in topics]
         mirror = self._live_mirror()
         out = ByDest()
@@ -470,7 +523,7 @@ class Router:
                 classes = list(self._dest_classes)
             n_dests = max(len(classes), 1)
             route = mirror.route_kids32 if self._route_in_place else mirror.route_kids
-            doff, tidx, kids, err = route(topics, n_dests)
+            doff, tidx, kids, err = route(topics, n_dests, aggre=True) if aggre else route(topics, n_dests)
             if len(err) and (err == 4).any():   # (the library returns TM_EDEVICE instead; never a client error)
                 raise ti.DeviceError(-3, "batch failed on the device (err flag 4)")
             for i in map(int, err.nonzero()[0]):
@@ -502,6 +555,8 @@ class Router:
                         for k in keys:
                             cls = dest_class(ti.get_id(k))
                             g = groups.setdefault(cls, {}).setdefault(("f", i), [])
+                            if aggre and any(x[0] == k[0] for x in g):
+                                continue   # aggre/1 for what the device copied whole: one key per filter
                             if g:
                                 mixed.add((cls, i))
                             g.append(k)
@@ -510,6 +565,8 @@ class Router:
         for cls, per_msg in groups.items():
             rows = []
             for i in sorted({m if isinstance(m, int) else m[1] for m in per_msg}):
+                if aggre and i in per_msg:
+                    out.host_rows.setdefault(cls, set()).update(range(len(rows), len(rows) + len(per_msg[i])))
                 rows.extend((i, r) for r in per_msg.get(i, ()))
                 keys = per_msg.get(("f", i), ())
                 if (cls, i) in mixed:   # from two buckets: back into traversal (term) order

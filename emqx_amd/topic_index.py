@@ -68,6 +68,12 @@ class Tab:
         # delta that inserts the key
         self.dest_fn = None
         self._dests: list = []          # pending (kid, destination id)
+        # aggre/1 on the device: filter_fn(key) -> the owner's u32 id of the key's topic
+        # filter (equal filters, equal ids), shipped with tm_set_route_filters in the same
+        # flush as the destinations; filter_release(key) tells the owner a key is gone
+        self.filter_fn = None
+        self.filter_release = None
+        self._filts: list = []          # pending (kid, filter id)
         self._route_pool: list = []     # route_kids32: idle sets of pinned batch buffers (host_array)
 
     # -- key <-> device encoding
@@ -112,6 +118,10 @@ class Tab:
             d = np.array(self._dests, dtype=np.uint32).reshape(-1, 2)
             self._dests = []
             self._index.set_dests(d[:, 0], d[:, 1])
+        if self._filts:
+            f = np.array(self._filts, dtype=np.uint32).reshape(-1, 2)
+            self._filts = []
+            self._index.set_route_filters(f[:, 0], f[:, 1])
         if not self._ops:
             return
         ops = np.array([o[0] for o in self._ops], dtype=np.uint8)
@@ -154,6 +164,8 @@ class Tab:
             self._kid[key] = kid
             if self.dest_fn is not None:
                 self._dests.append((kid, self.dest_fn(key)))
+            if self.filter_fn is not None:
+                self._filts.append((kid, self.filter_fn(key)))
             self._queue(_native.TM_OP_INSERT, key, kid)
         self._records[key] = record
 
@@ -165,6 +177,8 @@ class Tab:
             self._queue(_native.TM_OP_DELETE, key, kid)
             self._keys[kid] = None
             self._released.append(kid)
+            if self.filter_release is not None:
+                self.filter_release(key)
 
     def attach(self, rows, batch_size: int = 1000) -> int:
         """Boot the device mirror from an existing table (emqx_topic_index_gpu:
@@ -209,15 +223,16 @@ class Tab:
         hit, vals, err = self._index.match_batch(blob, offs)
         return [vals[hit[i]:hit[i + 1]] for i in range(len(topics))], err
 
-    def route_kids(self, topics, n_dests: int):
+    def route_kids(self, topics, n_dests: int, aggre: bool = False):
         """tm_route_batch -> (dest_offsets u64[n_dests + 2], topic index u32[],
         kid u32[], err u8[n]): destination b's (topic index, kid) pairs are
         [dest_offsets[b], dest_offsets[b + 1]), in topic order and traversal
         order inside a topic; bucket n_dests: kids without a destination
-        below n_dests.  Decoded like match_kids' results."""
+        below n_dests.  Decoded like match_kids' results.  aggre: the buckets
+        after aggre/1 (TM_ROUTE_AGGRE; the filter ids of filter_fn)."""
         self.flush()
         blob, offs = _native.pack_strings(topics)
-        return self._index.route_batch(blob, offs, n_dests)
+        return self._index.route_batch(blob, offs, n_dests, aggre=aggre)
 
     def _route_set(self, n: int, nbytes: int, n_dests: int, cap: int) -> dict:
         """A set of pinned buffers (host_array) large enough for the batch, from
@@ -242,7 +257,7 @@ class Tab:
         for a in s.values():
             self._index.host_free(a)
 
-    def route_kids32(self, topics, n_dests: int):
+    def route_kids32(self, topics, n_dests: int, aggre: bool = False):
         """route_kids through tm_route_batch32 on pooled pinned buffers: a
         micro-batch is matched and fanned out in place (two launches, no
         staging copy).  One retry on TM_ECAP, sized from the bucket offsets.
@@ -252,7 +267,7 @@ class Tab:
         blob, offs = _native.pack_strings(topics)
         n, nbytes = len(offs) - 1, int(offs[-1])
         if nbytes >= 1 << 32:
-            return self._index.route_batch(blob, offs, n_dests)
+            return self._index.route_batch(blob, offs, n_dests, aggre=aggre)
         s = self._route_set(n, nbytes, n_dests, max(4 * n, 1024))
         try:
             s["blob"][:nbytes] = blob[:nbytes]
@@ -260,7 +275,8 @@ class Tab:
             for attempt in (0, 1):
                 out = (s["doff"], s["topic"], s["vals"], s["err"])
                 try:
-                    doff, tidx, kids, err = self._index.route_batch32(s["blob"], s["offs"][: n + 1], n_dests, out)
+                    doff, tidx, kids, err = self._index.route_batch32(s["blob"], s["offs"][: n + 1], n_dests, out,
+                                                                      aggre=aggre)
                     break
                 except _native.TmError as e:
                     if e.code != _native.TM_ECAP or attempt:

@@ -476,6 +476,88 @@ int tm_route_batch32(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const 
                      uint32_t n_dests, uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
                      uint64_t cap, uint8_t *out_err);
 
+/* aggre/1 on the device (ABI minor 14): one entry per (To, destination).
+ * emqx_broker:aggre/1 (emqx_broker.erl:408-424), the middle call of
+ * do_publish/1, reduces {To, {Group, Node}} to {To, Group} and lists:usort's
+ * the list: a shared group with members on k nodes -- k routes of one filter
+ * -- gets a message once.  The calls above return match_routes' hits bucketed
+ * by destination, the k copies included.  A topic's keys come in ascending
+ * term order of their filters, the keys of one filter contiguous ("Output"),
+ * and the fan-out is a stable partition; so inside one destination bucket the
+ * entries of one topic that share a filter are adjacent, and the usort is
+ * "drop an entry whose predecessor in the same bucket has the same topic and
+ * the same filter".  Node routes are never touched ({Filter, Dest} keys are
+ * unique), so no group flag is needed.
+ *
+ * tm_set_route_filters: the index's value -> To table, the twin of
+ * tm_set_dests.  filter_ids[i] is the caller's id of the topic filter of the
+ * route values[i] names: equal filters have equal ids, different live filters
+ * different ids.  Ids are only compared, never index anything, and need not be
+ * dense.  0xFFFFFFFF (also: never set) is "no filter known": such an entry
+ * equals nothing and is never dropped.  Thread safe with every other call; an
+ * aggre queued after it returns sees the new table (only the entries changed
+ * since a device's last use are uploaded, in stream order before it), one
+ * already queued may see either state.  Set a value's filter before inserting
+ * its key.  The host table has one u32 per value up to the largest one set.
+ *
+ * tm_aggre_dev: device buffers, asynchronous on `stream`.  The input is what
+ * tm_fanout_dev / tm_fanout_dev_pairs write: d_dest_offsets[n_dests + 2],
+ * d_topic and d_value; E = min(d_dest_offsets[n_dests + 1], cap), cap clamped
+ * to 2^32 - 1.  f(v) = d_filter_of[v] if v < filter_len, else 0xFFFFFFFF
+ * (d_filter_of == NULL: the index's own table, filter_len ignored).  Entry
+ * q < E is DROPPED iff q is not the first position of its bucket, q is not in
+ * the unrouted bucket n_dests (which mixes classes the device cannot tell
+ * apart and is copied whole), d_topic[q] == d_topic[q - 1] and
+ * f(d_value[q]) == f(d_value[q - 1]) != 0xFFFFFFFF.  A run of k equal entries
+ * keeps its first.  The definition holds for any input (merged shards whose
+ * filters are not contiguous included); for one index's traversal order it
+ * equals aggre/1.  In numpy:
+ *   keep = ones(E); same = (t[1:E]==t[:E-1]) & (f[1:E]==f[:E-1]) & (f[1:E]!=NONE)
+ *   keep[1:] = ~same; keep[doff[b]] = 1 for every b with doff[b] < E
+ *   keep[min(doff[n_dests], E):] = 1
+ *   out = entries[keep]; out_doff[b] = keep[:min(doff[b], E)].sum()
+ * Output: the kept entries in input order in d_out_topic / d_out_value,
+ * d_out_dest_offsets[b] = the number kept before min(d_dest_offsets[b], E),
+ * d_out_dest_offsets[n_dests + 1] = the kept total K.  Nothing at or past K is
+ * written in either output array, the inputs are not modified, no input
+ * position >= E is read.  The outputs MUST NOT overlap the inputs.  Five
+ * launches over the fan-out's fixed grid, no block waiting for another; the
+ * stream's scratch (kept with the fan-out's, tm_stream_release) holds 12
+ * bytes per 64 entries of cap and 16 KiB (TM_ENOMEM if that cannot be had).
+ * It is sized from cap, not from the total, which only the device knows when
+ * the call is queued: pass the size of the buffers (what the fan-out was
+ * given), never 2^32 - 1 for "no bound" -- that asks for about 800 MB a stream.
+ * TM_EINVAL before any device work: a null handle, a null required pointer,
+ * n_dests == 0 or n_dests > 65536.
+ *
+ * tm_route_batch_ex / tm_route_batch32_ex: tm_route_batch / tm_route_batch32
+ * with trailing flags.  flags == 0 is the old call exactly; TM_ROUTE_AGGRE
+ * returns the aggregated buckets (the index's own filter table);
+ * any other bit is TM_EINVAL.  With TM_ROUTE_AGGRE out_dest_offsets holds the
+ * aggregated bounds, [n_dests + 1] = K, and only the K kept entries are
+ * written.  TM_ECAP when the total BEFORE aggregation exceeds cap (the
+ * fan-out needs that room): out_dest_offsets then holds the un-aggregated
+ * bucket sizes -- an upper bound to size the retry from --, the entries are
+ * undefined.  Lanes, read-your-writes, the device-failure retry and the
+ * out_err rules are unchanged.  tm_route_batch_ex: match, fan-out and aggre
+ * all in the lane's scratch.  tm_route_batch32_ex in place, under exactly
+ * tm_route_batch32's conditions: the one-launch fan-out writes the lane's
+ * scratch and a second launch of one workgroup compacts it into the caller's
+ * buffers -- still one synchronisation and no copy out; past 16384 entries
+ * the grid kernels run on the lane and the result is copied out.
+ * TM_DEBUG_ROUTE_ONE / TM_DEBUG_ROUTE_GRID count these calls too. */
+#define TM_ROUTE_AGGRE 1u
+int tm_set_route_filters(tm_index *h, uint64_t n, const uint32_t *values, const uint32_t *filter_ids);
+int tm_aggre_dev(tm_index *h, uint32_t n_dests, const uint64_t *d_dest_offsets, const uint32_t *d_topic,
+                 const uint32_t *d_value, uint64_t cap, const uint32_t *d_filter_of, uint64_t filter_len,
+                 uint64_t *d_out_dest_offsets, uint32_t *d_out_topic, uint32_t *d_out_value, void *stream);
+int tm_route_batch_ex(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint64_t *topic_offsets,
+                      uint32_t n_dests, uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
+                      uint64_t cap, uint8_t *out_err, uint32_t flags);
+int tm_route_batch32_ex(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint32_t *topic_offsets,
+                        uint32_t n_dests, uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
+                        uint64_t cap, uint8_t *out_err, uint32_t flags);
+
 /* Release the batch scratch kept for `stream` (after its batches finish);
  * a caller that retires a stream calls this.  No reference counterpart. */
 int tm_stream_release(tm_index *h, void *stream);

@@ -47,9 +47,32 @@ interleaved), one JSON line per batch size with three legs:
 
 (a)'s and (c)'s outputs are compared first (they must be identical); the line
 also says which fan-out (c) took (TM_DEBUG_ROUTE_ONE / _GRID).
+
+--aggre: aggre/1 on the device (nothing of the first part runs).  The batch is
+matched as pairs and fanned out with tm_fanout_dev_pairs over a destination
+table that puts a share p of the values on destination 0 (the local node) and
+the rest uniformly on the others, so that a topic's hits meet in one bucket;
+then tm_aggre_dev is timed against the torch composition a user would write on
+the same arrays (shifted compares, a boolean-mask index, bincount + cumsum over
+the kept entries' buckets), outputs compared first (identical), for two inputs:
+none_dropped -- p = 0.55 and filter_of[v] = v (every value its own filter) --
+and quarter -- filter_of built from the fanned-out arrays: the neighbours of one
+topic inside one bucket are the pairs that can be dropped; the distinct value
+pairs among them, in a seeded random order, are given equal ids (the ids of a
+prefix of that order, merged transitively), and the prefix is found by
+bisection so that the dropped share, counted with the torch composition before
+anything is timed, comes closest to a quarter.  p = 0.55 is kept when that gets
+within 3 points of a quarter; else p = 0.75 and p = 1 are tried and the closest
+input is taken (with many destinations a topic's hits seldom meet in a bucket
+unless most values are local).  The line says which p was taken, how many
+pairs were merged and what was dropped.  The call's median stands beside
+tm_fanout_dev_pairs' on the same entries, timed the same way.  With --small: a fourth leg, tm_route_batch32_ex with
+TM_ROUTE_AGGRE (the index's filter table: one id per distinct filter), its
+outputs compared with the numpy definition applied to (c)'s.
 """
 import argparse
 import json
+import os
 import sys
 from pathlib import Path
 
@@ -198,6 +221,160 @@ def synthetic_skew(torch, ix, a, s, n, total, n_dests=16):
           flush=True)
 
 
+def torch_aggre(torch, doff, t, v, E, fof, dest_of, n_dests):
+    """the composition a user would write on a fan-out's output (every value routed)"""
+    t, v = t[:E], v[:E]
+    f = fof[v]
+    keep = torch.ones(E, dtype=torch.bool, device=v.device)
+    keep[1:] = ~((t[1:] == t[:-1]) & (f[1:] == f[:-1]) & (f[1:] != -1))
+    heads = doff[:n_dests + 1]
+    keep[heads[heads < E]] = True
+    out_t, out_v = t[keep], v[keep]
+    offs = torch.zeros(n_dests + 2, dtype=torch.int64, device=v.device)
+    offs[1:] = torch.cumsum(torch.bincount(dest_of[out_v], minlength=n_dests + 1), 0)
+    return offs, out_t, out_v
+
+
+def merged_ids(nvals, pa, pb):
+    """filter ids with pa[i] and pb[i] equal for every i, transitively: the smallest value of each group"""
+    lab = np.arange(nvals, dtype=np.int64)
+    while len(pa):
+        new = lab.copy()
+        m = np.minimum(lab[pa], lab[pb])
+        np.minimum.at(new, pa, m)
+        np.minimum.at(new, pb, m)
+        new = new[new]
+        if np.array_equal(new, lab):
+            break
+        lab = new
+    return lab
+
+
+def quarter_table(torch, fo, total, n_dests, nvals, dest_of, want=0.25, seed=11):
+    """filter_of from a fan-out's output (see the docstring) -> (pairs merged, dropped share, filter_of)"""
+    t, v = fo[1][:total], fo[2][:total]
+    head = torch.zeros(total, dtype=torch.bool, device=v.device)
+    heads = fo[0][:n_dests + 1]
+    head[heads[heads < total]] = True
+    cand = (t[1:] == t[:-1]) & ~head[1:]
+    va, vb = v[:-1][cand].cpu().numpy().astype(np.int64), v[1:][cand].cpu().numpy().astype(np.int64)
+    keys, cnt = np.unique(np.minimum(va, vb) * nvals + np.maximum(va, vb), return_counts=True)
+    # rare pairs first (a seeded random order among equals): the share then grows in small steps
+    # until the few pairs of popular filters, which are worth whole points each, come in
+    keys = keys[np.lexsort((np.random.default_rng(seed).random(len(keys)), cnt))]
+    if os.environ.get("FANOUT_BENCH_VERBOSE"):
+        top = np.sort(cnt)[::-1][:8]
+        print(f"quarter_table: {len(va)} candidate neighbours of {total} entries, {len(keys)} distinct pairs, "
+              f"most frequent {top.tolist()}", file=sys.stderr, flush=True)
+    pa, pb = keys // nvals, keys % nvals
+
+    def dropped(k):
+        fof = torch.from_numpy(merged_ids(nvals, pa[:k], pb[:k]).astype(np.int32)).to(v.device)
+        kept = len(torch_aggre(torch, fo[0], fo[1], fo[2], total, fof, dest_of, n_dests)[1])
+        return 1 - kept / total, fof
+
+    lo, hi = 0, len(keys)   # the share grows with the prefix: bisect for the first prefix at or above `want`
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if dropped(mid)[0] < want:
+            lo = mid + 1
+        else:
+            hi = mid
+    cands = [(abs(dropped(k)[0] - want), k) for k in {max(lo - 1, 0), lo}]
+    k = min(cands)[1]
+    frac, fof = dropped(k)
+    return k, frac, fof
+
+
+def aggre_legs(torch, ix, a, s, n, d_blob, d_offs, d_err, total, most, nvals, fs_len):
+    """--aggre: tm_aggre_dev against the torch composition, and beside tm_fanout_dev_pairs"""
+    dev = d_blob.device
+    cap_p = total + 4096 * most
+    d_pairs = torch.zeros(2 * n + 2, dtype=torch.int32, device=dev)
+    d_pv = torch.zeros(cap_p, dtype=torch.int32, device=dev)
+    ix.match_batch_dev_pairs(n, d_blob.data_ptr(), d_offs.data_ptr(), d_pairs.data_ptr(), d_pv.data_ptr(), cap_p,
+                             d_err.data_ptr(), s)
+    torch.cuda.synchronize()
+    assert int(d_pairs[2 * n]) & 0xFFFFFFFF == total and int(d_pairs[2 * n + 1]) & 0xFFFFFFFF <= cap_p
+    rng = np.random.default_rng(7)
+    u, spread = rng.random(nvals), rng.integers(0, 1 << 30, nvals)
+    for n_dests in a.dests:
+        fo = (torch.zeros(n_dests + 2, dtype=torch.int64, device=dev), torch.zeros(total, dtype=torch.int32, device=dev),
+              torch.zeros(total, dtype=torch.int32, device=dev))
+        out = (torch.zeros(n_dests + 2, dtype=torch.int64, device=dev), torch.zeros(total, dtype=torch.int32, device=dev),
+               torch.zeros(total, dtype=torch.int32, device=dev))
+        dest_of = torch.zeros(nvals, dtype=torch.int32, device=dev)
+
+        def fanout():
+            ix.fanout_dev_pairs(n, d_pairs.data_ptr(), d_pv.data_ptr(), cap_p, n_dests, fo[0].data_ptr(), fo[1].data_ptr(),
+                                fo[2].data_ptr(), dest_of.data_ptr(), nvals, s)
+
+        def table(p):
+            dest_of.copy_(torch.from_numpy(np.where(u < p, 0, spread % n_dests).astype(np.int32)))
+
+        best = None   # (distance from a quarter, p, pairs merged, filter_of)
+        for p in (0.55, 0.75, 1.0):
+            table(p)
+            fanout()
+            torch.cuda.synchronize()
+            k, frac, fof = quarter_table(torch, fo, total, n_dests, nvals, dest_of)
+            if best is None or abs(frac - 0.25) < best[0]:
+                best = (abs(frac - 0.25), p, k, fof)
+            if best[0] <= 0.03:
+                break
+        inputs = {"none_dropped": (0.55, torch.arange(nvals, dtype=torch.int32, device=dev), "v"),
+                  "quarter": (best[1], best[3], f"{best[2]} neighbouring value pairs merged")}
+        for name, (p_local, fof, how) in inputs.items():
+            table(p_local)
+            fanout()
+            torch.cuda.synchronize()
+            assert int(fo[0][n_dests + 1]) == total
+
+            def hip():
+                ix.aggre_dev(n_dests, fo[0].data_ptr(), fo[1].data_ptr(), fo[2].data_ptr(), total, out[0].data_ptr(),
+                             out[1].data_ptr(), out[2].data_ptr(), fof.data_ptr(), nvals, s)
+
+            def tor():
+                return torch_aggre(torch, fo[0], fo[1], fo[2], total, fof, dest_of, n_dests)
+
+            hip()
+            r = tor()
+            torch.cuda.synchronize()
+            K = int(out[0][n_dests + 1])
+            assert K == len(r[1]) and torch.equal(out[0], r[0]) and torch.equal(out[1][:K], r[1]) and \
+                torch.equal(out[2][:K], r[2]), f"n_dests {n_dests} {name}: the two paths differ"
+            del r
+            th, tt = timed_pair(torch, hip, tor, a.warmup, a.reps)
+            th2, tf = timed_pair(torch, hip, fanout, a.warmup, a.reps)
+            h, t, h2, f = stats(th), stats(tt), stats(th2), stats(tf)
+            nbytes = 12 * total + 8 * K + 12 * ((total + 63) // 64) + 16 * (n_dests + 2)
+            print(json.dumps({"tool": "fanout_bench", "kind": "aggre", "filters": fs_len, "topics": n, "entries": total,
+                              "n_dests": n_dests, "input": name, "local_share": p_local, "filter_of": how, "kept": K,
+                              "dropped_fraction": round(1 - K / total, 4), "reps": a.reps, "hip": h, "torch": t,
+                              "torch_over_hip": round(t["median_ms"] / h["median_ms"], 2),
+                              "hip_beside_fanout": h2, "fanout_dev_pairs": f,
+                              "aggre_over_fanout": round(h2["median_ms"] / f["median_ms"], 3),
+                              "algorithmic_bytes": nbytes,
+                              "hip_algorithmic_GBps": round(nbytes / (h["median_ms"] * 1e-3) / 1e9, 1),
+                              "identical": True}), flush=True)
+            assert h["p90_ms"] < t["p10_ms"], f"n_dests {n_dests} {name}: tm_aggre_dev is not clearly below the torch composition"
+
+
+def _np_aggre(doff, t, v, fof, n_dests):
+    """include/tmatch.h's numpy definition on a whole fan-out"""
+    doff = doff.astype(np.int64)
+    E = int(doff[n_dests + 1])
+    f = fof[v[:E]]
+    keep = np.ones(E, bool)
+    if E > 1:
+        keep[1:] = ~((t[1:E] == t[:E - 1]) & (f[1:] == f[:-1]) & (f[1:] != 0xFFFFFFFF))
+    heads = doff[:n_dests + 1]
+    keep[heads[heads < E]] = True
+    keep[min(int(doff[n_dests]), E):] = True
+    before = np.concatenate([[0], np.cumsum(keep)])
+    return before[np.minimum(doff, E)], t[:E][keep], v[:E][keep]
+
+
 def small_batches(a, sizes=(64, 1024, 4096, 16384), n_dests=16, warmup=20, reps=200):
     """--small: host-to-host latency of a micro-batch's route fan-out, three legs interleaved"""
     import time
@@ -206,6 +383,14 @@ def small_batches(a, sizes=(64, 1024, 4096, 16384), n_dests=16, warmup=20, reps=
     rng = np.random.default_rng(7)
     nvals = int(fs.vals.max()) + 1
     ix.set_dests(np.arange(nvals, dtype=np.uint32), rng.integers(0, n_dests, nvals).astype(np.uint32))
+    fof = None
+    if a.aggre:   # one id per distinct filter, in order of first sight
+        ids: dict = {}
+        raw = fs.blob.tobytes()
+        fof = np.full(nvals, 0xFFFFFFFF, np.uint32)
+        for k in range(len(fs)):
+            fof[int(fs.vals[k])] = ids.setdefault(raw[int(fs.offs[k]):int(fs.offs[k + 1])], len(ids))
+        ix.set_route_filters(np.arange(nvals, dtype=np.uint32), fof)
     ix.apply(np.ones(len(fs), np.uint8), fs.blob, fs.offs, fs.vals)
     ix.sync(None)
     P = _native._ptr
@@ -243,7 +428,22 @@ def small_batches(a, sizes=(64, 1024, 4096, 16384), n_dests=16, warmup=20, reps=
             np.array_equal(o64[1][:total], o32[1][:total]) and np.array_equal(o64[2][:total], o32[2][:total]), \
             f"n {n}: tm_route_batch and tm_route_batch32 differ"
         legs = (leg_a, leg_b, leg_c)
-        ms = ([], [], [])
+        extra = {}
+        if a.aggre:
+            o32a = (ix.host_array(n_dests + 2, np.uint32), ix.host_array(cap, np.uint32), ix.host_array(cap, np.uint32))
+
+            def leg_d():
+                return lib.tm_route_batch32_ex(h, n, P(blob), P(offs32), n_dests, P(o32a[0]), P(o32a[1]), P(o32a[2]), cap,
+                                               P(err), _native.TM_ROUTE_AGGRE)
+
+            assert leg_d() == 0
+            e_off, e_t, e_v = _np_aggre(o32[0], o32[1], o32[2], fof, n_dests)
+            K = int(e_off[-1])
+            assert np.array_equal(o32a[0].astype(np.int64), e_off) and np.array_equal(o32a[1][:K], e_t) and \
+                np.array_equal(o32a[2][:K], e_v), f"n {n}: the aggregated call differs from the definition"
+            legs = (leg_a, leg_b, leg_c, leg_d)
+            extra = {"kept": K}
+        ms = tuple([] for _ in legs)
         for r in range(warmup + reps):
             for k, f in enumerate(legs):
                 t0 = time.perf_counter_ns()
@@ -252,11 +452,19 @@ def small_batches(a, sizes=(64, 1024, 4096, 16384), n_dests=16, warmup=20, reps=
                 if r >= warmup:
                     ms[k].append((t1 - t0) * 1e-6)
         sa, sb, sc = stats(ms[0]), stats(ms[1]), stats(ms[2])
+        if a.aggre:
+            sd = stats(ms[3])
+            sd["p50_ms"], sd["p99_ms"] = sd["median_ms"], round(float(np.percentile(ms[3], 99)), 4)
+            sc = dict(sc, p99_ms=round(float(np.percentile(ms[2], 99)), 4))
+            extra.update({"route_batch32_aggre": sd, "d_minus_c_ms": round(sd["median_ms"] - sc["median_ms"], 4)})
+            for x in o32a:
+                ix.host_free(x)
         print(json.dumps({"tool": "fanout_bench", "kind": "small", "filters": len(fs), "topics": n, "entries": total,
                           "n_dests": n_dests, "warmup": warmup, "reps": reps, "route32_fanout": path,
                           "route_batch": sa, "match32_pairs": sb, "route_batch32": sc,
                           "c_minus_b_ms": round(sc["median_ms"] - sb["median_ms"], 4),
-                          "a_minus_c_ms": round(sa["median_ms"] - sc["median_ms"], 4), "identical": True}), flush=True)
+                          "a_minus_c_ms": round(sa["median_ms"] - sc["median_ms"], 4), "identical": True, **extra}),
+              flush=True)
         for x in (blob, offs32, offs64, err, pairs, pvals, *o32, *o64):
             ix.host_free(x)
 
@@ -270,12 +478,14 @@ def main():
     p.add_argument("--dests", type=int, nargs="+", default=[16, 4096])
     p.add_argument("--form", choices=["csr", "pairs", "both"], default="csr")
     p.add_argument("--small", action="store_true", help="the NIF's micro-batches, host to host (see above)")
+    p.add_argument("--aggre", action="store_true", help="aggre/1 on the device (see above); with --small: a fourth leg")
+    p.add_argument("--sizes", type=int, nargs="+", default=None, help="--small: the batch sizes")
     a = p.parse_args()
     import torch
     if not torch.cuda.is_available():
         sys.exit("fanout_bench: no HIP device (this measurement has no CPU form)")
     if a.small:
-        small_batches(a)
+        small_batches(a, **({"sizes": tuple(a.sizes)} if a.sizes else {}))
         return
     dev = torch.device("cuda")
     fs = wl.filters(3, a.filters)
@@ -299,6 +509,9 @@ def main():
     nvals = int(fs.vals.max()) + 1
     assert int(d_vals[:total].max()) < nvals and int(d_vals[:total].min()) >= 0
     most = int((d_hit[1:] - d_hit[:-1]).max())
+    if a.aggre:
+        aggre_legs(torch, ix, a, s, n, d_blob, d_offs, d_err, total, most, nvals, len(fs))
+        return
     rng = np.random.default_rng(7)
     for n_dests in a.dests:
         # every value routed, the destinations uniform: a cluster's nodes / a deployment's groups
