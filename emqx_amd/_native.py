@@ -47,6 +47,8 @@ TM_DEBUG_CMB_SPIN = 23
 TM_DEBUG_PATCH_ZC = 24
 TM_DEBUG_FANOUT_GRID = 25   # (get only) one-wave blocks of a fan-out pass
 TM_DEBUG_ROUTE_ONE, TM_DEBUG_ROUTE_GRID = 26, 27   # (get only) route_batch32 calls per fan-out path
+# (get only) the node annexed to a vocab-hint slot (depth << 32 | children; all ones: none); hints that disagree (0)
+TM_DEBUG_ANNEX0, TM_DEBUG_ANNEX1, TM_DEBUG_HINT_AUDIT = 28, 29, 30
 MAX_DESTS = 65536           # tm_fanout_dev / tm_route_batch: n_dests is 1 .. MAX_DESTS
 
 

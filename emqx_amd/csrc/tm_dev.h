@@ -26,6 +26,9 @@ struct DevIndex {
     uint32_t depth, xlen_max;
     uint64_t xlen_mask;
     uint32_t hdesc;   // keys with a '#' that is not last are stored (NLIT_HDESC nodes exist)
+    // depth of the node annexed to each vocab-hint slot (tm_layout.h HINT_*): the
+    // walk keeps that slot's hint of its word at this level (NONE: slot unused)
+    uint32_t anx_depth[ANX_SLOTS];
 };
 
 constexpr int FAST_L = 8;        // levels handled by the main walk kernel (LDS frontier)

@@ -83,7 +83,7 @@ struct NodeAux {
 
 struct WordRef { const uint8_t *p; uint32_t n; int kind; };   // kind: 0 binary, 1 '+', 2 '#'
 
-// literal children of a node (its nlit word also carries NLIT_HDESC)
+// literal children of a node (its nlit word also carries NLIT_HDESC and the annex flags)
 inline uint32_t nlit_of(const Node &n) { return n.nlit & NLIT_MASK; }
 
 }  // namespace
@@ -206,6 +206,10 @@ struct tm_index {
     Mirror<uint32_t> wseq; uint64_t wseq_dead = 0;   // words of erased long exact keys
     Mirror<uint32_t> wbits; uint32_t wb_words = 0;   // wide nodes' child bitmaps, wb_words words each
     std::vector<uint32_t> free_wbits; std::set<uint32_t> wide;
+    // the nodes annexed to the vocab entries' hint slots (tm_layout.h HINT_*;
+    // NONE: slot unused), chosen among the wide nodes by annex_designate
+    uint32_t anx[ANX_SLOTS] = {NONE, NONE};
+    bool anx_dirty = false;   // a node turned wide / stopped being wide, or an annexed node's child count moved
     // literal edges per (level, wid) and distinct edge words per level: a wide
     // node whose children cover most of its level's words probes its child
     // table directly (its line's bitmap pointer NONE, wide_dense)
@@ -381,13 +385,12 @@ void pack8(const uint8_t *p, uint32_t n, uint32_t &b0, uint32_t &b1) {
 }
 
 bool vocab_eq(tm_index *ix, const VocabEntry &e, uint64_t h, const uint8_t *p, uint32_t n) {
-    if (e.tag != vocab_tag(h, n)) return false;
-    if (n <= VINL) {
+    if (n <= VINL) {   // (the tag's upper bits are hints)
         uint32_t b0, b1;
         pack8(p, n, b0, b1);
-        return e.b0 == b0 && e.b1 == b1;
+        return vocab_short_eq(e.tag, e.b0, e.b1, n, b0, b1);
     }
-    return e.b1 == n && !memcmp(ix->wpool.h.data() + e.b0, p, n);
+    return e.tag == vocab_tag(h, n) && e.b1 == n && !memcmp(ix->wpool.h.data() + e.b0, p, n);
 }
 
 uint32_t vocab_find(tm_index *ix, const uint8_t *p, uint32_t n) {
@@ -693,6 +696,7 @@ void wide_cover(tm_index *ix) {
 }
 
 void to_wide(tm_index *ix, uint32_t node) {
+    ix->anx_dirty = true;
     if (ix->wide.empty()) ix->wb_words = 0;
     ix->wide.insert(node);
     if ((uint64_t)ix->wb_words * 32 < ix->wid_next) {
@@ -704,7 +708,12 @@ void to_wide(tm_index *ix, uint32_t node) {
     wide_fill(ix, node);
 }
 
+void annex_set(tm_index *ix, uint32_t s, uint32_t p);
+int annex_slot(const tm_index *ix, uint32_t p);
+
 void from_wide(tm_index *ix, uint32_t node) {
+    if (const int s = annex_slot(ix, node); s >= 0) annex_set(ix, (uint32_t)s, NONE);
+    ix->anx_dirty = true;
     ix->free_wbits.push_back(ix->aux[node].bm);
     ix->aux[node].bm = NONE;
     ix->wide.erase(node);
@@ -756,6 +765,91 @@ void summary_refresh(tm_index *ix, uint32_t x) {
     if (x != ROOT && ix->aux[x].is_plus) summary_refresh1(ix, ix->aux[x].parent);
 }
 
+// ---- vocab-entry hints (tm_layout.h HINT_*)
+
+// the hint slot node p is annexed to, or -1
+int annex_slot(const tm_index *ix, uint32_t p) {
+    for (uint32_t s = 0; s < ANX_SLOTS; s++) if (ix->anx[s] == p) return (int)s;
+    return -1;
+}
+
+// write slot s's 12 bits of word wid's entry (short words only: a long word's
+// tag is its hash, and the walk probes for it as without hints)
+void hint_put(tm_index *ix, uint32_t s, uint32_t wid, uint32_t hint) {
+    const uint32_t sl = ix->wslot[wid];
+    if (sl == NONE) return;
+    VocabEntry &e = ix->vocab.h[sl];
+    if (e.wid != wid || (e.tag & 0xFFu) > VINL) return;
+    const uint32_t sh = s ? HINT_SHIFT1 : HINT_SHIFT0;
+    const uint32_t t = (e.tag & ~(HINT_MASK << sh)) | hint << sh;
+    if (t != e.tag) { e.tag = t; ix->vocab.touch(sl); }
+}
+
+// The hint is a pure function of the child's slot in p's table, so it is
+// written again from the slot wherever a slot of an annexed parent is put,
+// erased or refreshed -- in the same delta batch, hence in the same patch (or
+// before the same whole-table upload) as the slot itself.
+void hint_sync(tm_index *ix, uint32_t p, uint32_t wid) {
+    const int s = annex_slot(ix, p);
+    if (s < 0) return;
+    const Node &pn = ix->nodes.h[p];
+    uint32_t hint = 0;
+    if (nlit_of(pn) > KINL) {
+        const uint32_t sl = ctab_find(ix, pn.kw[0], pn.kw[1], wid);
+        if (sl != NONE) { const CSlot &c = ix->ctab.h[pn.kw[0] + sl]; hint = hint_of_sum(c.sum_lo, c.sum_hi); }
+    }
+    hint_put(ix, (uint32_t)s, wid, hint);
+}
+
+// (re)write slot s in every short word's entry from node p's table (p == NONE:
+// the slot is released; its bits are left as they are -- no node carries its
+// flag and no view names its depth, so nothing reads them -- and written again
+// here when the slot is next given out).  Rare; ships the vocab whole.
+void annex_set(tm_index *ix, uint32_t s, uint32_t p) {
+    const uint32_t flag = s ? NLIT_ANX1 : NLIT_ANX0;
+    const uint32_t old = ix->anx[s];
+    if (old != NONE) { ix->nodes.h[old].nlit &= ~flag; ix->nodes.touch(old); }
+    ix->anx[s] = p;
+    if (p == NONE) return;
+    const uint32_t sh = s ? HINT_SHIFT1 : HINT_SHIFT0;
+    for (VocabEntry &e : ix->vocab.h)
+        if (e.wid != NONE && (e.tag & 0xFFu) <= VINL) e.tag &= ~(HINT_MASK << sh);
+    Node &pn = ix->nodes.h[p];
+    for (uint32_t i = 0; i <= pn.kw[1]; i++) {
+        const CSlot &c = ix->ctab.h[pn.kw[0] + i];
+        if (c.wid == NONE) continue;
+        VocabEntry &e = ix->vocab.h[ix->wslot[c.wid]];
+        if ((e.tag & 0xFFu) <= VINL) e.tag |= hint_of_sum(c.sum_lo, c.sum_hi) << sh;
+    }
+    ix->vocab.dirty.set_all();
+    pn.nlit |= flag;
+    ix->nodes.touch(p);
+}
+
+// Choose the annexed nodes: the wide nodes (depth >= 1) with the most literal
+// children.  Hysteresis: a slot's node is replaced only when it stopped being
+// wide (from_wide released it) or a wide node that holds no slot has at least
+// twice its children.  Run with wide_dense, before the next patch.
+void annex_designate(tm_index *ix) {
+    if (!ix->anx_dirty) return;
+    ix->anx_dirty = false;
+    for (int round = 0; round < (int)ANX_SLOTS; round++) {
+        uint32_t best = NONE;   // the widest wide node that holds no slot
+        for (uint32_t node : ix->wide) {
+            if (ix->aux[node].depth < 1 || annex_slot(ix, node) >= 0) continue;
+            if (best == NONE || nlit_of(ix->nodes.h[node]) > nlit_of(ix->nodes.h[best])) best = node;
+        }
+        if (best == NONE) return;
+        uint32_t s = ANX_SLOTS;   // a free slot, else the slot whose node has the fewest children
+        for (uint32_t k = 0; k < ANX_SLOTS && s == ANX_SLOTS; k++) if (ix->anx[k] == NONE) s = k;
+        if (s == ANX_SLOTS) {
+            s = nlit_of(ix->nodes.h[ix->anx[1]]) < nlit_of(ix->nodes.h[ix->anx[0]]) ? 1 : 0;
+            if (nlit_of(ix->nodes.h[best]) < 2 * (uint64_t)nlit_of(ix->nodes.h[ix->anx[s]])) return;
+        }
+        annex_set(ix, s, best);
+    }
+}
+
 void summary_refresh1(tm_index *ix, uint32_t x) {
     if (x == ROOT) return;
     const NodeAux &a = ix->aux[x];
@@ -779,6 +873,7 @@ void summary_refresh1(tm_index *ix, uint32_t x) {
     if (c.sum_lo != (uint32_t)m || c.sum_hi != (uint32_t)(m >> 32)) {
         c.sum_lo = (uint32_t)m; c.sum_hi = (uint32_t)(m >> 32);
         ix->ctab.touch(pn.kw[0] + sl);
+        hint_sync(ix, p, a.wid);
     }
 }
 
@@ -853,7 +948,7 @@ void wide_dense(tm_index *ix) {
 void child_add(tm_index *ix, uint32_t node, uint32_t wid, uint32_t child) {
     ix->nlinks++;
     lvl_edge(ix, ix->aux[node].depth, wid, true);
-    if (ix->aux[node].bm != NONE) ix->dense_dirty = true;
+    if (ix->aux[node].bm != NONE) { ix->dense_dirty = true; ix->anx_dirty = true; }
     Node *n = &ix->nodes.h[node];
     if (nlit_of(*n) < KINL) {
         for (uint32_t k = 0; k < KINL; k++)
@@ -865,6 +960,7 @@ void child_add(tm_index *ix, uint32_t node, uint32_t wid, uint32_t child) {
         ctab_put(ix, n->kw[0], n->kw[1], wid, child, node_psum(ix, child));
         if (ix->aux[node].bm != NONE) wide_bit(ix, node, wid, true);
         else set_bloom(*n, wid);
+        hint_sync(ix, node, wid);
     }
     n->nlit++;
     if (nlit_of(*n) == WIDE_LIT && ix->aux[node].bm == NONE) { to_wide(ix, node); n = &ix->nodes.h[node]; }
@@ -875,7 +971,7 @@ void child_add(tm_index *ix, uint32_t node, uint32_t wid, uint32_t child) {
 void child_remove(tm_index *ix, uint32_t node, uint32_t wid) {
     ix->nlinks--;
     lvl_edge(ix, ix->aux[node].depth, wid, false);
-    if (ix->aux[node].bm != NONE) ix->dense_dirty = true;
+    if (ix->aux[node].bm != NONE) { ix->dense_dirty = true; ix->anx_dirty = true; }
     Node &n = ix->nodes.h[node];
     if (nlit_of(n) <= KINL) {
         for (uint32_t k = 0; k < KINL; k++)
@@ -884,6 +980,7 @@ void child_remove(tm_index *ix, uint32_t node, uint32_t wid) {
     } else {
         ctab_erase(ix, n.kw[0], n.kw[1], wid);
         wide_bit(ix, node, wid, false);
+        hint_sync(ix, node, wid);
         n.nlit--;
         if (ix->aux[node].bm != NONE && nlit_of(n) < WIDE_LIT) from_wide(ix, node);
         if (nlit_of(n) == KINL) {   // back to inline mode
@@ -899,7 +996,7 @@ void child_remove(tm_index *ix, uint32_t node, uint32_t wid) {
 
 bool node_empty(tm_index *ix, uint32_t id) {
     const Node &n = ix->nodes.h[id];
-    return n.plus == NONE && n.nlit == 0 && n.hash_cnt == 0 && n.exact_cnt == 0 && ix->aux[id].hdesc == 0;
+    return n.plus == NONE && nlit_of(n) == 0 && n.hash_cnt == 0 && n.exact_cnt == 0 && ix->aux[id].hdesc == 0;
 }
 
 void node_prune(tm_index *ix, uint32_t id) {
@@ -1270,7 +1367,7 @@ void word_key_op(tm_index *ix, bool ins, const std::vector<WordRef> &w, uint32_t
     if (hpos < w.size()) {   // a '#'-not-last key: P's count (the path exists: the key was inserted)
         a.hdesc += ins ? 1 : -1;
         ix->n_hdesc_keys += ins ? 1 : -1;
-        nd.nlit = nlit_of(nd) | (a.hdesc ? NLIT_HDESC : 0);
+        nd.nlit = (nd.nlit & ~NLIT_HDESC) | (a.hdesc ? NLIT_HDESC : 0);
         ix->nodes.touch(node);
         summary_refresh(ix, node);
         if (!ins) node_prune(ix, node);
@@ -1672,6 +1769,7 @@ DevIndex dev_view_build(tm_index *ix, int r) {
     d.xlen_mask = 0;
     for (size_t k = 0; k < xc.size() && k < 64; k++) if (xc[k]) d.xlen_mask |= 1ull << k;
     d.hdesc = ix->n_hdesc_keys != 0;
+    for (uint32_t s = 0; s < ANX_SLOTS; s++) d.anx_depth[s] = ix->anx[s] == NONE ? NONE : ix->aux[ix->anx[s]].depth;
     return d;
 }
 
@@ -1921,7 +2019,7 @@ int drain_lanes(tm_index *ix) {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 14u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 15u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 
@@ -2079,6 +2177,7 @@ int tm_apply_deltas_ex(tm_index *ix, uint64_t n, const uint8_t *ops, const uint8
                    key_flags ? key_flags[i] : 0, w, wids);
         reclaim(ix);
         wide_dense(ix);
+        annex_designate(ix);
     } catch (const std::bad_alloc &) {
         return fail(ix, TM_ENOMEM, "tm_apply_deltas: out of host memory");
     }
@@ -2117,12 +2216,13 @@ constexpr auto COMMIT_WAIT = std::chrono::milliseconds(20);
 // what a launch reads of a copy's cached view, field by field (the struct has
 // padding); a field added to DevIndex belongs here too, or a change of it alone
 // would let a commit wait again
-static_assert(sizeof(DevIndex) == 120, "DevIndex changed: compare the new field in same_view");
+static_assert(sizeof(DevIndex) == 128, "DevIndex changed: compare the new field in same_view");
 static bool same_view(const DevIndex &a, const DevIndex &b) {
     return a.vocab == b.vocab && a.vmask == b.vmask && a.wpool == b.wpool && a.nodes == b.nodes && a.ctab == b.ctab &&
            a.vals == b.vals && a.exact == b.exact && a.xmask == b.xmask && a.xfp == b.xfp && a.wseq == b.wseq &&
            a.wbits == b.wbits && a.wcap == b.wcap && a.depth == b.depth && a.xlen_max == b.xlen_max &&
-           a.xlen_mask == b.xlen_mask && a.hdesc == b.hdesc;
+           a.xlen_mask == b.xlen_mask && a.hdesc == b.hdesc && a.anx_depth[0] == b.anx_depth[0] &&
+           a.anx_depth[1] == b.anx_depth[1];
 }
 
 int tm_commit(tm_index *ix, uint64_t n, const uint8_t *ops, const uint8_t *fb, const uint64_t *fo,
@@ -3765,6 +3865,34 @@ int tm_debug_get(tm_index *ix, uint32_t key, uint64_t *value) {
         uint64_t v = 0;
         for (uint32_t node : ix->wide) v += key == TM_DEBUG_WIDE_NODES || ix->nodes.h[node].kw[2] == NONE;
         *value = v;
+        break;
+    }
+    case TM_DEBUG_ANNEX0:
+    case TM_DEBUG_ANNEX1: {
+        std::lock_guard<std::mutex> g(ix->img);
+        const uint32_t p = ix->anx[key - TM_DEBUG_ANNEX0];
+        *value = p == NONE ? ~0ull : (uint64_t)ix->aux[p].depth << 32 | nlit_of(ix->nodes.h[p]);
+        break;
+    }
+    case TM_DEBUG_HINT_AUDIT: {   // every short word's hint of every annexed node against that node's table
+        std::lock_guard<std::mutex> g(ix->img);
+        uint64_t bad = 0;
+        for (uint32_t s = 0; s < ANX_SLOTS; s++) {
+            const uint32_t p = ix->anx[s];
+            if (p == NONE) continue;
+            const Node &pn = ix->nodes.h[p];
+            const uint32_t flag = s ? NLIT_ANX1 : NLIT_ANX0;
+            bad += (pn.nlit & (NLIT_ANX0 | NLIT_ANX1)) != flag || nlit_of(pn) < WIDE_LIT;
+            for (const VocabEntry &e : ix->vocab.h) {
+                if (e.wid == NONE || (e.tag & 0xFFu) > VINL) continue;
+                const uint32_t sl = ctab_find(ix, pn.kw[0], pn.kw[1], e.wid);
+                const CSlot *c = sl == NONE ? nullptr : &ix->ctab.h[pn.kw[0] + sl];
+                bad += ((e.tag >> (s ? HINT_SHIFT1 : HINT_SHIFT0)) & HINT_MASK) != (c ? hint_of_sum(c->sum_lo, c->sum_hi) : 0u);
+            }
+        }
+        for (uint32_t id = 0; id < ix->nodes.h.size(); id++)   // no other line carries a flag
+            bad += (ix->nodes.h[id].nlit & (NLIT_ANX0 | NLIT_ANX1)) && annex_slot(ix, id) < 0;
+        *value = bad;
         break;
     }
     default: return fail(ix, TM_EINVAL, "tm_debug_get: unknown key");

@@ -77,24 +77,7 @@ __device__ __forceinline__ uint32_t child_maybe(const DevIndex &ix, const uint4 
     return bloom_bit(n2, n3, child_bit(h));
 }
 
-// can a child Q (summarised as Node.psum / CSlot.sum, tm_layout.h) matter to
-// a topic of L levels when entered at level lq?  At lq == L, Q must emit or cut
-// the walk (NLIT_HDESC); below it Q must emit ('#' terminal) or go on: a
-// literal child for word wq, or its '+' child QQ, which in turn must be able to
-// matter at lq + 1 (word wq2)
-__device__ __forceinline__ bool child_alive(uint32_t lo, uint32_t hi, uint32_t lq, uint32_t L, uint32_t wq,
-                                            uint32_t wq2) {
-    const uint64_t m = (uint64_t)hi << 32 | lo;
-    constexpr uint32_t AT_END = PSUM_HASH | PSUM_EXACT | PSUM_HDESC;
-    if (lq == L) return (m & AT_END) != 0;
-    if (m & PSUM_HASH) return true;
-    if (wq != NONE && ((m >> (PSUM_BQ + psum_bit(child_hash(wq)))) & 1u)) return true;
-    if (!(m & PSUM_PLUS)) return false;
-    const uint32_t qq = (uint32_t)(m >> PSUM_QQ) & 15u;
-    if (lq + 1 == L) return (qq & AT_END) != 0;
-    if (qq & (PSUM_HASH | PSUM_PLUS)) return true;
-    return wq2 != NONE && ((m >> (PSUM_BQQ + psum_bit(child_hash(wq2)))) & 1u);
-}
+// (child_alive, and its shadow on a vocab-entry hint, hint_alive: tm_layout.h)
 
 // Empty asm "uses": pin a loaded value at this point on every path.  Without
 // them the compiler sinks loads into the branches that read each field (one
@@ -167,31 +150,31 @@ __device__ __forceinline__ uint64_t word_hash_dev(const WordAcc &w, const Src &s
     return word_hash_finish(h, w.len);
 }
 
-// continue a vocab probe sequence from `slot` (exact: tag, then bytes: the
-// word at `start` of src when it is longer than VINL)
+// continue a vocab probe sequence from `slot` (exact: length and packed bytes
+// of a short word; tag, then the bytes of the word at `start` of src when it is
+// longer than VINL)
 template <class Src>
 __device__ uint32_t vocab_probe(const DevIndex &ix, uint32_t slot, uint32_t tag, uint32_t len, uint32_t b0,
                                 uint32_t b1, const Src &src, uint64_t start) {
     for (;;) {
         const uint4 e = ld4(ix.vocab + slot);   // tag, wid, b0, b1
         if (e.y == NONE) return NONE;
-        if (e.x == tag) {
-            if (len <= VINL) {
-                if (e.z == b0 && e.w == b1) return e.y;
-            } else if (e.w == len && bytes_eq(ix.wpool + e.z, src, start, len)) {
-                return e.y;
-            }
+        if (len <= VINL) {
+            if (vocab_short_eq(e.x, e.z, e.w, len, b0, b1)) return e.y;
+        } else if (e.x == tag && e.w == len && bytes_eq(ix.wpool + e.z, src, start, len)) {
+            return e.y;
         }
         slot = (slot + 1) & ix.vmask;
     }
 }
 
-// the same for a word of <= VINL bytes (tag, then its packed bytes)
-__device__ uint32_t vocab_probe_short(const DevIndex &ix, uint32_t slot, uint32_t tag, uint32_t b0, uint32_t b1) {
+// the same for a word of <= VINL bytes; `tag`: the entry's own (its hints) on a hit
+__device__ uint32_t vocab_probe_short(const DevIndex &ix, uint32_t slot, uint32_t len, uint32_t b0, uint32_t b1,
+                                      uint32_t &tag) {
     for (;;) {
         const uint4 e = ld4(ix.vocab + slot);   // tag, wid, b0, b1
         if (e.y == NONE) return NONE;
-        if (e.x == tag && e.z == b0 && e.w == b1) return e.y;
+        if (vocab_short_eq(e.x, e.z, e.w, len, b0, b1)) { tag = e.x; return e.y; }
         slot = (slot + 1) & ix.vmask;
     }
 }
@@ -236,6 +219,11 @@ struct LdsStore {
     static constexpr bool deferred = true;   // vocab probes of short words after tokenisation
     static constexpr bool cuts = ML > FAST_L;
     static constexpr bool need = ML > FAST_L || LITE;   // resolve only need_levels(), scan the rest
+    // The main walk's store keeps the vocab-entry hints (tm_layout.h HINT_*) of
+    // the words at the annex slots' levels, parked in pend[0]: dead once the
+    // probes are done (push takes levels >= 1 only).  Slot s at bits 16 s:
+    // the 12 hint bits | HINT_KNOWN (unset: no hint, probe as without one).
+    static constexpr bool hints = ML == FAST_L && !LITE;
     uint32_t *wid, *pend;
     uint8_t *len8;                           // [level][thread] word lengths (deferred probes)
     uint32_t stride;
@@ -263,7 +251,9 @@ struct LdsStore {
     __device__ __forceinline__ uint32_t word_b0(uint32_t l) const { return wid[l * stride]; }
     __device__ __forceinline__ uint32_t word_b1(uint32_t l) const { return pend[l * stride]; }
     __device__ __forceinline__ uint32_t word_len(uint32_t l) const { return len8[l * stride]; }
-    __device__ __forceinline__ void push(uint32_t l, uint32_t node) {
+    __device__ __forceinline__ void park_hints(uint32_t v) { pend[0] = v; }
+    __device__ __forceinline__ uint32_t parked_hints() const { return pend[0]; }
+    __device__ __forceinline__ void push(uint32_t l, uint32_t node) {   // (l >= 1)
         pend[l * stride] = node; mask |= 1ull << l;
     }
     __device__ __forceinline__ bool pop(uint32_t &l, uint32_t &node) {
@@ -282,6 +272,7 @@ struct GlobalStore {
     static constexpr bool deferred = false;
     static constexpr bool cuts = true;
     static constexpr bool need = true;
+    static constexpr bool hints = false;
     uint32_t *wid;
     uint2 *stk;
     uint8_t *plus_at;
@@ -313,6 +304,14 @@ enum { RC_OK = 0, RC_BADARG = 1, RC_DEEP = 2 };
 // 8 waves per SIMD -- a budget small code changes can tip: check the
 // -Rpass-analysis=kernel-resource-usage remark after every change)
 constexpr uint32_t VGROUP = 6;
+
+// a parked hint is known (LdsStore::hints); what the entry `tag` of the word at
+// level l parks: its 12 bits of each annex slot whose node sits at depth l
+constexpr uint32_t HINT_KNOWN = 0x1000u;
+__device__ __forceinline__ uint32_t hints_of_level(const DevIndex &ix, uint32_t l, uint32_t tag) {
+    return (l == ix.anx_depth[0] ? ((tag >> HINT_SHIFT0) & HINT_MASK) | HINT_KNOWN : 0u) |
+           (l == ix.anx_depth[1] ? (((tag >> HINT_SHIFT1) & HINT_MASK) | HINT_KNOWN) << 16 : 0u);
+}
 
 // '/' bytes in [p, end), p 16-byte aligned: four 16-byte loads in flight per
 // round trip, bytes compared a word at a time
@@ -447,9 +446,9 @@ __device__ int tokenize(const DevIndex &ix, const Src &src, uint64_t beg, uint64
         // (unused levels read slot 0) and consumes all of them, so no load is
         // left pending on a skipped branch -- the compiler would otherwise drain
         // vmcnt(0) before reusing its registers and serialise the probes.
+        uint32_t park = 0;   // (S::hints)
         for (uint32_t base = 0; base < (S::need ? L >> 24 : L); base += VGROUP) {
             uint4 e[VGROUP];
-            uint32_t tg[VGROUP];
             bool use[VGROUP];
 #pragma unroll
             for (uint32_t k = 0; k < VGROUP; k++) {
@@ -458,27 +457,30 @@ __device__ int tokenize(const DevIndex &ix, const Src &src, uint64_t beg, uint64
                 const uint32_t ls = use[k] ? l : 0;
                 const uint32_t len = st.word_len(ls);
                 const uint64_t h = word_hash_short(st.word_b0(ls), st.word_b1(ls), len);
-                tg[k] = vocab_tag(h, len);
                 e[k] = ld4(ix.vocab + (use[k] ? ((uint32_t)h & ix.vmask) : 0u));
             }
 #pragma unroll
             for (uint32_t k = 0; k < VGROUP; k++) {
                 const uint32_t l = use[k] ? base + k : 0;
                 const uint32_t b0 = st.word_b0(l), b1 = st.word_b1(l);
-                const bool hit = e[k].x == tg[k] && e[k].z == b0 && e[k].w == b1;
+                const uint32_t len = st.word_len(l);
+                const bool hit = vocab_short_eq(e[k].x, e[k].z, e[k].w, len, b0, b1);
                 uint32_t wid = e[k].y == NONE ? NONE : hit ? e[k].y : NONE - 1;
+                uint32_t tag = e[k].x;
                 pin(wid);   // consume e[k] here on every path
                 if (use[k]) {
-                    if (wid == NONE - 1) {   // rare at load <= 1/2: walk the probe sequence on
+                    if (wid == NONE - 1) {   // rare at load <= 1/4: walk the probe sequence on
                         // (the hash again: six home slots kept across the loads spill k_walk_fast)
-                        const uint32_t len = st.word_len(l);
                         const uint64_t h = word_hash_short(b0, b1, len);
-                        wid = vocab_probe_short(ix, ((uint32_t)h + 1) & ix.vmask, tg[k], b0, b1);
+                        wid = vocab_probe_short(ix, ((uint32_t)h + 1) & ix.vmask, len, b0, b1, tag);
                     }
                     st.set_wid(l, wid);
+                    if constexpr (S::hints) park |= hints_of_level(ix, l, tag);
                 }
             }
         }
+        // (a level resolved before the loop -- a long word -- parks nothing: no hint)
+        if constexpr (S::hints) st.park_hints(park);
     }
     if constexpr (S::deferred && S::need) {
       const uint32_t Lw = L >> 24;
@@ -586,7 +588,18 @@ __device__ int dfs(const DevIndex &ix, uint32_t L, bool dollar, S &st, EM &em) {
                     lit = inl;
                 } else {
                     const uint32_t h = child_hash(w);
-                    if (child_maybe(ix, n1, n2, n3, w, h) & 1u) {
+                    // an annexed node: the hint w's vocab entry carried says the
+                    // child is absent or cannot matter -- no bitmap load, no probe
+                    bool probe = true;
+                    if constexpr (S::hints) {
+                        if (n1.y & (NLIT_ANX0 | NLIT_ANX1)) {
+                            const uint32_t hk = st.parked_hints() >> ((n1.y & NLIT_ANX1) ? 16 : 0);
+                            if (hk & HINT_KNOWN)
+                                probe = (hk & HINT_CHILD) &&
+                                        hint_alive(hk & HINT_MASK, l + 1, L, l + 1 < L ? st.get_wid(l + 1) : NONE);
+                        }
+                    }
+                    if (probe && (child_maybe(ix, n1, n2, n3, w, h) & 1u)) {
                         uint32_t slo, shi;
                         lit = ctab_find(ix, n2.x, n2.y, w, h, slo, shi);
                         if (lit != NONE && !child_alive(slo, shi, l + 1, L, l + 1 < L ? st.get_wid(l + 1) : NONE,

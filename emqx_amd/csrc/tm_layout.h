@@ -41,7 +41,8 @@ constexpr uint32_t VINL = 8;    // inline word bytes in a vocab entry
 constexpr uint32_t XINL = 10;   // inline wids in an exact entry
 
 struct alignas(16) VocabEntry {   // 16 B
-    uint32_t tag;                  // hash bits 32..55 | min(len, 255); 0 with wid NONE = empty
+    uint32_t tag;                  // len <= 8: len | two 12-bit child hints << 8 (HINT_*, below)
+                                   // len  > 8: hash bits 32..55 | min(len, 255); 0 with wid NONE = empty
     uint32_t wid;                  // NONE = empty slot
     uint32_t b0, b1;               // len <= 8: the bytes, little endian, zero padded
                                    // len  > 8: b0 = offset of the word in wpool, b1 = len
@@ -84,7 +85,7 @@ struct alignas(64) Node {          // 64 B
     uint32_t plus;                 // '+' child or NONE
     uint32_t hash_off, hash_cnt;   // values of filter <path>/#
     uint32_t exact_off, exact_cnt; // values of filter <path> (word-list form)
-    uint32_t nlit;                 // literal children (NLIT_MASK; > KINL: table mode) | NLIT_HDESC
+    uint32_t nlit;                 // literal children (NLIT_MASK; > KINL: table mode) | NLIT_HDESC | NLIT_ANX0/1
     uint32_t psum_lo, psum_hi;     // summary of the '+' child (PSUM_*)
     uint32_t kw[KINL];             // inline: child wids (NONE = free); table mode: kw[0] = table
                                    // offset (CSlots), kw[1] = table size - 1, kw[2..3] Bloom bits 0-63
@@ -104,7 +105,9 @@ struct alignas(64) Node {          // 64 B
 //     literal branch P[0..q)/W_q (the '+' frame turns lower into a seek,
 //     :302-320).
 constexpr uint32_t NLIT_HDESC = 0x80000000u;
-constexpr uint32_t NLIT_MASK = 0x7FFFFFFFu;
+// NLIT_ANX0 / NLIT_ANX1: the node is annexed to hint slot 0 / 1 (HINT_*, below)
+constexpr uint32_t NLIT_ANX0 = 0x40000000u, NLIT_ANX1 = 0x20000000u;
+constexpr uint32_t NLIT_MASK = 0x1FFFFFFFu;
 
 // Summary of a child Q (Node.psum for the '+' child, CSlot.sum for a literal
 // child), two levels deep so a '+' chain that dies one level down is skipped too:
@@ -115,6 +118,25 @@ constexpr uint32_t NLIT_MASK = 0x7FFFFFFFu;
 //   bits 36-63 28-bit Bloom of QQ's literal child wids
 constexpr uint32_t PSUM_HASH = 1u, PSUM_EXACT = 2u, PSUM_PLUS = 4u, PSUM_HDESC = 8u;   // psum_lo bits (<< 4: QQ's)
 constexpr uint32_t PSUM_QQ = 4, PSUM_BQ = 8, PSUM_BQQ = 36, PSUM_BLOOM = 28;
+
+// Vocab-entry hints.  A word of <= VINL bytes is compared exactly by its length
+// and packed bytes, so the 24 hash bits of its entry's tag are free: they hold
+// two 12-bit hints, one per annex slot.  The host annexes up to two of the
+// widest nodes (NLIT_ANX0 / NLIT_ANX1 in their line; DevIndex::anx_depth).  The
+// hint of word w in slot s describes the literal child Q that slot's node has
+// for w -- a redundant copy of that child's CSlot summary, kept in the line the
+// walk fetches anyway to resolve w:
+//   bit 11      Q exists
+//   bits 10..7  Q has a '#' terminal / an exact terminal / NLIT_HDESC / a '+' child
+//   bits 6..0   7-bit Bloom of Q's literal child wids (the slot's 28-bit Bloom
+//               folded four to one, so it saturates with it)
+// All zero: the node has no child for w.  At an annexed node a walk that holds
+// the hint of its level's word skips the child-table probe when the hint says
+// no child or !hint_alive (the conservative shadow of child_alive).
+constexpr uint32_t HINT_BITS = 12, HINT_MASK = 0xFFFu, HINT_SHIFT0 = 8, HINT_SHIFT1 = 20;
+constexpr uint32_t HINT_CHILD = 0x800u, HINT_HASH = 0x400u, HINT_EXACT = 0x200u, HINT_HDESC = 0x100u,
+                   HINT_PLUS = 0x80u, HINT_BLOOM = 7;
+constexpr uint32_t ANX_SLOTS = 2;
 
 struct alignas(16) ExactEntry {    // 64 B
     uint32_t h_lo, h_hi;           // hash of the wid sequence
@@ -157,8 +179,14 @@ TM_HD uint64_t word_hash_short(uint32_t b0, uint32_t b1, uint32_t len) {
 }
 TM_HD uint64_t word_hash_finish(uint64_t fnv, uint32_t len) { return mix64(fnv ^ ((uint64_t)len << 56)); }
 
+// tag of a fresh entry: a short word's carries no hints yet (it has no children)
 TM_HD uint32_t vocab_tag(uint64_t h, uint32_t len) {
+    if (len <= VINL) return len;
     return ((uint32_t)(h >> 32) & 0xFFFFFF00u) | (len < 255 ? len : 255);
+}
+// does entry (tag, e0, e1) hold the word of len <= VINL bytes packed as (b0, b1)?
+TM_HD bool vocab_short_eq(uint32_t tag, uint32_t e0, uint32_t e1, uint32_t len, uint32_t b0, uint32_t b1) {
+    return (tag & 0xFFu) == len && e0 == b0 && e1 == b1;
 }
 
 // child table hash: low bits pick the slot, the high 16 bits the Bloom bits.
@@ -177,6 +205,42 @@ TM_HD uint32_t child_bit(uint32_t h) { return ((h >> 16) * 192u) >> 16; }      /
 TM_HD uint32_t psum_bit(uint32_t h) { return ((h >> 16) * PSUM_BLOOM) >> 16; }   // 0..27, + PSUM_BQ / PSUM_BQQ
 // Bloom word j (bits 32j .. 32j+31) of a table-mode node line
 TM_HD uint32_t &bloom_word(Node &n, uint32_t j) { return j < 2 ? n.kw[2 + j] : n.kc[j - 2]; }
+
+// can a child Q (summarised as Node.psum / CSlot.sum) matter to a topic of L
+// levels when entered at level lq?  At lq == L, Q must emit or cut the walk
+// (NLIT_HDESC); below it Q must emit ('#' terminal) or go on: a literal child
+// for word wq, or its '+' child QQ, which in turn must be able to matter at
+// lq + 1 (word wq2)
+TM_HD bool child_alive(uint32_t lo, uint32_t hi, uint32_t lq, uint32_t L, uint32_t wq, uint32_t wq2) {
+    const uint64_t m = (uint64_t)hi << 32 | lo;
+    constexpr uint32_t AT_END = PSUM_HASH | PSUM_EXACT | PSUM_HDESC;
+    if (lq == L) return (m & AT_END) != 0;
+    if (m & PSUM_HASH) return true;
+    if (wq != NONE && ((m >> (PSUM_BQ + psum_bit(child_hash(wq)))) & 1u)) return true;
+    if (!(m & PSUM_PLUS)) return false;
+    const uint32_t qq = (uint32_t)(m >> PSUM_QQ) & 15u;
+    if (lq + 1 == L) return (qq & AT_END) != 0;
+    if (qq & (PSUM_HASH | PSUM_PLUS)) return true;
+    return wq2 != NONE && ((m >> (PSUM_BQQ + psum_bit(child_hash(wq2)))) & 1u);
+}
+
+// the hint of a live child slot (its summary sum_lo, sum_hi): never 0
+TM_HD uint32_t hint_bit(uint32_t h) { return psum_bit(h) >> 2; }   // 0..6
+TM_HD uint32_t hint_of_sum(uint32_t lo, uint32_t hi) {
+    const uint64_t m = (uint64_t)hi << 32 | lo;
+    uint32_t v = HINT_CHILD | ((m & PSUM_HASH) ? HINT_HASH : 0) | ((m & PSUM_EXACT) ? HINT_EXACT : 0) |
+                 ((m & PSUM_HDESC) ? HINT_HDESC : 0) | ((m & PSUM_PLUS) ? HINT_PLUS : 0);
+    for (uint32_t j = 0; j < HINT_BLOOM; j++) v |= ((m >> (PSUM_BQ + 4 * j)) & 15u) ? 1u << j : 0u;
+    return v;
+}
+// child_alive's conservative shadow on a hint h != 0: false only where
+// child_alive is false for every summary the hint can stand for (the hint
+// knows nothing about Q's '+' child, so a '+' child keeps Q alive)
+TM_HD bool hint_alive(uint32_t h, uint32_t lq, uint32_t L, uint32_t wq) {
+    if (lq == L) return (h & (HINT_HASH | HINT_EXACT | HINT_HDESC)) != 0;
+    if (h & (HINT_HASH | HINT_PLUS)) return true;
+    return wq != NONE && ((h >> hint_bit(child_hash(wq))) & 1u);
+}
 
 // exact-table fingerprint of a wid-sequence hash (never 0: 0 marks an empty slot)
 TM_HD uint16_t exact_fp(uint64_t h) { return (uint16_t)((h >> 48) | 1u); }

@@ -653,7 +653,11 @@ int tm_profile_read(tm_index *h, double *walk_ms, double *batch_ms, uint64_t *ba
  * fan-out pass (tm_fanout_dev), each owning an equal chunk of the entries.
  * TM_DEBUG_ROUTE_ONE / TM_DEBUG_ROUTE_GRID (get only): tm_route_batch32 calls
  * whose fan-out the one-launch kernel completed / that the grid kernels or the
- * staged path finished. */
+ * staged path finished.  TM_DEBUG_ANNEX0 / TM_DEBUG_ANNEX1 (get only): the trie
+ * node annexed to that vocab-hint slot as depth << 32 | literal children, or
+ * all ones while the slot is unused; TM_DEBUG_HINT_AUDIT (get only): vocab
+ * entries whose hint of an annexed node differs from what that node's child
+ * slot gives, in the host image (always 0). */
 enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES = 3, TM_DEBUG_PHASES = 4,
        TM_DEBUG_FAILED_BATCHES = 5, TM_DEBUG_RETRIED_BATCHES = 6, TM_DEBUG_PATH_PHASES = 7,
        TM_DEBUG_PATH_SMALL = 8, TM_DEBUG_PATH_LANE = 9, TM_DEBUG_SMALL_KERNEL = 10,
@@ -661,7 +665,8 @@ enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES =
        TM_DEBUG_WIDE_NODES = 15, TM_DEBUG_DENSE_WIDE = 16, TM_DEBUG_CMB_GATHER = 17, TM_DEBUG_CMB_LAND = 18,
        TM_DEBUG_COMMITS = 19, TM_DEBUG_COMMIT_WAITS = 20, TM_DEBUG_COMMIT_FORCED = 21, TM_DEBUG_SMALL_TICKET = 22,
        TM_DEBUG_CMB_SPIN = 23, TM_DEBUG_PATCH_ZC = 24, TM_DEBUG_FANOUT_GRID = 25,
-       TM_DEBUG_ROUTE_ONE = 26, TM_DEBUG_ROUTE_GRID = 27 };
+       TM_DEBUG_ROUTE_ONE = 26, TM_DEBUG_ROUTE_GRID = 27, TM_DEBUG_ANNEX0 = 28, TM_DEBUG_ANNEX1 = 29,
+       TM_DEBUG_HINT_AUDIT = 30 };
 int tm_debug_set(tm_index *h, uint32_t key, uint64_t value);
 int tm_debug_get(tm_index *h, uint32_t key, uint64_t *value);
 
