@@ -67,7 +67,7 @@ __host__ __device__ constexpr uint32_t lb_state(uint64_t w) { return (uint32_t)(
 // publication (e.g. a predecessor's waves preempted for long) from leaving a
 // spinning grid behind: past it the block and every later one flag their
 // topics err 4 and raise the workspace's fail word, and the host API runs the
-// batch again (tm_host.cpp retry_or_fail).
+// batch again (tm_host.cpp HostBatch::run).
 constexpr uint32_t LB_SPINS = 1u << 22;   // polls of one predecessor word (LB_SLEEP apart: >= 0.1 s)
 constexpr uint32_t LB_SLEEP = 1;          // s_sleep between polls of a word not yet published (x 64 clocks)
 constexpr uint32_t LB_STRIDE = 1;         // 8-B words between consecutive blocks' look-back words

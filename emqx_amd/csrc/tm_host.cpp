@@ -1844,24 +1844,6 @@ int host_lane(tm_index *ix, std::unique_lock<std::mutex> &g, Lane *&out) {
     }
 }
 
-// releases a checked-out host lane on every exit path (retaking the lock if
-// the caller dropped it to wait for the GPU).  Round 6 measured releasing it
-// without the lock (an atomic flag, waiters announced): the leader's 55-85 us
-// wait for the lock after its GPU wait went, and 16 concurrent callers lost
-// 10-15 % (4.0-4.1 vs 4.8-4.9e8 topics/s, profiles/r6/lane_release/) -- the
-// lock paces the leaders; kept.
-struct LaneLease {
-    tm_index *ix;
-    std::unique_lock<std::mutex> &g;
-    Lane *ln = nullptr;
-    ~LaneLease() {
-        if (!ln) return;
-        if (!g.owns_lock()) g.lock();
-        ln->busy = false;
-        ix->cv.notify_one();
-    }
-};
-
 // the group of the calling thread's current HIP device (the first entry of
 // the device list on it)
 int dev_group(tm_index *ix, int &g) {
@@ -2013,6 +1995,135 @@ int drain_lanes(tm_index *ix) {
     return TM_OK;
 }
 
+// the lane a fan-out on stream s uses: the one the stream's match batches use, if any
+int fanout_lane(tm_index *ix, hipStream_t s, int grp, Lane *&ln) {
+    for (auto &l : ix->lanes)
+        if (!l->owned && l->s == s && ix->rep[l->r].group == grp) { ln = l.get(); ln->tick = ++ix->tick; return TM_OK; }
+    int r = 0;
+    while (ix->rep[r].group != grp) r++;
+    return dev_lane(ix, s, r, ln);
+}
+
+// TM_HOST_TIMING=1 (diagnostics): host timings on stderr, per tm_match_batch and summed by tm_destroy
+static const bool g_cmb_timing = getenv("TM_HOST_TIMING") != nullptr;
+static inline uint64_t ns_now() {
+    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
+        std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// A device-API call: it holds the index lock throughout (nothing waits for
+// the GPU) and queues on the caller's stream, on the group of the calling
+// thread's device.  An entry point checks its arguments, opens one of the two
+// kinds, queues its kernels on `s` and returns done().
+struct DevBatch {
+    tm_index *ix;
+    std::lock_guard<std::mutex> g;
+    hipStream_t s;
+    int grp = 0;
+    Lane *ln = nullptr;
+    DevIndex d;   // (open_match) the copy's view
+    tm_index::ProfEv ev{nullptr, nullptr, nullptr, nullptr, 0};
+    DevBatch(tm_index *ix, void *stream) : ix(ix), g(ix->mu), s(pick_stream(ix, stream)) {}
+    // a match batch of n topics: pending deltas collected, the copy picked and
+    // counted, its lane on `s` brought up to date with a workspace for n
+    int open_match(uint64_t n) {
+        int rc;
+        if ((rc = dev_group(ix, grp))) return rc;
+        if ((rc = collect_patch(ix))) return rc;
+        const int r = pick_copy(ix, grp, nullptr, s, true);
+        ix->rep[r].last_use = ++ix->tick;
+        ix->rep[r].batches++;
+        if ((rc = dev_lane(ix, s, r, ln))) return rc;
+        if ((rc = sync_locked(ix, ln->r, s))) return rc;
+        if ((rc = ensure_ws(ix, n, *ln))) return rc;
+        d = dev_view(ix, ln->r);
+        return prof_begin(ix, ev, s);
+    }
+    // a fan-out or aggre pass over the caller's device arrays: only the lane (its scratch)
+    int open_fanout() {
+        if (int rc = dev_group(ix, grp)) return rc;
+        return fanout_lane(ix, s, grp, ln);
+    }
+    int done() {
+        if (int rc = batch_done(ix, *ln)) return rc;
+        return prof_end(ix, ev, s);
+    }
+};
+
+// A host-API batch: the index lock, the lane checked out for the call, the
+// workspace it asked for and the call's retry count.  Host-API batches hold
+// the lock only to ship pending patches, pick up the index's current device
+// view and queue the kernels on their lane; they wait for the GPU and copy
+// results out without it, so concurrent callers overlap on the device (each
+// lane is its own stream) and deltas keep flowing.  An entry point checks its
+// arguments, open()s, and gives run() what it queues; relock() is the only way
+// back under the lock after run() dropped it (a retry, a scratch that grew).
+// The lane is released on every exit path, under the lock (retaken if need
+// be).  Round 6 measured releasing it without the lock (an atomic flag,
+// waiters announced): the leader's 55-85 us wait for the lock after its GPU
+// wait went, and 16 concurrent callers lost 10-15 % (4.0-4.1 vs 4.8-4.9e8
+// topics/s, profiles/r6/lane_release/) -- the lock paces the leaders; kept.
+struct HostBatch {
+    tm_index *ix;
+    std::unique_lock<std::mutex> g;
+    Lane *ln = nullptr;
+    uint64_t ws_topics = 0;
+    int tries = 0;
+    uint64_t t_queued = 0, t_synced = 0;   // (TM_HOST_TIMING) the last attempt: lock dropped, GPU wait over
+    explicit HostBatch(tm_index *ix) : ix(ix), g(ix->mu) {}
+    ~HostBatch() {
+        if (!ln) return;
+        if (!g.owns_lock()) g.lock();
+        ln->busy = false;
+        ix->cv.notify_one();
+    }
+    // a lane, up to date, with a workspace for ws topics (the batch is counted
+    // by the caller, once it is known to run here)
+    int open(uint64_t ws) {
+        int rc;
+        ws_topics = ws;
+        if ((rc = host_lane(ix, g, ln))) return rc;
+        if ((rc = sync_locked(ix, ln->r, ln->s))) return rc;
+        return ensure_ws(ix, ws_topics, *ln);
+    }
+    // ensure_ws too: while the lock was away another caller may have patched
+    // this copy on its own stream, and that is where the lane's stream waits
+    // for the copy's last patch
+    int relock() {
+        g.lock();
+        HIPCHK(ix, hipSetDevice(ix->rep[ln->r].device));
+        if (int rc = sync_locked(ix, ln->r, ln->s)) return rc;
+        return ensure_ws(ix, ws_topics, *ln);
+    }
+    // queue(view, tag) queues the batch on ln->s (and counts its path); then
+    // the lock is dropped for the GPU wait.  A failed one-launch batch (its
+    // look-back wait expired: err 4 flags, never a client error -- the
+    // reference raises badarg only for a '+'/'#' level,
+    // emqx_trie_search.erl:374-375) runs again, on the same lane with the
+    // current device view, once per call; the second failure is TM_EDEVICE
+    // for the whole call.
+    template <class Queue>
+    int run(Queue &&queue) {
+        for (;;) {
+            int rc;
+            uint32_t tag;
+            if ((rc = next_tag(ix, *ln, ln->s, tag))) return rc;
+            if ((rc = queue(dev_view(ix, ln->r), tag))) return rc;
+            if ((rc = batch_done(ix, *ln))) return rc;
+            g.unlock();
+            if (g_cmb_timing) t_queued = ns_now();
+            HIPCHK(ix, hipStreamSynchronize(ln->s));
+            if (g_cmb_timing) t_synced = ns_now();
+            if (!batch_failed(ix, *ln)) return TM_OK;
+            if (tries++ >= 1)
+                return fail(ix, TM_EDEVICE, "tm_match_batch: the batch failed on the device twice (look-back wait "
+                                            "expired, err 4); not matched");
+            ix->retried_batches++;
+            if ((rc = relock())) return rc;
+        }
+    }
+};
+
 }  // namespace
 
 // =================================================================== C ABI
@@ -2088,11 +2199,6 @@ struct CommitTiming {
     std::atomic<uint64_t> n{0}, apply_ns{0}, lock_ns{0}, collect_ns{0}, idle_ns{0}, ship_ns{0};
 };
 static CommitTiming g_cmt;
-static const bool g_cmb_timing = getenv("TM_HOST_TIMING") != nullptr;
-static inline uint64_t ns_now() {
-    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
-        std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 int tm_destroy(tm_index *ix) {
     if (!ix) return TM_EINVAL;
@@ -2349,32 +2455,19 @@ int tm_match_batch_dev_ex(tm_index *ix, uint64_t n, const uint8_t *bytes, const 
     if (!hit_offs || (n && (!offs || !bytes || !err))) return fail(ix, TM_EINVAL, "tm_match_batch_dev: null buffer");
     if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_match_batch_dev: batch too large");
     if (order > TM_ORDER_UNIQUE) return fail(ix, TM_EINVAL, "tm_match_batch_dev: bad order");
-    std::lock_guard<std::mutex> g(ix->mu);
-    hipStream_t s = pick_stream(ix, stream);
-    int rc, grp = 0;
-    Lane *ln;
-    if ((rc = dev_group(ix, grp))) return rc;
-    if ((rc = collect_patch(ix))) return rc;
-    const int r = pick_copy(ix, grp, nullptr, s, true);
-    ix->rep[r].last_use = ++ix->tick;
-    ix->rep[r].batches++;
-    if ((rc = dev_lane(ix, s, r, ln))) return rc;
-    if ((rc = sync_locked(ix, ln->r, s))) return rc;
-    if ((rc = ensure_ws(ix, n, *ln))) return rc;
-    const DevIndex d = dev_view(ix, ln->r);
-    tm_index::ProfEv ev;
-    if ((rc = prof_begin(ix, ev, s))) return rc;
+    DevBatch b(ix, stream);
+    int rc;
+    if ((rc = b.open_match(n))) return rc;
     uint32_t tag;
-    if ((rc = next_tag(ix, *ln, s, tag))) return rc;
+    if ((rc = next_tag(ix, *b.ln, b.s, tag))) return rc;
     // (asynchronous: a failed look-back reaches the caller as err 4 flags, include/tmatch.h)
     int path = PATH_PHASES;
-    HIPCHK(ix, launch_match(d, ln->w, n, bytes, offs, hit_offs, err, out, out ? cap : 0, tag, next_lb(ix),
-                            ix->dbg_phases, ix->small_kind, s, ev.w0, ev.w1, &path));
+    HIPCHK(ix, launch_match(b.d, b.ln->w, n, bytes, offs, hit_offs, err, out, out ? cap : 0, tag, next_lb(ix),
+                            ix->dbg_phases, ix->small_kind, b.s, b.ev.w0, b.ev.w1, &path));
     ix->path_batches[path]++;
     if (order != TM_ORDER_TRAVERSAL && out)
-        HIPCHK(ix, launch_sort_segments(ln->w, n, hit_offs, out, cap, order == TM_ORDER_UNIQUE, ucnt, s));
-    if ((rc = batch_done(ix, *ln))) return rc;
-    return prof_end(ix, ev, s);
+        HIPCHK(ix, launch_sort_segments(b.ln->w, n, hit_offs, out, cap, order == TM_ORDER_UNIQUE, ucnt, b.s));
+    return b.done();
 }
 
 int tm_match_batch_dev_pairs(tm_index *ix, uint64_t n, const uint8_t *bytes, const uint64_t *offs, uint32_t *pairs,
@@ -2385,25 +2478,11 @@ int tm_match_batch_dev_pairs(tm_index *ix, uint64_t n, const uint8_t *bytes, con
     if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_match_batch_dev_pairs: batch too large");
     if (!out) cap = 0;
     if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
-    std::lock_guard<std::mutex> g(ix->mu);
-    hipStream_t s = pick_stream(ix, stream);
-    int rc, grp = 0;
-    Lane *ln;
-    if ((rc = dev_group(ix, grp))) return rc;
-    if ((rc = collect_patch(ix))) return rc;
-    const int r = pick_copy(ix, grp, nullptr, s, true);
-    ix->rep[r].last_use = ++ix->tick;
-    ix->rep[r].batches++;
-    if ((rc = dev_lane(ix, s, r, ln))) return rc;
-    if ((rc = sync_locked(ix, ln->r, s))) return rc;
-    if ((rc = ensure_ws(ix, n, *ln))) return rc;
-    const DevIndex d = dev_view(ix, ln->r);
-    tm_index::ProfEv ev;
-    if ((rc = prof_begin(ix, ev, s))) return rc;
-    HIPCHK(ix, launch_match_pairs(d, ln->w, n, bytes, offs, err, pairs, out, cap, s, ev.w0, ev.w1));
+    DevBatch b(ix, stream);
+    if (int rc = b.open_match(n)) return rc;
+    HIPCHK(ix, launch_match_pairs(b.d, b.ln->w, n, bytes, offs, err, pairs, out, cap, b.s, b.ev.w0, b.ev.w1));
     ix->path_batches[PATH_PHASES]++;
-    if ((rc = batch_done(ix, *ln))) return rc;
-    return prof_end(ix, ev, s);
+    return b.done();
 }
 
 int tm_match_batch_dev(tm_index *ix, uint64_t n, const uint8_t *bytes, const uint64_t *offs, uint64_t *hit_offs,
@@ -2481,15 +2560,6 @@ int ensure_fanout(tm_index *ix, Lane &ln, uint32_t n_dests, uint64_t cap, bool p
         return fail(ix, TM_ENOMEM, "fan-out: no device memory for a two-pass pairs batch's scratch (16 bytes x cap)");
     }
     return TM_OK;
-}
-
-// the lane a fan-out on stream s uses: the one the stream's match batches use, if any
-int fanout_lane(tm_index *ix, hipStream_t s, int grp, Lane *&ln) {
-    for (auto &l : ix->lanes)
-        if (!l->owned && l->s == s && ix->rep[l->r].group == grp) { ln = l.get(); ln->tick = ++ix->tick; return TM_OK; }
-    int r = 0;
-    while (ix->rep[r].group != grp) r++;
-    return dev_lane(ix, s, r, ln);
 }
 
 // The index's own value -> destination table on group g, current as of now,
@@ -2649,17 +2719,14 @@ int tm_aggre_dev(tm_index *ix, uint32_t n_dests, const uint64_t *dest_offs, cons
     if (!dest_offs || !out_dest_offs || (cap && (!topic || !value || !out_topic || !out_value)))
         return fail(ix, TM_EINVAL, "tm_aggre_dev: null buffer");
     if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
-    std::lock_guard<std::mutex> g(ix->mu);
-    hipStream_t s = pick_stream(ix, stream);
-    Lane *ln = nullptr;
-    int rc, grp = 0;
-    if ((rc = dev_group(ix, grp))) return rc;
-    if ((rc = fanout_lane(ix, s, grp, ln))) return rc;
-    if ((rc = ensure_aggre(ix, *ln, cap))) return rc;
-    if (!filter_of && (rc = filter_upload(ix, grp, s, filter_of, filter_len))) return rc;
-    HIPCHK(ix, launch_aggre(ln->f, n_dests, dest_offs, topic, value, cap, filter_of, filter_len, out_dest_offs, out_topic,
-                            out_value, s));
-    return batch_done(ix, *ln);
+    DevBatch b(ix, stream);
+    int rc;
+    if ((rc = b.open_fanout())) return rc;
+    if ((rc = ensure_aggre(ix, *b.ln, cap))) return rc;
+    if (!filter_of && (rc = filter_upload(ix, b.grp, b.s, filter_of, filter_len))) return rc;
+    HIPCHK(ix, launch_aggre(b.ln->f, n_dests, dest_offs, topic, value, cap, filter_of, filter_len, out_dest_offs,
+                            out_topic, out_value, b.s));
+    return b.done();
 }
 
 int tm_fanout_dev(tm_index *ix, uint64_t n, const uint64_t *hit_offs, const uint32_t *vals, uint64_t cap,
@@ -2671,16 +2738,14 @@ int tm_fanout_dev(tm_index *ix, uint64_t n, const uint64_t *hit_offs, const uint
         return fail(ix, TM_EINVAL, "tm_fanout_dev: null buffer");
     if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_fanout_dev: too many topics");
     if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
-    std::lock_guard<std::mutex> g(ix->mu);
-    hipStream_t s = pick_stream(ix, stream);
-    Lane *ln = nullptr;
-    int rc, grp = 0;
-    if ((rc = dev_group(ix, grp))) return rc;
-    if ((rc = fanout_lane(ix, s, grp, ln))) return rc;
-    if ((rc = ensure_fanout(ix, *ln, n_dests, cap))) return rc;
-    if (!dest_of && (rc = dest_upload(ix, grp, s, dest_of, dest_len))) return rc;
-    HIPCHK(ix, launch_fanout(ln->f, n, hit_offs, vals, cap, dest_of, dest_len, n_dests, dest_offs, out_topic, out_value, s));
-    return batch_done(ix, *ln);
+    DevBatch b(ix, stream);
+    int rc;
+    if ((rc = b.open_fanout())) return rc;
+    if ((rc = ensure_fanout(ix, *b.ln, n_dests, cap))) return rc;
+    if (!dest_of && (rc = dest_upload(ix, b.grp, b.s, dest_of, dest_len))) return rc;
+    HIPCHK(ix, launch_fanout(b.ln->f, n, hit_offs, vals, cap, dest_of, dest_len, n_dests, dest_offs, out_topic, out_value,
+                             b.s));
+    return b.done();
 }
 
 int tm_fanout_dev_pairs(tm_index *ix, uint64_t n, const uint32_t *pairs, const uint32_t *vals, uint64_t cap,
@@ -2693,16 +2758,14 @@ int tm_fanout_dev_pairs(tm_index *ix, uint64_t n, const uint32_t *pairs, const u
     if ((uintptr_t)pairs & 7) return fail(ix, TM_EINVAL, "tm_fanout_dev_pairs: d_pairs must be 8-byte aligned");
     if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_fanout_dev_pairs: too many topics");
     if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
-    std::lock_guard<std::mutex> g(ix->mu);
-    hipStream_t s = pick_stream(ix, stream);
-    Lane *ln = nullptr;
-    int rc, grp = 0;
-    if ((rc = dev_group(ix, grp))) return rc;
-    if ((rc = fanout_lane(ix, s, grp, ln))) return rc;
-    if ((rc = ensure_fanout(ix, *ln, n_dests, cap, true, n))) return rc;
-    if (!dest_of && (rc = dest_upload(ix, grp, s, dest_of, dest_len))) return rc;
-    HIPCHK(ix, launch_fanout_pairs(ln->f, n, pairs, vals, cap, dest_of, dest_len, n_dests, dest_offs, out_topic, out_value, s));
-    return batch_done(ix, *ln);
+    DevBatch b(ix, stream);
+    int rc;
+    if ((rc = b.open_fanout())) return rc;
+    if ((rc = ensure_fanout(ix, *b.ln, n_dests, cap, true, n))) return rc;
+    if (!dest_of && (rc = dest_upload(ix, b.grp, b.s, dest_of, dest_len))) return rc;
+    HIPCHK(ix, launch_fanout_pairs(b.ln->f, n, pairs, vals, cap, dest_of, dest_len, n_dests, dest_offs, out_topic,
+                                   out_value, b.s));
+    return b.done();
 }
 
 int tm_stream_release(tm_index *ix, void *stream) {
@@ -2898,26 +2961,16 @@ int tm_host_free(tm_index *ix, void *p) {
     return fail(ix, TM_EINVAL, "tm_host_free: not a tm_host_alloc buffer of this index");
 }
 
-// TM_HOST_TIMING=1: per-phase host timings of tm_match_batch on stderr (diagnostics)
-static double now_us() {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
+// an optional caller buffer of an in-place batch: its device address, or null
+// when it is absent or empty; one that is present must lie in a tm_host_alloc
+// buffer, else `ok` is cleared (the batch is staged)
+static uint8_t *opt_dev(tm_index *ix, const void *p, uint64_t bytes, bool &ok) {
+    if (!p || !bytes) return nullptr;
+    uint8_t *d = pinned_dev(ix, p, bytes);
+    if (!d) ok = false;
+    return d;
 }
 
-// After a failed one-launch batch (its look-back wait expired: err 4 flags,
-// never a client error -- the reference raises badarg only for a '+'/'#'
-// level, emqx_trie_search.erl:374-375): the first failure runs the batch
-// again, on the same lane with the current device view; the second returns
-// TM_EDEVICE for the whole call.  Retakes the index lock (released for the
-// GPU wait).
-static int retry_or_fail(tm_index *ix, std::unique_lock<std::mutex> &g, Lane &ln, int tries) {
-    if (tries >= 1)
-        return fail(ix, TM_EDEVICE, "tm_match_batch: the batch failed on the device twice (look-back wait expired, "
-                                    "err 4); not matched");
-    ix->retried_batches++;
-    g.lock();
-    HIPCHK(ix, hipSetDevice(ix->rep[ln.r].device));
-    return sync_locked(ix, ln.r, ln.s);
-}
 
 // ---- the host-batch combiner (32-bit in-place batches, the NIF's calls)
 //
@@ -2956,15 +3009,11 @@ static int run_small_group(tm_index *ix, const std::vector<SmallReq *> &grp, uin
     uint64_t total = 0;
     for (auto *r : grp) total += r->n;
     const uint64_t ta = g_cmb_timing ? ns_now() : 0;
-    std::unique_lock<std::mutex> g(ix->mu);
+    HostBatch hb(ix);
     const uint64_t tb = g_cmb_timing ? ns_now() : 0;
-    LaneLease lease{ix, g};
     int rc;
-    if ((rc = host_lane(ix, g, lease.ln))) return rc;
-    Lane &ln = *lease.ln;
-    const hipStream_t s = ln.s;
-    if ((rc = sync_locked(ix, ln.r, s))) return rc;
-    if ((rc = ensure_ws(ix, total + (uint64_t)SMALL_SEGS * SM_TOPICS, ln))) return rc;
+    if ((rc = hb.open(total + (uint64_t)SMALL_SEGS * SM_TOPICS))) return rc;
+    Lane &ln = *hb.ln;
     if (!small_path_ok(dev_view(ix, ln.r), total)) return CMB_LEGACY;
     ix->rep[ln.r].batches++;
     SmallSegs sg{};
@@ -2977,29 +3026,21 @@ static int run_small_group(tm_index *ix, const std::vector<SmallReq *> &grp, uin
                            (uint32_t)r.n, 0};
     }
     const uint64_t tc = g_cmb_timing ? ns_now() : 0;
-    for (int tries = 0;; tries++) {
-        const DevIndex d = dev_view(ix, ln.r);
-        uint32_t tag;
-        if ((rc = next_tag(ix, ln, s, tag))) return rc;
+    rc = hb.run([&](const DevIndex &d, uint32_t tag) -> int {
         int path = PATH_SMALL;
-        HIPCHK(ix, launch_small_segs(d, ln.w, sg, true, tag, next_lb(ix), ix->small_kind, s, &path));
+        HIPCHK(ix, launch_small_segs(d, ln.w, sg, true, tag, next_lb(ix), ix->small_kind, ln.s, &path));
         ix->path_batches[path]++;
         ix->cmb_launches++;
         ix->cmb_batches += grp.size();
-        if ((rc = batch_done(ix, ln))) return rc;
-        g.unlock();
-        const uint64_t td = g_cmb_timing ? ns_now() : 0;
-        HIPCHK(ix, hipStreamSynchronize(s));
-        if (g_cmb_timing) {
-            const uint64_t te = ns_now();
-            g_cmbt.groups++;
-            g_cmbt.lock_ns += tb - ta; g_cmbt.setup_ns += tc - tb; g_cmbt.launch_ns += td - tc; g_cmbt.sync_ns += te - td;
-            *t_sync_end = te;
-        }
-        if (!batch_failed(ix, ln)) break;
-        if ((rc = retry_or_fail(ix, g, ln, tries))) return rc;
+        return TM_OK;
+    });
+    if (g_cmb_timing && hb.t_synced) {   // (the last attempt's launch and wait)
+        g_cmbt.groups++;
+        g_cmbt.lock_ns += tb - ta; g_cmbt.setup_ns += tc - tb;
+        g_cmbt.launch_ns += hb.t_queued - tc; g_cmbt.sync_ns += hb.t_synced - hb.t_queued;
+        *t_sync_end = hb.t_synced;
     }
-    return TM_OK;
+    return rc;
 }
 
 // (caller holds cmb_mu) queued + in flight, against the recent high-water mark
@@ -3083,44 +3124,38 @@ static int small_combined(tm_index *ix, SmallReq &rq) {
     return rq.rc;
 }
 
-// Host-API batches hold the index lock only to ship pending patches, pick up
-// the index's current device view and queue the kernels on the caller's lane;
-// they wait for the GPU and copy results out without it, so concurrent callers
-// overlap on the device (each lane is its own stream) and deltas keep flowing.
 // tm_match_batch_ex, or (to32v) the same over u32 offsets that lie in
 // TM_ALLOC_VRAM memory with their bytes (tm_match_batch32_ex's batches the
 // one-launch path does not take): widened on the device, never read by the host
+// TM_HOST_TIMING=1: its per-phase host timings on stderr (diagnostics)
 static int match_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, const uint32_t *to32v,
                             uint64_t *out_hit, uint32_t *out_vals, uint64_t cap, uint8_t *out_err, uint32_t order,
                             uint32_t *out_unique) {
-    static const bool timing = getenv("TM_HOST_TIMING") != nullptr;
-    double tt[8]; int nt = 0;
-    if (timing) tt[nt++] = now_us();
+    const bool timing = g_cmb_timing;
+    const uint64_t t0 = timing ? ns_now() : 0;
     if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_match_batch: batch too large");
     if (order > TM_ORDER_UNIQUE) return fail(ix, TM_EINVAL, "tm_match_batch: bad order");
     const bool sorted = order != TM_ORDER_TRAVERSAL, unique = order == TM_ORDER_UNIQUE;
-    std::unique_lock<std::mutex> g(ix->mu);
-    LaneLease lease{ix, g};
+    HostBatch hb(ix);
     int rc;
-    if ((rc = host_lane(ix, g, lease.ln))) return rc;
-    Lane &ln = *lease.ln;
+    if ((rc = hb.open(n))) return rc;
+    Lane &ln = *hb.ln;
     const hipStream_t s = ln.s;
-    if ((rc = sync_locked(ix, ln.r, s))) return rc;
-    if ((rc = ensure_ws(ix, n, ln))) return rc;
     ix->rep[ln.r].batches++;
-    if (timing) tt[nt++] = now_us();
+    const uint64_t t1 = timing ? ns_now() : 0;
     if (n && n <= ZC_TOPICS && !to32v) {
         // every buffer from tm_host_alloc: the kernels read the topics and
         // write the hit lists in place (no staging copy in, no copy out)
         const uint64_t nbytes = to[n];
-        uint8_t *db = nbytes ? pinned_dev(ix, tb, nbytes) : nullptr;
-        uint8_t *dof = pinned_dev(ix, to, (n + 1) * 8);
-        uint8_t *dh = pinned_dev(ix, out_hit, (n + 1) * 8);
-        uint8_t *dv = out_vals ? pinned_dev(ix, out_vals, cap * 4) : nullptr;
-        uint8_t *de = out_err ? pinned_dev(ix, out_err, n) : nullptr;
-        uint8_t *du = out_unique ? pinned_dev(ix, out_unique, n * 4) : nullptr;
+        bool ok = tb || !nbytes;
+        uint8_t *db = opt_dev(ix, tb, nbytes, ok);
+        uint8_t *dof = opt_dev(ix, to, (n + 1) * 8, ok);
+        uint8_t *dh = opt_dev(ix, out_hit, (n + 1) * 8, ok);
+        uint8_t *dv = opt_dev(ix, out_vals, cap * 4, ok);
+        uint8_t *de = opt_dev(ix, out_err, n, ok);
+        uint8_t *du = opt_dev(ix, out_unique, n * 4, ok);
         const bool aligned = ((uintptr_t)tb & 15) == 0;
-        if ((db || !nbytes) && aligned && dof && dh && (dv || !out_vals) && (de || !out_err) && (du || !out_unique)) {
+        if (ok && aligned) {
             if (!de) {   // flags nobody reads still need a home
                 if ((rc = stage_out(ix, ln, n, n, de))) return rc;
             }
@@ -3131,10 +3166,7 @@ static int match_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const u
                 if ((rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, cap))) return rc;
                 vdst = ln.d_vals;
             }
-            for (int tries = 0;; tries++) {
-                const DevIndex d = dev_view(ix, ln.r);
-                uint32_t tag;
-                if (int rc = next_tag(ix, ln, s, tag)) return rc;
+            rc = hb.run([&](const DevIndex &d, uint32_t tag) -> int {
                 int path = PATH_PHASES;
                 HIPCHK(ix, launch_match(d, ln.w, n, dbytes, reinterpret_cast<const uint64_t *>(dof), dhit, de, vdst,
                                         dv ? cap : 0, tag, next_lb(ix), ix->dbg_phases, ix->small_kind, s, nullptr,
@@ -3144,26 +3176,19 @@ static int match_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const u
                     HIPCHK(ix, launch_sort_segments(ln.w, n, dhit, vdst, cap, unique, reinterpret_cast<uint32_t *>(du), s));
                     HIPCHK(ix, launch_copy_values(dhit, n, vdst, reinterpret_cast<uint32_t *>(dv), cap, s));
                 }
-                if ((rc = batch_done(ix, ln))) return rc;
-                g.unlock();
-                if (timing) tt[nt++] = now_us();
-                HIPCHK(ix, hipStreamSynchronize(s));
-                if (!batch_failed(ix, ln)) break;
-                if ((rc = retry_or_fail(ix, g, ln, tries))) return rc;
-                if (timing) nt = 1;
-            }
-            if (timing) {
-                tt[nt++] = now_us();
+                return TM_OK;
+            });
+            if (rc) return rc;
+            if (timing)
                 fprintf(stderr, "tm_match_batch n=%lu (in place): sync %.1f launch %.1f wait %.1f us\n",
-                        (unsigned long)n, tt[1] - tt[0], tt[2] - tt[1], tt[3] - tt[2]);
-            }
+                        (unsigned long)n, (t1 - t0) * 1e-3, (hb.t_queued - t1) * 1e-3, (hb.t_synced - hb.t_queued) * 1e-3);
             return (out_vals && out_hit[n] > cap) ? TM_ECAP : TM_OK;
         }
     }
     const uint8_t *dbytes;
     const uint64_t *doffs;
     if ((rc = stage_in(ix, ln, n, tb, to, to32v, dbytes, doffs))) return rc;
-    if (timing) tt[nt++] = now_us();
+    const uint64_t t2 = timing ? ns_now() : 0;
     // results: hit offsets (n + 1) x u64, then the badarg flags (then the
     // distinct counts, u32, for UNIQUE); the values are written by k_emit
     // straight into mapped pinned memory (sorted orders: sorted in HBM, then
@@ -3177,59 +3202,44 @@ static int match_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     uint8_t *derr = dres + (n + 1) * 8;
     uint32_t *dunq = (sorted && out_unique) ? reinterpret_cast<uint32_t *>(dres + uoff) : nullptr;
     uint64_t total = 0;
-    for (int attempt = 0, tries = 0; attempt < 3; attempt++) {
+    for (int attempt = 0;; attempt++) {
         if (!ln.pin_vals) {
             ln.pin_vals_cap = std::max<uint64_t>(ln.pin_vals_cap, 1 << 16);
             HIPCHK(ix, hipHostMalloc(&ln.pin_vals, ln.pin_vals_cap * 4, hipHostMallocMapped));
             HIPCHK(ix, hipHostGetDevicePointer(reinterpret_cast<void **>(&ln.pin_vals_dev), ln.pin_vals, 0));
         }
-        uint32_t *vdst = ln.pin_vals_dev;
         if (sorted && (rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, ln.pin_vals_cap))) return rc;
-        if (sorted) vdst = ln.d_vals;
-        const DevIndex d = dev_view(ix, ln.r);
-        uint32_t tag;
-        if (int rc = next_tag(ix, ln, s, tag)) return rc;
-        int path = PATH_PHASES;
-        HIPCHK(ix, launch_match(d, ln.w, n, dbytes, doffs, dhit, derr, vdst, ln.pin_vals_cap, tag, next_lb(ix),
-                                ix->dbg_phases, ix->small_kind, s, nullptr, nullptr, &path));
-        ix->path_batches[path]++;
-        if (sorted) {
-            HIPCHK(ix, launch_sort_segments(ln.w, n, dhit, vdst, ln.pin_vals_cap, unique, dunq, s));
-            HIPCHK(ix, launch_copy_values(dhit, n, vdst, ln.pin_vals_dev, ln.pin_vals_cap, s));
-        }
-        if ((rc = fetch_out(ix, ln, n, rbytes))) return rc;
-        if ((rc = batch_done(ix, ln))) return rc;
-        g.unlock();
-        if (timing && nt < 5) tt[nt++] = now_us();
-        HIPCHK(ix, hipStreamSynchronize(s));
-        if (timing && nt < 6) tt[nt++] = now_us();
-        if (batch_failed(ix, ln)) {   // the look-back failed: run the batch again, once
-            if ((rc = retry_or_fail(ix, g, ln, tries++))) return rc;
-            attempt--;
-            continue;
-        }
+        uint32_t *vdst = sorted ? ln.d_vals : ln.pin_vals_dev;
+        rc = hb.run([&](const DevIndex &d, uint32_t tag) -> int {
+            int path = PATH_PHASES;
+            HIPCHK(ix, launch_match(d, ln.w, n, dbytes, doffs, dhit, derr, vdst, ln.pin_vals_cap, tag, next_lb(ix),
+                                    ix->dbg_phases, ix->small_kind, s, nullptr, nullptr, &path));
+            ix->path_batches[path]++;
+            if (sorted) {
+                HIPCHK(ix, launch_sort_segments(ln.w, n, dhit, vdst, ln.pin_vals_cap, unique, dunq, s));
+                HIPCHK(ix, launch_copy_values(dhit, n, vdst, ln.pin_vals_dev, ln.pin_vals_cap, s));
+            }
+            return fetch_out(ix, ln, n, rbytes);
+        });
+        if (rc) return rc;
         memcpy(&total, ln.pin_out + n * 8, 8);
-        if (total <= ln.pin_vals_cap || !out_vals || total <= 0) break;
+        if (total <= ln.pin_vals_cap || !out_vals) break;
         if (attempt == 2) return fail(ix, TM_EDEVICE, "tm_match_batch: hit total kept growing past the staging buffer");
         // grow the mapped buffer and run the batch again (rare: sizes are sticky)
-        g.lock();
+        if ((rc = hb.relock())) return rc;
         HIPCHK(ix, hipHostFree(ln.pin_vals));
         ln.pin_vals = nullptr;
         ln.pin_vals_cap = total + total / 4;
-        HIPCHK(ix, hipSetDevice(ix->rep[ln.r].device));
-        if ((rc = sync_locked(ix, ln.r, s))) return rc;
-        if ((rc = ensure_ws(ix, n, ln))) return rc;
     }
     memcpy(out_hit, ln.pin_out, (n + 1) * 8);
     if (out_err && n) memcpy(out_err, ln.pin_out + (n + 1) * 8, n);
     if (dunq && n) memcpy(out_unique, ln.pin_out + uoff, 4 * n);
     const uint64_t keep = std::min(total, out_vals ? cap : 0);
     if (keep) memcpy(out_vals, ln.pin_vals, keep * 4);
-    if (timing) {
-        tt[nt++] = now_us();
+    if (timing)
         fprintf(stderr, "tm_match_batch n=%lu: sync %.1f stage %.1f launch %.1f wait %.1f copy-out %.1f us\n",
-                (unsigned long)n, tt[1] - tt[0], tt[2] - tt[1], tt[3] - tt[2], tt[4] - tt[3], tt[nt - 1] - tt[4]);
-    }
+                (unsigned long)n, (t1 - t0) * 1e-3, (t2 - t1) * 1e-3, (hb.t_queued - t2) * 1e-3,
+                (hb.t_synced - hb.t_queued) * 1e-3, (ns_now() - hb.t_synced) * 1e-3);
     return (out_vals && total > cap) ? TM_ECAP : TM_OK;
 }
 
@@ -3245,13 +3255,85 @@ int tm_match_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *
     return tm_match_batch_ex(ix, n, tb, to, out_hit, out_vals, cap, out_err, TM_ORDER_TRAVERSAL, nullptr);
 }
 
+// ---- the route fan-out on a host lane's scratch (tm_route_batch, and the
+// batches of tm_route_batch32 that k_fo_one does not take)
+
+// room for vcap entries over n_dests destinations: the fan-out's arrays and
+// passes (pairs: from the n topics' spans), and under aggre the kept ones
+static int route_scratch(tm_index *ix, Lane &ln, uint32_t n_dests, uint64_t vcap, bool aggre, bool pairs, uint64_t n) {
+    int rc;
+    const hipStream_t s = ln.s;
+    if ((rc = grow_dev(ix, s, ln.d_ft, ln.d_ft_cap, vcap))) return rc;
+    if ((rc = grow_dev(ix, s, ln.d_fv, ln.d_fv_cap, vcap))) return rc;
+    if ((rc = grow_dev(ix, s, ln.d_fo, ln.d_fo_cap, (uint64_t)n_dests + 2))) return rc;
+    if ((rc = ensure_fanout(ix, ln, n_dests, vcap, pairs, n))) return rc;
+    if (!aggre) return TM_OK;
+    if ((rc = grow_dev(ix, s, ln.d_at, ln.d_at_cap, vcap))) return rc;
+    if ((rc = grow_dev(ix, s, ln.d_av, ln.d_av_cap, vcap))) return rc;
+    if ((rc = grow_dev(ix, s, ln.d_ao, ln.d_ao_cap, (uint64_t)n_dests + 2))) return rc;
+    return ensure_aggre(ix, ln, vcap);
+}
+
+// queues the grid fan-out of the lane's matched values (d_vals; their CSR
+// offsets `hit`, or with `pairs` their spans) into d_fo/d_ft/d_fv with the
+// index's own destination table, and with `aggre` the aggre pass over that
+// into d_ao/d_at/d_av (caller holds ix->mu)
+static int queue_grid_fanout(tm_index *ix, Lane &ln, uint64_t n, const uint64_t *hit, const uint32_t *pairs,
+                             uint64_t vcap, uint32_t n_dests, bool aggre) {
+    int rc;
+    const hipStream_t s = ln.s;
+    const int grp = ix->rep[ln.r].group;
+    const uint32_t *dtab = nullptr, *ftab = nullptr;
+    uint64_t dlen = 0, flen = 0;
+    if ((rc = dest_upload(ix, grp, s, dtab, dlen))) return rc;
+    uint32_t *ft = ln.d_ft, *fv = ln.d_fv;
+    if (pairs) HIPCHK(ix, launch_fanout_pairs(ln.f, n, pairs, ln.d_vals, vcap, dtab, dlen, n_dests, ln.d_fo, ft, fv, s));
+    else HIPCHK(ix, launch_fanout(ln.f, n, hit, ln.d_vals, vcap, dtab, dlen, n_dests, ln.d_fo, ft, fv, s));
+    if (!aggre) return TM_OK;
+    if ((rc = filter_upload(ix, grp, s, ftab, flen))) return rc;
+    HIPCHK(ix, launch_aggre(ln.f, n_dests, ln.d_fo, ln.d_ft, ln.d_fv, vcap, ftab, flen, ln.d_ao, ln.d_at, ln.d_av, s));
+    return TM_OK;
+}
+
+// The lane's fan-out results to the caller (the lock is not held; the lane is
+// still checked out: its buffers are this caller's).  `fo`: n_dests + 2 u64
+// the offsets land in -- the caller's own array, or narrowed into fo32.
+// aggre_ran: the aggre pass's offsets, then its kept entries (two waits: the
+// count comes with the offsets).  Otherwise the fan-out's offsets and the
+// first min(total, cap) entries -- none under aggre, which then had no room
+// (TM_ECAP: the un-aggregated sizes).
+static int copy_route_out(tm_index *ix, Lane &ln, uint32_t n_dests, uint64_t total, uint64_t cap, bool aggre,
+                          bool aggre_ran, uint64_t *fo, uint32_t *fo32, uint32_t *out_topic, uint32_t *out_values) {
+    const hipStream_t s = ln.s;
+    const uint64_t nfo = (uint64_t)n_dests + 2;
+    if (aggre_ran) {
+        HIPCHK(ix, hipMemcpyAsync(fo, ln.d_ao, nfo * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ix, hipStreamSynchronize(s));
+        const uint64_t kept = std::min(fo[n_dests + 1], cap);   // (K <= total <= cap)
+        if (kept) {
+            HIPCHK(ix, hipMemcpyAsync(out_topic, ln.d_at, kept * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipMemcpyAsync(out_values, ln.d_av, kept * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipStreamSynchronize(s));
+        }
+    } else {
+        const uint64_t keep = aggre ? 0 : std::min(total, cap);
+        HIPCHK(ix, hipMemcpyAsync(fo, ln.d_fo, nfo * 8, hipMemcpyDeviceToHost, s));
+        if (keep) {
+            HIPCHK(ix, hipMemcpyAsync(out_topic, ln.d_ft, keep * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipMemcpyAsync(out_values, ln.d_fv, keep * 4, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(ix, hipStreamSynchronize(s));
+    }
+    if (fo32)
+        for (uint64_t i = 0; i < nfo; i++) fo32[i] = (uint32_t)fo[i];
+    return total > cap ? TM_ECAP : TM_OK;
+}
+
 // The product path of a batched broker: match into device scratch (CSR,
 // traversal order), fan out with the index's own destination table, copy the
 // destination-major arrays back.  The lane's value scratch always holds the
-// whole batch (it grows and the batch runs again, as tm_match_batch's staging
-// does), so the bucket offsets are complete whatever `cap` is; cap only bounds
-// what is copied out.  Same lanes, locking and look-back retry as
-// match_batch_impl.
+// whole batch (it grows and the batch runs again), so the bucket offsets are
+// complete whatever `cap` is; cap only bounds what is copied out.
 // TM_ROUTE_AGGRE: the aggre pass runs on the fan-out's results in the lane's
 // scratch, and only the kept entries are copied back.
 int tm_route_batch_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
@@ -3264,14 +3346,11 @@ int tm_route_batch_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_
     if (!to || !out_dest_offsets || (n && !tb && to[n] != to[0]) || (cap && (!out_topic || !out_values)))
         return fail(ix, TM_EINVAL, "tm_route_batch: null buffer");
     if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch: batch too large");
-    std::unique_lock<std::mutex> g(ix->mu);
-    LaneLease lease{ix, g};
+    HostBatch hb(ix);
     int rc;
-    if ((rc = host_lane(ix, g, lease.ln))) return rc;
-    Lane &ln = *lease.ln;
+    if ((rc = hb.open(n))) return rc;
+    Lane &ln = *hb.ln;
     const hipStream_t s = ln.s;
-    if ((rc = sync_locked(ix, ln.r, s))) return rc;
-    if ((rc = ensure_ws(ix, n, ln))) return rc;
     ix->rep[ln.r].batches++;
     const uint8_t *dbytes;
     const uint64_t *doffs;
@@ -3282,77 +3361,31 @@ int tm_route_batch_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_
     uint64_t *dhit = reinterpret_cast<uint64_t *>(dres);
     uint8_t *derr = dres + (n + 1) * 8;
     uint64_t total = 0, vcap = std::max<uint64_t>({ln.d_vals_cap, 4 * n, 1 << 16});
-    for (int attempt = 0, tries = 0;; attempt++) {
+    for (int attempt = 0;; attempt++) {
         if (vcap > 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch: more than 2^32 - 1 hits in one batch");
         if ((rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, vcap))) return rc;
-        if ((rc = grow_dev(ix, s, ln.d_ft, ln.d_ft_cap, vcap))) return rc;
-        if ((rc = grow_dev(ix, s, ln.d_fv, ln.d_fv_cap, vcap))) return rc;
-        if ((rc = grow_dev(ix, s, ln.d_fo, ln.d_fo_cap, (uint64_t)n_dests + 2))) return rc;
-        if ((rc = ensure_fanout(ix, ln, n_dests, vcap))) return rc;
-        if (aggre) {
-            if ((rc = grow_dev(ix, s, ln.d_at, ln.d_at_cap, vcap))) return rc;
-            if ((rc = grow_dev(ix, s, ln.d_av, ln.d_av_cap, vcap))) return rc;
-            if ((rc = grow_dev(ix, s, ln.d_ao, ln.d_ao_cap, (uint64_t)n_dests + 2))) return rc;
-            if ((rc = ensure_aggre(ix, ln, vcap))) return rc;
-        }
-        const DevIndex d = dev_view(ix, ln.r);
-        uint32_t tag;
-        if ((rc = next_tag(ix, ln, s, tag))) return rc;
-        int path = PATH_PHASES;
-        HIPCHK(ix, launch_match(d, ln.w, n, dbytes, doffs, dhit, derr, ln.d_vals, vcap, tag, next_lb(ix), ix->dbg_phases,
-                                ix->small_kind, s, nullptr, nullptr, &path));
-        ix->path_batches[path]++;
-        const uint32_t *dtab = nullptr;
-        uint64_t dlen = 0;
-        if ((rc = dest_upload(ix, ix->rep[ln.r].group, s, dtab, dlen))) return rc;
-        HIPCHK(ix, launch_fanout(ln.f, n, dhit, ln.d_vals, vcap, dtab, dlen, n_dests, ln.d_fo, ln.d_ft, ln.d_fv, s));
-        if (aggre) {
-            const uint32_t *ftab = nullptr;
-            uint64_t flen = 0;
-            if ((rc = filter_upload(ix, ix->rep[ln.r].group, s, ftab, flen))) return rc;
-            HIPCHK(ix, launch_aggre(ln.f, n_dests, ln.d_fo, ln.d_ft, ln.d_fv, vcap, ftab, flen, ln.d_ao, ln.d_at, ln.d_av, s));
-        }
-        if ((rc = fetch_out(ix, ln, n, rbytes))) return rc;
-        if ((rc = batch_done(ix, ln))) return rc;
-        g.unlock();
-        HIPCHK(ix, hipStreamSynchronize(s));
-        if (batch_failed(ix, ln)) {   // the look-back failed: run the batch again, once
-            if ((rc = retry_or_fail(ix, g, ln, tries++))) return rc;
-            attempt--;
-            continue;
-        }
+        if ((rc = route_scratch(ix, ln, n_dests, vcap, aggre, false, 0))) return rc;
+        rc = hb.run([&](const DevIndex &d, uint32_t tag) -> int {
+            int path = PATH_PHASES;
+            HIPCHK(ix, launch_match(d, ln.w, n, dbytes, doffs, dhit, derr, ln.d_vals, vcap, tag, next_lb(ix),
+                                    ix->dbg_phases, ix->small_kind, s, nullptr, nullptr, &path));
+            ix->path_batches[path]++;
+            // (aggre before the total is known: no second wait when it fits)
+            if (int rc = queue_grid_fanout(ix, ln, n, dhit, nullptr, vcap, n_dests, aggre)) return rc;
+            return fetch_out(ix, ln, n, rbytes);
+        });
+        if (rc) return rc;
         std::memcpy(&total, ln.pin_out + n * 8, 8);
         if (total <= vcap) break;
         if (attempt >= 2) return fail(ix, TM_EDEVICE, "tm_route_batch: hit total kept growing past the value scratch");
         vcap = total + total / 4;
-        g.lock();
-        HIPCHK(ix, hipSetDevice(ix->rep[ln.r].device));
-        if ((rc = sync_locked(ix, ln.r, s))) return rc;
-        if ((rc = ensure_ws(ix, n, ln))) return rc;
+        if ((rc = hb.relock())) return rc;
     }
-    // (the lane is still checked out: its buffers are this caller's)
-    if (aggre && total <= cap) {
-        HIPCHK(ix, hipMemcpyAsync(out_dest_offsets, ln.d_ao, ((uint64_t)n_dests + 2) * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ix, hipStreamSynchronize(s));
-        const uint64_t kept = std::min(out_dest_offsets[n_dests + 1], cap);   // (K <= total <= cap)
-        if (kept) {
-            HIPCHK(ix, hipMemcpyAsync(out_topic, ln.d_at, kept * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(ix, hipMemcpyAsync(out_values, ln.d_av, kept * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(ix, hipStreamSynchronize(s));
-        }
-        if (out_err && n) std::memcpy(out_err, ln.pin_out + (n + 1) * 8, n);
-        return TM_OK;
-    }
-    // (aggre and no room for the fan-out: the un-aggregated sizes, no entries)
-    const uint64_t keep = aggre ? 0 : std::min(total, cap);
-    HIPCHK(ix, hipMemcpyAsync(out_dest_offsets, ln.d_fo, ((uint64_t)n_dests + 2) * 8, hipMemcpyDeviceToHost, s));
-    if (keep) {
-        HIPCHK(ix, hipMemcpyAsync(out_topic, ln.d_ft, keep * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(ix, hipMemcpyAsync(out_values, ln.d_fv, keep * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(ix, hipStreamSynchronize(s));
+    rc = copy_route_out(ix, ln, n_dests, total, cap, aggre, aggre && total <= cap, out_dest_offsets, nullptr, out_topic,
+                        out_values);
+    if (rc != TM_OK && rc != TM_ECAP) return rc;
     if (out_err && n) std::memcpy(out_err, ln.pin_out + (n + 1) * 8, n);
-    return total > cap ? TM_ECAP : TM_OK;
+    return rc;
 }
 
 int tm_route_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
@@ -3374,15 +3407,16 @@ int tm_match_batch32_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint3
     if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (a 32-bit offset addresses no more)
     if (n && n <= ZC_TOPICS && order == TM_ORDER_TRAVERSAL && ((uintptr_t)tb & 15) == 0) {
         const uint64_t nbytes = to[n];   // (before the lock: in TM_ALLOC_VRAM memory a host read is a PCIe round trip)
-        std::unique_lock<std::mutex> g(ix->mu);
-        uint8_t *db = nbytes ? pinned_dev(ix, tb, nbytes) : nullptr;
-        uint8_t *dof = pinned_dev(ix, to, (n + 1) * 4);
-        uint8_t *dh = pinned_dev(ix, out_hit, (n + 1) * 4);
-        uint8_t *dv = out_vals ? pinned_dev(ix, out_vals, cap * 4) : nullptr;
-        uint8_t *de = out_err ? pinned_dev(ix, out_err, n) : nullptr;
-        if ((db || !nbytes) && dof && dh && (dv || !out_vals) && (de || !out_err)) {
+        HostBatch hb(ix);
+        bool ok = tb || !nbytes;
+        uint8_t *db = opt_dev(ix, tb, nbytes, ok);
+        uint8_t *dof = opt_dev(ix, to, (n + 1) * 4, ok);
+        uint8_t *dh = opt_dev(ix, out_hit, (n + 1) * 4, ok);
+        uint8_t *dv = opt_dev(ix, out_vals, cap * 4, ok);
+        uint8_t *de = opt_dev(ix, out_err, n, ok);
+        if (ok) {
             if (ix->cmb_leaders > 0 && de) {   // through the combiner (the flags have a home)
-                g.unlock();
+                hb.g.unlock();
                 SmallReq rq;
                 rq.n = n; rq.db = db; rq.dof = dof; rq.dh = dh; rq.de = de; rq.dv = dv; rq.cap = dv ? cap : 0;
                 const int rc = small_combined(ix, rq);
@@ -3390,33 +3424,23 @@ int tm_match_batch32_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint3
                     if (rc) return rc;
                     return (out_vals && out_hit[n] > cap) ? TM_ECAP : TM_OK;
                 }
-                g.lock();
+                hb.g.lock();
             }
-            LaneLease lease{ix, g};
             int rc;
-            if ((rc = host_lane(ix, g, lease.ln))) return rc;
-            Lane &ln = *lease.ln;
-            const hipStream_t s = ln.s;
-            if ((rc = sync_locked(ix, ln.r, s))) return rc;
-            if ((rc = ensure_ws(ix, n, ln))) return rc;
+            if ((rc = hb.open(n))) return rc;
+            Lane &ln = *hb.ln;
             if (small_path_ok(dev_view(ix, ln.r), n)) {
                 ix->rep[ln.r].batches++;
                 if (!de && (rc = stage_out(ix, ln, n, n, de))) return rc;   // flags nobody reads still need a home
-                for (int tries = 0;; tries++) {
-                    const DevIndex d = dev_view(ix, ln.r);
-                    uint32_t tag;
-                    if ((rc = next_tag(ix, ln, s, tag))) return rc;
+                rc = hb.run([&](const DevIndex &d, uint32_t tag) -> int {
                     int path = PATH_SMALL;
                     HIPCHK(ix, launch_match32(d, ln.w, n, db ? db : dof, reinterpret_cast<const uint32_t *>(dof),
                                               reinterpret_cast<uint32_t *>(dh), de, reinterpret_cast<uint32_t *>(dv),
-                                              dv ? cap : 0, tag, next_lb(ix), ix->small_kind, s, &path));
+                                              dv ? cap : 0, tag, next_lb(ix), ix->small_kind, ln.s, &path));
                     ix->path_batches[path]++;
-                    if ((rc = batch_done(ix, ln))) return rc;
-                    g.unlock();
-                    HIPCHK(ix, hipStreamSynchronize(s));
-                    if (!batch_failed(ix, ln)) break;
-                    if ((rc = retry_or_fail(ix, g, ln, tries))) return rc;
-                }
+                    return TM_OK;
+                });
+                if (rc) return rc;
                 return (out_vals && out_hit[n] > cap) ? TM_ECAP : TM_OK;
             }
         }
@@ -3460,15 +3484,16 @@ int tm_match_batch32_pairs(tm_index *ix, uint64_t n, const uint8_t *tb, const ui
     if (n <= ZC_TOPICS && ((uintptr_t)tb & 15) == 0) {
         const uint64_t nbytes = to[n];   // (before the lock: in TM_ALLOC_VRAM memory a host read is a PCIe round trip)
         SmallReq rq;
+        bool ok = tb || !nbytes;
         {
             std::lock_guard<std::mutex> g(ix->mu);
-            rq.db = nbytes ? pinned_dev(ix, tb, nbytes) : nullptr;
-            rq.dof = pinned_dev(ix, to, (n + 1) * 4);
-            rq.dh = pinned_dev(ix, out_pairs, (2 * n + 1) * 4);
-            rq.dv = out_vals ? pinned_dev(ix, out_vals, cap * 4) : nullptr;
-            rq.de = pinned_dev(ix, out_err, n);
+            rq.db = opt_dev(ix, tb, nbytes, ok);
+            rq.dof = opt_dev(ix, to, (n + 1) * 4, ok);
+            rq.dh = opt_dev(ix, out_pairs, (2 * n + 1) * 4, ok);
+            rq.dv = opt_dev(ix, out_vals, cap * 4, ok);
+            rq.de = opt_dev(ix, out_err, n, ok);
         }
-        if ((rq.db || !nbytes) && rq.dof && rq.dh && (rq.dv || !out_vals) && rq.de) {
+        if (ok) {
             rq.n = n; rq.cap = rq.dv ? cap : 0; rq.pairs = true;
             uint64_t t_end = 0;   // (TM_DEBUG_COMBINE 0: every batch its own launch)
             const int rc = ix->cmb_leaders.load() > 0 ? small_combined(ix, rq)
@@ -3504,21 +3529,19 @@ constexpr int ROUTE32_OTHER = 1;   // (not a TM_ code)
 static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint64_t nbytes,
                             uint32_t n_dests, uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
                             uint64_t cap, uint8_t *out_err, bool aggre) {
-    std::unique_lock<std::mutex> g(ix->mu);
-    uint8_t *db = nbytes ? pinned_dev(ix, tb, nbytes) : nullptr;
-    uint8_t *dof = pinned_dev(ix, to, (n + 1) * 4);
-    uint8_t *dfo = pinned_dev(ix, out_dest_offsets, ((uint64_t)n_dests + 2) * 4);
-    uint8_t *dt = cap ? pinned_dev(ix, out_topic, cap * 4) : nullptr;
-    uint8_t *dv = cap ? pinned_dev(ix, out_values, cap * 4) : nullptr;
-    uint8_t *de = pinned_dev(ix, out_err, n);
-    if (!((db || !nbytes) && dof && dfo && (!cap || (dt && dv)) && de)) return ROUTE32_OTHER;
-    LaneLease lease{ix, g};
+    HostBatch hb(ix);
+    bool ok = tb || !nbytes;
+    uint8_t *db = opt_dev(ix, tb, nbytes, ok);
+    uint8_t *dof = opt_dev(ix, to, (n + 1) * 4, ok);
+    uint8_t *dfo = opt_dev(ix, out_dest_offsets, ((uint64_t)n_dests + 2) * 4, ok);
+    uint8_t *dt = opt_dev(ix, out_topic, cap * 4, ok);
+    uint8_t *dv = opt_dev(ix, out_values, cap * 4, ok);
+    uint8_t *de = pinned_dev(ix, out_err, n);   // (required even for no topics)
+    if (!ok || !de) return ROUTE32_OTHER;
     int rc;
-    if ((rc = host_lane(ix, g, lease.ln))) return rc;
-    Lane &ln = *lease.ln;
+    if ((rc = hb.open(n + (uint64_t)SMALL_SEGS * SM_TOPICS))) return rc;
+    Lane &ln = *hb.ln;
     const hipStream_t s = ln.s;
-    if ((rc = sync_locked(ix, ln.r, s))) return rc;
-    if ((rc = ensure_ws(ix, n + (uint64_t)SMALL_SEGS * SM_TOPICS, ln))) return rc;
     if (n && !small_path_ok(dev_view(ix, ln.r), n)) return ROUTE32_OTHER;
     ix->rep[ln.r].batches++;
     if (!ln.fo1_h) {
@@ -3528,7 +3551,7 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     if (aggre && !ln.fo1_s) HIPCHK(ix, hipMalloc(&ln.fo1_s, FO1_ST_WORDS * 4));
     volatile uint32_t *st = ln.fo1_h;
     uint64_t total = 0, vcap = std::max<uint64_t>({ln.d_vals_cap, 4 * n, 1 << 16});
-    for (int attempt = 0, tries = 0;; attempt++) {
+    for (int attempt = 0;; attempt++) {
         if (vcap > 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch32: more than 2^32 - 1 hits in one batch");
         if ((rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, vcap))) return rc;
         if ((rc = grow_dev(ix, s, ln.d_pr, ln.d_pr_cap, 2 * n + 2))) return rc;
@@ -3537,52 +3560,42 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
             if ((rc = grow_dev(ix, s, ln.d_fv, ln.d_fv_cap, FO1_ENTRIES))) return rc;
             if ((rc = grow_dev(ix, s, ln.d_fo, ln.d_fo_cap, (uint64_t)n_dests + 2))) return rc;
         }
-        if (n) {
-            const DevIndex d = dev_view(ix, ln.r);
-            uint32_t tag;
-            if ((rc = next_tag(ix, ln, s, tag))) return rc;
-            SmallSegs sg{};
-            sg.count = 1;
-            sg.pairs = 1;
-            sg.s[0] = SmallSeg{db ? db : dof, dof, ln.d_pr, de, ln.d_vals, vcap, (uint32_t)n, 0};
-            int path = PATH_SMALL;
-            HIPCHK(ix, launch_small_segs(d, ln.w, sg, true, tag, next_lb(ix), ix->small_kind, s, &path));
-            ix->path_batches[path]++;
-        }
-        const uint32_t *dtab = nullptr;
-        uint64_t dlen = 0;
-        if ((rc = dest_upload(ix, ix->rep[ln.r].group, s, dtab, dlen))) return rc;
-        st[FO1_ST_STATE] = 0;   // (the lane's stream is idle: nothing else writes the words)
-        if (!aggre) {
-            HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, reinterpret_cast<uint32_t *>(dfo),
-                                         reinterpret_cast<uint32_t *>(dt), reinterpret_cast<uint32_t *>(dv), cap, ln.fo1_d, s));
-        } else {
-            const uint32_t *ftab = nullptr;
-            uint64_t flen = 0;
-            if ((rc = filter_upload(ix, ix->rep[ln.r].group, s, ftab, flen))) return rc;
-            uint32_t *fo32 = reinterpret_cast<uint32_t *>(ln.d_fo);
-            HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, fo32, ln.d_ft, ln.d_fv,
+        rc = hb.run([&](const DevIndex &d, uint32_t tag) -> int {
+            int rc;
+            if (n) {
+                SmallSegs sg{};
+                sg.count = 1;
+                sg.pairs = 1;
+                sg.s[0] = SmallSeg{db ? db : dof, dof, ln.d_pr, de, ln.d_vals, vcap, (uint32_t)n, 0};
+                int path = PATH_SMALL;
+                HIPCHK(ix, launch_small_segs(d, ln.w, sg, true, tag, next_lb(ix), ix->small_kind, s, &path));
+                ix->path_batches[path]++;
+            }
+            const int grp = ix->rep[ln.r].group;
+            const uint32_t *dtab = nullptr, *ftab = nullptr;
+            uint64_t dlen = 0, flen = 0;
+            if ((rc = dest_upload(ix, grp, s, dtab, dlen))) return rc;
+            st[FO1_ST_STATE] = 0;   // (the lane's stream is idle: nothing else writes the words)
+            uint32_t *fo32 = reinterpret_cast<uint32_t *>(dfo), *t32 = reinterpret_cast<uint32_t *>(dt),
+                     *v32 = reinterpret_cast<uint32_t *>(dv);
+            if (!aggre) {
+                HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, fo32, t32, v32, cap, ln.fo1_d, s));
+                return TM_OK;
+            }
+            if ((rc = filter_upload(ix, grp, s, ftab, flen))) return rc;
+            uint32_t *lfo = reinterpret_cast<uint32_t *>(ln.d_fo);
+            HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, lfo, ln.d_ft, ln.d_fv,
                                          FO1_ENTRIES, ln.fo1_s, s));
-            HIPCHK(ix, launch_aggre_one(ln.fo1_s, fo32, n_dests, ln.d_ft, ln.d_fv, ftab, flen,
-                                        reinterpret_cast<uint32_t *>(dfo), reinterpret_cast<uint32_t *>(dt),
-                                        reinterpret_cast<uint32_t *>(dv), cap, ln.fo1_d, s));
-        }
-        if ((rc = batch_done(ix, ln))) return rc;
-        g.unlock();
-        HIPCHK(ix, hipStreamSynchronize(s));
-        if (batch_failed(ix, ln)) {   // (as tm_route_batch: run the batch again, once)
-            if ((rc = retry_or_fail(ix, g, ln, tries++))) return rc;
-            attempt--;
-            continue;
-        }
+            HIPCHK(ix, launch_aggre_one(ln.fo1_s, lfo, n_dests, ln.d_ft, ln.d_fv, ftab, flen, fo32, t32, v32, cap,
+                                        ln.fo1_d, s));
+            return TM_OK;
+        });
+        if (rc) return rc;
         total = st[FO1_ST_TOTAL];
         if (total <= vcap) break;
         if (attempt >= 2) return fail(ix, TM_EDEVICE, "tm_route_batch32: hit total kept growing past the value scratch");
         vcap = total + total / 4;
-        g.lock();
-        HIPCHK(ix, hipSetDevice(ix->rep[ln.r].device));
-        if ((rc = sync_locked(ix, ln.r, s))) return rc;
-        if ((rc = ensure_ws(ix, n + (uint64_t)SMALL_SEGS * SM_TOPICS, ln))) return rc;
+        if ((rc = hb.relock())) return rc;
     }
     const uint32_t state = st[FO1_ST_STATE];
     if (state == FO1_DONE) {
@@ -3592,58 +3605,21 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     if (state != FO1_TOO_LARGE) return fail(ix, TM_EDEVICE, "tm_route_batch32: the fan-out kernel left no status");
     // more entries than k_fo_one takes: the grid kernels on the same pairs (no
     // second walk), into the lane's scratch, copied out and narrowed
-    g.lock();
-    HIPCHK(ix, hipSetDevice(ix->rep[ln.r].device));
-    if ((rc = grow_dev(ix, s, ln.d_ft, ln.d_ft_cap, vcap))) return rc;
-    if ((rc = grow_dev(ix, s, ln.d_fv, ln.d_fv_cap, vcap))) return rc;
-    if ((rc = grow_dev(ix, s, ln.d_fo, ln.d_fo_cap, (uint64_t)n_dests + 2))) return rc;
-    if ((rc = ensure_fanout(ix, ln, n_dests, vcap, true, n))) return rc;
-    const uint32_t *dtab = nullptr;
-    uint64_t dlen = 0;
-    if ((rc = dest_upload(ix, ix->rep[ln.r].group, s, dtab, dlen))) return rc;
-    HIPCHK(ix, launch_fanout_pairs(ln.f, n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, ln.d_fo, ln.d_ft, ln.d_fv, s));
     const bool ag = aggre && total <= cap;   // (else TM_ECAP: the un-aggregated sizes, no entries)
-    if (ag) {
-        if ((rc = grow_dev(ix, s, ln.d_at, ln.d_at_cap, vcap))) return rc;
-        if ((rc = grow_dev(ix, s, ln.d_av, ln.d_av_cap, vcap))) return rc;
-        if ((rc = grow_dev(ix, s, ln.d_ao, ln.d_ao_cap, (uint64_t)n_dests + 2))) return rc;
-        if ((rc = ensure_aggre(ix, ln, vcap))) return rc;
-        const uint32_t *ftab = nullptr;
-        uint64_t flen = 0;
-        if ((rc = filter_upload(ix, ix->rep[ln.r].group, s, ftab, flen))) return rc;
-        HIPCHK(ix, launch_aggre(ln.f, n_dests, ln.d_fo, ln.d_ft, ln.d_fv, vcap, ftab, flen, ln.d_ao, ln.d_at, ln.d_av, s));
-    }
-    if ((rc = batch_done(ix, ln))) return rc;
-    g.unlock();
     std::vector<uint64_t> fo;
     try {
         fo.resize((uint64_t)n_dests + 2);
     } catch (const std::bad_alloc &) {
         return fail(ix, TM_ENOMEM, "tm_route_batch32: out of host memory");
     }
-    if (ag) {
-        HIPCHK(ix, hipMemcpyAsync(fo.data(), ln.d_ao, fo.size() * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ix, hipStreamSynchronize(s));
-        const uint64_t kept = std::min(fo[n_dests + 1], cap);   // (K <= total <= cap)
-        if (kept) {
-            HIPCHK(ix, hipMemcpyAsync(out_topic, ln.d_at, kept * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(ix, hipMemcpyAsync(out_values, ln.d_av, kept * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(ix, hipStreamSynchronize(s));
-        }
-        for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
-        ix->route_grid++;
-        return TM_OK;
-    }
-    const uint64_t keep = aggre ? 0 : std::min(total, cap);
-    HIPCHK(ix, hipMemcpyAsync(fo.data(), ln.d_fo, fo.size() * 8, hipMemcpyDeviceToHost, s));
-    if (keep) {
-        HIPCHK(ix, hipMemcpyAsync(out_topic, ln.d_ft, keep * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(ix, hipMemcpyAsync(out_values, ln.d_fv, keep * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(ix, hipStreamSynchronize(s));
-    for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
-    ix->route_grid++;
-    return total > cap ? TM_ECAP : TM_OK;
+    if ((rc = hb.relock())) return rc;
+    if ((rc = route_scratch(ix, ln, n_dests, vcap, ag, true, n))) return rc;
+    if ((rc = queue_grid_fanout(ix, ln, n, nullptr, ln.d_pr, vcap, n_dests, ag))) return rc;
+    if ((rc = batch_done(ix, ln))) return rc;
+    hb.g.unlock();
+    rc = copy_route_out(ix, ln, n_dests, total, cap, aggre, ag, fo.data(), out_dest_offsets, out_topic, out_values);
+    if (rc == TM_OK || rc == TM_ECAP) ix->route_grid++;
+    return rc;
 }
 
 int tm_route_batch32_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint32_t n_dests,
@@ -3691,21 +3667,13 @@ int tm_match_batch32_dev(tm_index *ix, uint64_t n, const uint8_t *bytes, const u
     if (!hit_offs || (n && (!offs || !bytes || !err))) return fail(ix, TM_EINVAL, "tm_match_batch32_dev: null buffer");
     if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_match_batch32_dev: batch too large");
     if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;
-    std::lock_guard<std::mutex> g(ix->mu);
-    hipStream_t s = pick_stream(ix, stream);
-    int rc, grp = 0;
-    Lane *ln;
-    if ((rc = dev_group(ix, grp))) return rc;
-    if ((rc = collect_patch(ix))) return rc;
-    const int r = pick_copy(ix, grp, nullptr, s, true);
-    ix->rep[r].last_use = ++ix->tick;
-    ix->rep[r].batches++;
-    if ((rc = dev_lane(ix, s, r, ln))) return rc;
-    if ((rc = sync_locked(ix, ln->r, s))) return rc;
-    if ((rc = ensure_ws(ix, n, *ln))) return rc;
-    const DevIndex d = dev_view(ix, ln->r);
-    tm_index::ProfEv ev;
-    if ((rc = prof_begin(ix, ev, s))) return rc;
+    DevBatch b(ix, stream);
+    int rc;
+    if ((rc = b.open_match(n))) return rc;
+    Lane *ln = b.ln;
+    const DevIndex &d = b.d;
+    const hipStream_t s = b.s;
+    const tm_index::ProfEv &ev = b.ev;
     uint32_t tag;
     if ((rc = next_tag(ix, *ln, s, tag))) return rc;
     if (small_path_ok(d, n)) {
@@ -3726,8 +3694,7 @@ int tm_match_batch32_dev(tm_index *ix, uint64_t n, const uint8_t *bytes, const u
         ix->path_batches[path]++;
         HIPCHK(ix, launch_offs_narrow(ln->d_h64, hit_offs, n + 1, s));
     }
-    if ((rc = batch_done(ix, *ln))) return rc;
-    return prof_end(ix, ev, s);
+    return b.done();
 }
 
 int tm_first_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t *out_value,
@@ -3736,25 +3703,26 @@ int tm_first_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *
     if (!to || !out_value || !out_found || (n && !tb && to[n] != to[0]))
         return fail(ix, TM_EINVAL, "tm_first_batch: null buffer");
     if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_first_batch: batch too large");
-    std::unique_lock<std::mutex> g(ix->mu);
-    LaneLease lease{ix, g};
+    HostBatch hb(ix);
     int rc;
-    if ((rc = host_lane(ix, g, lease.ln))) return rc;
-    Lane &ln = *lease.ln;
+    if ((rc = hb.open(n))) return rc;
+    Lane &ln = *hb.ln;
     const hipStream_t s = ln.s;
-    if ((rc = sync_locked(ix, ln.r, s))) return rc;
-    if ((rc = ensure_ws(ix, n, ln))) return rc;
     ix->rep[ln.r].batches++;
-    if (n && n <= ZC_TOPICS) {   // tm_host_alloc buffers: in place, as tm_match_batch
+    // (launch_first has no look-back: nothing to retry, so no run())
+    if (n && n <= ZC_TOPICS) {   // tm_host_alloc buffers: in place
         const uint64_t nbytes = to[n];
-        uint8_t *db = nbytes ? pinned_dev(ix, tb, nbytes) : nullptr;
-        uint8_t *dof = pinned_dev(ix, to, (n + 1) * 8);
-        uint8_t *dv = pinned_dev(ix, out_value, n * 4), *df = pinned_dev(ix, out_found, n);
-        if ((db || !nbytes) && ((uintptr_t)tb & 15) == 0 && dof && dv && df) {
+        bool ok = tb || !nbytes;
+        uint8_t *db = opt_dev(ix, tb, nbytes, ok);
+        uint8_t *dof = opt_dev(ix, to, (n + 1) * 8, ok);
+        uint8_t *dv = opt_dev(ix, out_value, n * 4, ok);
+        uint8_t *df = opt_dev(ix, out_found, n, ok);
+        const bool aligned = ((uintptr_t)tb & 15) == 0;
+        if (ok && aligned) {
             HIPCHK(ix, launch_first(dev_view(ix, ln.r), ln.w, n, db ? db : dof, reinterpret_cast<const uint64_t *>(dof),
                                     reinterpret_cast<uint32_t *>(dv), df, s));
             if ((rc = batch_done(ix, ln))) return rc;
-            g.unlock();
+            hb.g.unlock();
             HIPCHK(ix, hipStreamSynchronize(s));
             return TM_OK;
         }
@@ -3768,7 +3736,7 @@ int tm_first_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *
     HIPCHK(ix, launch_first(dev_view(ix, ln.r), ln.w, n, dbytes, doffs, reinterpret_cast<uint32_t *>(dres), dres + n * 4, s));
     if ((rc = fetch_out(ix, ln, n, rbytes))) return rc;
     if ((rc = batch_done(ix, ln))) return rc;
-    g.unlock();
+    hb.g.unlock();
     HIPCHK(ix, hipStreamSynchronize(s));
     if (n) {
         memcpy(out_value, ln.pin_out, n * 4);
