@@ -29,7 +29,7 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_match_batch32_dev", "tm_matches_filter_ex", "tm_host_alloc_ex", "tm_commit",
            "tm_match_batch32_pairs", "tm_match_batch_dev_pairs", "tm_set_dests", "tm_fanout_dev", "tm_route_batch",
            "tm_fanout_dev_pairs", "tm_route_batch32", "tm_set_route_filters", "tm_aggre_dev", "tm_route_batch_ex",
-           "tm_route_batch32_ex")
+           "tm_route_batch32_ex", "tm_set_subscribers", "tm_dispatch_dev", "tm_dispatch_batch")
 TM_ALLOC_VRAM = 1
 TM_ROUTE_AGGRE = 1          # tm_route_batch_ex / tm_route_batch32_ex: aggre/1 applied to the buckets
 NO_FILTER = 0xFFFFFFFF      # tm_set_route_filters: no filter known (equal to nothing)
@@ -49,6 +49,7 @@ TM_DEBUG_FANOUT_GRID = 25   # (get only) one-wave blocks of a fan-out pass
 TM_DEBUG_ROUTE_ONE, TM_DEBUG_ROUTE_GRID = 26, 27   # (get only) route_batch32 calls per fan-out path
 # (get only) the node annexed to a vocab-hint slot (depth << 32 | children; all ones: none); hints that disagree (0)
 TM_DEBUG_ANNEX0, TM_DEBUG_ANNEX1, TM_DEBUG_HINT_AUDIT = 28, 29, 30
+TM_DEBUG_SUB_COMPACTIONS = 31   # (get only) rewrites of tm_set_subscribers' pool
 MAX_DESTS = 65536           # tm_fanout_dev / tm_route_batch: n_dests is 1 .. MAX_DESTS
 
 
@@ -137,6 +138,9 @@ def load_library(path: Path | None = None):
         "tm_aggre_dev": (i32, [vp, u32, vp, vp, vp, u64, vp, u64, vp, vp, vp, vp]),
         "tm_route_batch_ex": (i32, [vp, u64, vp, vp, u32, vp, vp, vp, u64, vp, u32]),
         "tm_route_batch32_ex": (i32, [vp, u64, vp, vp, u32, vp, vp, vp, u64, vp, u32]),
+        "tm_set_subscribers": (i32, [vp, u64, vp, vp, vp]),
+        "tm_dispatch_dev": (i32, [vp, u32, vp, u32, vp, vp, u64, vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, vp]),
+        "tm_dispatch_batch": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp]),
         "tm_debug_set": (i32, [vp, u32, u64]),
         "tm_debug_get": (i32, [vp, u32, C.POINTER(u64)]),
     }
@@ -513,6 +517,68 @@ class Index:
                                                    _ptr(vals), cap, _ptr(err)))
         total = int(doff[n_dests + 1])
         return doff[: n_dests + 2], topic[:total], vals[:total], err[:n]
+
+    # ---- local dispatch (include/tmatch.h "Local dispatch on the device")
+    def set_subscribers(self, values, lists):
+        """tm_set_subscribers: lists[i] (u32 subscriber ids, in dispatch order)
+        becomes the local subscriber list of route value values[i]."""
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        if len(values) != len(lists):
+            raise ValueError("set_subscribers: one list per value")
+        offs = np.zeros(len(values) + 1, dtype=np.uint64)
+        if len(values):
+            offs[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64)
+        subs = np.zeros(max(int(offs[-1]), 1), dtype=np.uint32)
+        for i, x in enumerate(lists):
+            subs[int(offs[i]):int(offs[i + 1])] = np.asarray(x, dtype=np.uint32)
+        self._check(self._lib.tm_set_subscribers(self._h, len(values), _ptr(values), _ptr(offs), _ptr(subs)))
+
+    def dispatch_dev(self, n_dests: int, d_dest_offs: int, bucket: int, d_topic: int, d_value: int, cap: int,
+                     d_out_head: int, d_out_topic: int, d_out_value: int, d_out_sub: int, out_cap: int,
+                     d_out_offsets: int | None = None, d_sub_span: int | None = None, span_len: int = 0,
+                     d_sub_pool: int | None = None, pool_len: int = 0, stream: int | None = None):
+        """tm_dispatch_dev on device pointers: bucket `bucket` of a fan-out's or
+        an aggre pass's output expanded to one (topic, value, subscriber)
+        delivery per subscriber of each entry's value; d_out_head u64[2] = (the
+        bucket's entries M, the deliveries T), the first min(T, out_cap) of them
+        written; d_out_offsets (optional) u64[M + 1].  d_sub_span None: the
+        table of set_subscribers."""
+        self._check(self._lib.tm_dispatch_dev(self._h, n_dests, d_dest_offs, bucket, d_topic, d_value, cap, d_sub_span,
+                                              span_len, d_sub_pool, pool_len, d_out_head, d_out_offsets, d_out_topic,
+                                              d_out_value, d_out_sub, out_cap, stream))
+
+    def dispatch_batch(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, local_dest: int, cap: int | None = None,
+                       dcap: int | None = None, aggre: bool = False):
+        """tm_dispatch_batch -> (route_batch's (dest_offsets, topic, values, err),
+        (dtopic u32[T], dvalue u32[T], dsub u32[T])): the route buckets and the
+        deliveries of bucket local_dest with the table of set_subscribers, in
+        entry order and list order.  A cap that proves too small is retried,
+        sized from what the call returned."""
+        n = len(offs) - 1
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        doff = np.zeros(n_dests + 2, dtype=np.uint64)
+        head = np.zeros(2, dtype=np.uint64)
+        err = np.zeros(max(n, 1), dtype=np.uint8)
+        if cap is None:
+            cap = max(4 * n, 1024)
+        if dcap is None:
+            dcap = max(4 * n, 1024)
+        for _ in range(4):
+            topic = np.empty(max(cap, 1), dtype=np.uint32)
+            vals = np.empty(max(cap, 1), dtype=np.uint32)
+            dt, dv, ds = (np.empty(max(dcap, 1), dtype=np.uint32) for _ in range(3))
+            rc = self._lib.tm_dispatch_batch(self._h, n, _ptr(blob), _ptr(offs), n_dests, local_dest,
+                                             TM_ROUTE_AGGRE if aggre else 0, _ptr(doff), _ptr(topic), _ptr(vals), cap,
+                                             _ptr(head), _ptr(dt), _ptr(dv), _ptr(ds), dcap, _ptr(err))
+            if rc == TM_ECAP and (int(doff[-1]) > cap or int(head[1]) > dcap):
+                cap = max(cap, int(doff[-1]))
+                dcap = max(dcap, int(head[1]))
+                continue
+            self._check(rc)
+            total, T = int(doff[-1]), int(head[1])
+            return (doff, topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T])
+        raise TmError(TM_ECAP, "dispatch_batch: the totals kept growing")
 
     def release_stream(self, stream: int | None):
         """Drop the batch scratch the library keeps for `stream`."""

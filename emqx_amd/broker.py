@@ -13,7 +13,10 @@ deliveries as an unbatched publish.
 
 Delivery itself (sessions, shared-subscription pick, cluster RPC) is out of
 scope: ``dispatch(To, Msg)``, ``forward(Node, To, Msg)`` and
-``share_dispatch(Group, To, Msg)`` are caller-supplied callbacks.
+``share_dispatch(Group, To, Msg)`` are caller-supplied callbacks.  With
+``dispatch_on_device`` the local node's ``dispatch/2`` -- the ?SUBSCRIBER
+lookups of do_dispatch2/2 (:726-760) -- has run on the device as well, and the
+callback is ``deliver(SubPid, To, Msg)``, the ``SubPid ! {deliver, To, Msg}``.
 """
 from __future__ import annotations
 
@@ -53,11 +56,17 @@ def aggre(routes):
 class Broker:
     def __init__(self, router, node=None, dispatch=None, forward=None, share_dispatch=None,
                  max_batch: int = 4096, max_wait_ms: float = 0.2, start: bool = False,
-                 aggre_on_device: bool = False):
+                 aggre_on_device: bool = False, dispatch_on_device: bool = False, deliver=None):
         """aggre_on_device: publish_batch_by_dest asks the router for buckets
-        the device has already applied aggre/1 to (TM_ROUTE_AGGRE)."""
+        the device has already applied aggre/1 to (TM_ROUTE_AGGRE).
+        dispatch_on_device: publish_batch_by_dest asks the router for the local
+        node's deliveries too (Router.match_routes_dispatch); the local node's
+        plan is then [(message index, To, subscriber)], each handed to
+        deliver(subscriber, To, message), and dispatch is not called."""
         self.router = router
         self.aggre_on_device = aggre_on_device
+        self.dispatch_on_device = dispatch_on_device
+        self.deliver = deliver or (lambda sub, to, msg: None)
         self.node = router.node if node is None else node
         self.dispatch = dispatch or (lambda to, msg: 0)
         self.forward = forward or (lambda node, to, msg: "ok")
@@ -128,7 +137,11 @@ class Broker:
         if not msgs:
             return {}, {}
         on_dev = self.aggre_on_device
-        if on_dev:
+        deliveries = None
+        if self.dispatch_on_device:
+            by_dest, deliveries = self.router.match_routes_dispatch([m.topic for m in msgs], errors="return",
+                                                                    aggre=on_dev)
+        elif on_dev:
             by_dest = self.router.match_routes_by_dest([m.topic for m in msgs], errors="return", aggre=True)
         else:
             by_dest = self.router.match_routes_by_dest([m.topic for m in msgs], errors="return")
@@ -136,6 +149,8 @@ class Broker:
         plans: dict = {}
         seen = set()
         for cls, rows in by_dest.items():
+            if deliveries is not None and cls == self.node:
+                continue   # the local node's routes are already expanded: its plan is the deliveries
             node = not isinstance(rows[0][1].dest, tuple)
             dest = cls[0] if isinstance(cls, tuple) else cls   # aggre/1: {Group, _Node} -> Group, whatever the pair
             plan = plans.setdefault(dest, [])
@@ -151,6 +166,10 @@ class Broker:
         for dest, plan in plans.items():
             plan.sort(key=lambda e: e[0])   # several classes in one plan (every ("external", X)): message order again
             out[dest] = [(i, to) + (self._route2((to, dest), msgs[i])[2],) for i, to in plan]
+        if deliveries:
+            for i, to, sub in deliveries:
+                self.deliver(sub, to, msgs[i])
+            out[self.node] = list(deliveries)
         return out, by_dest.errors
 
     # ---- asynchronous micro-batching

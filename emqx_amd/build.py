@@ -28,6 +28,7 @@ ARCH = os.environ.get("TM_OFFLOAD_ARCH", "gfx950")
 KERNEL_SOURCES = ("tm_kernels.hip", "tm_host.cpp", "tm_layout.h", "tm_dev.h", "tm_scan.h")
 FANOUT_SOURCE = "tm_fanout.hip"   # the route fan-out's kernels (not among the match kernels' sources)
 AGGRE_SOURCE = "tm_aggre.hip"     # aggre/1 on the fan-out's output (likewise)
+DISPATCH_SOURCE = "tm_dispatch.hip"   # local dispatch: route hits expanded to subscribers (likewise)
 
 
 def source_hash() -> str:
@@ -57,8 +58,9 @@ def _run(cmd, cwd=None):
 
 
 def build_tmatch(force: bool = False) -> Path:
-    srcs = [CSRC / "tm_host.cpp", CSRC / "tm_kernels.hip", CSRC / FANOUT_SOURCE, CSRC / AGGRE_SOURCE]
-    deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", ROOT / "include" / "tmatch.h"]
+    srcs = [CSRC / "tm_host.cpp", CSRC / "tm_kernels.hip", CSRC / FANOUT_SOURCE, CSRC / AGGRE_SOURCE,
+            CSRC / DISPATCH_SOURCE]
+    deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", CSRC / "tm_subs.h", ROOT / "include" / "tmatch.h"]
     if force or _stale(LIB_TMATCH, deps):
         tmp = LIB_TMATCH.with_suffix(".so.tmp")
         _run(["hipcc", "-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-shared",
@@ -77,8 +79,9 @@ def build_variant(name: str, kernel_src: str | None = None, force: bool = False,
     out = PKG / "variants" / f"libtmatch_{name}.so"
     out.parent.mkdir(exist_ok=True)
     kern = Path(kernel_src) if kernel_src else CSRC / "tm_kernels.hip"
-    srcs = [Path(host_src) if host_src else CSRC / "tm_host.cpp", kern, CSRC / FANOUT_SOURCE, CSRC / AGGRE_SOURCE]
-    deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", ROOT / "include" / "tmatch.h"]
+    srcs = [Path(host_src) if host_src else CSRC / "tm_host.cpp", kern, CSRC / FANOUT_SOURCE, CSRC / AGGRE_SOURCE,
+            CSRC / DISPATCH_SOURCE]
+    deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", CSRC / "tm_subs.h", ROOT / "include" / "tmatch.h"]
     if force or _stale(out, deps):
         _run(["hipcc", "-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-shared", "-Wall",
               "-Wno-unused-function", f"-I{CSRC}", "-o", str(out)] + [str(s) for s in srcs])

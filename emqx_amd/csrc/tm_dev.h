@@ -221,8 +221,80 @@ struct FanoutScratch {
     uint64_t *ag_bits;
     uint32_t *ag_pre, *ag_cnt;
     uint64_t ag_cap;
+    // dispatch (launch_dispatch): the per-entry list lengths below dp_cap, their scan when the caller
+    // takes no offsets (dp_off_cap + 1 words), the FO_GRID chunk sums + their total
+    uint32_t *dp_cnt;
+    uint64_t *dp_off, *dp_tot;
+    uint64_t dp_cap, dp_off_cap;
 };
 constexpr uint32_t FP_TILES = 1024;
+#if defined(__HIPCC__)
+// "Which segment holds position p": the device helpers of the fan-out's first
+// pass (tm_fanout.hip), shared with the dispatch's expansion (tm_dispatch.hip),
+// for one-wave blocks.
+// The topic of position p: the last t with hit[t] <= p, i.e. (the first index u
+// of [lo, n] with hit[u] > p) - 1, found by the whole wave, 64 probes a round
+// (1M offsets: 4 rounds instead of a binary search's 20 dependent loads).
+// `lo` is a known lower bound of u.  Reads hit[0 .. n] only, and ends whatever
+// the offsets hold.
+__device__ __forceinline__ uint64_t fo_topic_at(const uint64_t *hit, uint64_t n, uint64_t p, uint64_t lo,
+                                                uint32_t lane) {
+    uint64_t hi = n + 1;
+    if (lo > hi) lo = hi;
+    while (lo < hi) {
+        const uint64_t step = (hi - lo + 63) / 64;
+        const uint64_t idx = lo + lane * step;
+        const bool in = idx < hi;
+        const bool gt = in && hit[idx] > p;
+        const uint64_t m_gt = __ballot(gt), m_in = __ballot(in);
+        if (!m_gt) {
+            lo = lo + ((uint64_t)__popcll(m_in) - 1) * step + 1;   // every probe <= p
+        } else {
+            const uint64_t f = (uint64_t)__builtin_ctzll(m_gt);
+            hi = lo + f * step;
+            if (f) lo = lo + (f - 1) * step + 1;
+        }
+    }
+    return lo ? lo - 1 : 0;
+}
+
+// The topics of one step's positions p0 + lane (`ok`: below the chunk's end c1),
+// by the whole wave: a window of the next 64 offsets in LDS that each lane
+// searches; lanes whose topic lies beyond it (a run of more than 64 empty
+// topics) search again from the first of them.  tcur: hit[tcur] <= p0 on entry,
+// the step's last topic on return.
+__device__ __forceinline__ uint32_t fo_step_topics(const uint64_t *hit, uint64_t n, uint64_t p0, uint64_t c1, bool ok,
+                                                   uint64_t &tcur, uint64_t *s_win, uint32_t lane) {
+    const uint64_t p = p0 + lane;
+    uint32_t t = 0;
+    bool found = !ok;
+    uint64_t tw = tcur;
+    for (;;) {
+        // the ends of topics tw .. tw + 63; a lane's topic is tw + (how many of them are <= p)
+        const uint64_t idx = tw + 1 + lane;
+        s_win[lane] = idx <= n ? hit[idx] : ~0ull;
+        __syncthreads();
+        if (!found && s_win[63] > p) {
+            uint32_t c = 0;
+#pragma unroll
+            for (uint32_t st = 32; st; st >>= 1)
+                if (s_win[c + st - 1] <= p) c += st;
+            t = (uint32_t)(tw + c);
+            found = true;
+        }
+        __syncthreads();
+        const uint64_t left = __ballot(!found);
+        if (!left) break;
+        // a run of empty topics longer than the window: search again for the first lane left
+        const uint32_t fl = (uint32_t)__builtin_ctzll(left);
+        tw = fo_topic_at(hit, n, p0 + fl, tw + 65, lane);
+    }
+    const uint32_t last = c1 - p0 < 64 ? (uint32_t)(c1 - p0) - 1 : 63u;
+    tcur = __shfl(t, last, 64);
+    return t;
+}
+#endif   // __HIPCC__
+
 bool fanout_two_pass(uint32_t n_dests);
 hipError_t launch_fanout(const FanoutScratch &fs, uint64_t n, const uint64_t *hit, const uint32_t *values,
                          uint64_t cap, const uint32_t *dest_of, uint64_t dest_len, uint32_t n_dests,
@@ -273,6 +345,21 @@ hipError_t launch_aggre_one(const uint32_t *status_in, const uint32_t *dest_offs
                             const uint32_t *in_topic, const uint32_t *in_value, const uint32_t *filter_of,
                             uint64_t filter_len, uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_value,
                             uint64_t cap, uint32_t *status, hipStream_t s);
+// Local dispatch (tm_dispatch.hip): bucket `bucket` of a fan-out's or an aggre
+// pass's output -- the M entries [q0, q1), q = min(dest_offsets[bucket (+ 1)],
+// E), E = min(dest_offsets[n_dests + 1], cap) -- expanded to one delivery per
+// (entry, subscriber of the entry's value): span[2 v], span[2 v + 1] = the
+// position and length of v's list in pool (v >= span_len, or a span that does
+// not lie inside pool_len: no subscribers).  head = [M, T]; the first min(T,
+// out_cap) deliveries, in entry order and list order, go to out_topic /
+// out_value / out_sub; out_offsets (NULL: fs.dp_off) takes the M + 1 delivery
+// offsets.  span must be 8-byte aligned.  Needs fs.dp_cap >= min(cap, 2^32 -
+// 1), and fs.dp_off_cap as much when out_offsets is NULL.
+hipError_t launch_dispatch(const FanoutScratch &fs, uint32_t n_dests, const uint64_t *dest_offsets, uint32_t bucket,
+                           const uint32_t *in_topic, const uint32_t *in_value, uint64_t cap, const uint32_t *span,
+                           uint64_t span_len, const uint32_t *pool, uint64_t pool_len, uint64_t *head,
+                           uint64_t *out_offsets, uint32_t *out_topic, uint32_t *out_value, uint32_t *out_sub,
+                           uint64_t out_cap, hipStream_t s);
 // delta upload: run i copies runs[i].n u32 words from data + runs[i].src to
 // word (dst & PATCH_OFF) of table (dst >> 48), whose device address on the
 // replica being patched is bases.b[table] (the same runs patch every replica)

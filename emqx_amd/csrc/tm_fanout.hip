@@ -86,67 +86,8 @@ __device__ __forceinline__ void fo_chunk(const uint64_t *hit, uint64_t n, uint64
     if (c0 > c1) c0 = c1;
 }
 
-// The topic of position p: the last t with hit[t] <= p, i.e. (the first index u
-// of [lo, n] with hit[u] > p) - 1, found by the whole wave, 64 probes a round
-// (1M offsets: 4 rounds instead of a binary search's 20 dependent loads).
-// `lo` is a known lower bound of u.  Reads hit[0 .. n] only, and ends whatever
-// the offsets hold.
-__device__ __forceinline__ uint64_t fo_topic_at(const uint64_t *hit, uint64_t n, uint64_t p, uint64_t lo,
-                                                uint32_t lane) {
-    uint64_t hi = n + 1;
-    if (lo > hi) lo = hi;
-    while (lo < hi) {
-        const uint64_t step = (hi - lo + 63) / 64;
-        const uint64_t idx = lo + lane * step;
-        const bool in = idx < hi;
-        const bool gt = in && hit[idx] > p;
-        const uint64_t m_gt = __ballot(gt), m_in = __ballot(in);
-        if (!m_gt) {
-            lo = lo + ((uint64_t)__popcll(m_in) - 1) * step + 1;   // every probe <= p
-        } else {
-            const uint64_t f = (uint64_t)__builtin_ctzll(m_gt);
-            hi = lo + f * step;
-            if (f) lo = lo + (f - 1) * step + 1;
-        }
-    }
-    return lo ? lo - 1 : 0;
-}
-
-// The topics of one step's positions p0 + lane (`ok`: below the chunk's end c1),
-// by the whole wave: a window of the next 64 offsets in LDS that each lane
-// searches; lanes whose topic lies beyond it (a run of more than 64 empty
-// topics) search again from the first of them.  tcur: hit[tcur] <= p0 on entry,
-// the step's last topic on return.
-__device__ __forceinline__ uint32_t fo_step_topics(const uint64_t *hit, uint64_t n, uint64_t p0, uint64_t c1, bool ok,
-                                                   uint64_t &tcur, uint64_t *s_win, uint32_t lane) {
-    const uint64_t p = p0 + lane;
-    uint32_t t = 0;
-    bool found = !ok;
-    uint64_t tw = tcur;
-    for (;;) {
-        // the ends of topics tw .. tw + 63; a lane's topic is tw + (how many of them are <= p)
-        const uint64_t idx = tw + 1 + lane;
-        s_win[lane] = idx <= n ? hit[idx] : ~0ull;
-        __syncthreads();
-        if (!found && s_win[63] > p) {
-            uint32_t c = 0;
-#pragma unroll
-            for (uint32_t st = 32; st; st >>= 1)
-                if (s_win[c + st - 1] <= p) c += st;
-            t = (uint32_t)(tw + c);
-            found = true;
-        }
-        __syncthreads();
-        const uint64_t left = __ballot(!found);
-        if (!left) break;
-        // a run of empty topics longer than the window: search again for the first lane left
-        const uint32_t fl = (uint32_t)__builtin_ctzll(left);
-        tw = fo_topic_at(hit, n, p0 + fl, tw + 65, lane);
-    }
-    const uint32_t last = c1 - p0 < 64 ? (uint32_t)(c1 - p0) - 1 : 63u;
-    tcur = __shfl(t, last, 64);
-    return t;
-}
+// (fo_topic_at and fo_step_topics, the search for the topic of a position: tm_dev.h,
+// shared with tm_dispatch.hip)
 
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
 #pragma unroll

@@ -31,6 +31,7 @@
 
 #include "../../include/tmatch.h"
 #include "tm_dev.h"
+#include "tm_subs.h"
 #include "tm_layout.h"
 
 using namespace tmx;
@@ -130,6 +131,8 @@ struct Lane {
     uint32_t *d_at = nullptr, *d_av = nullptr; uint64_t d_at_cap = 0, d_av_cap = 0;
     uint64_t *d_ao = nullptr; uint64_t d_ao_cap = 0;
     uint32_t *fo1_s = nullptr;
+    // tm_dispatch_batch: the local bucket's deliveries (topic, value, subscriber)
+    uint32_t *d_dt = nullptr, *d_dv = nullptr, *d_ds = nullptr; uint64_t d_dt_cap = 0, d_dv_cap = 0, d_ds_cap = 0;
 };
 
 // Patch log: a ring of the last PATCH_RING patches (numbered 1, 2, ... in the
@@ -284,6 +287,12 @@ struct tm_index {
     // destinations are, under the same lock (table_upload)
     std::vector<uint32_t> filt_h;
     DestDev filt[MAX_REPLICAS];
+    // value -> local subscriber list (tm_set_subscribers): the pool and the
+    // spans of tm_subs.h, each kept on the device as the two tables above are,
+    // under the same lock; a dispatch takes both in one hold of it, the pool
+    // first (subs_upload)
+    SubPool subs_h;
+    DestDev sub_pool[MAX_REPLICAS], sub_span[MAX_REPLICAS];
 
     // caller buffers from tm_host_alloc (host address -> size, device address;
     // vram: TM_ALLOC_VRAM device memory, the same address on both sides)
@@ -1786,7 +1795,8 @@ void free_workspace(Workspace &w) {
 void free_lane(Lane &l) {
     free_workspace(l.w);
     void *dv[] = {l.d_in, l.d_res, l.d_vals, l.d_o64, l.d_h64, l.f.tab, l.f.tot, l.f.t, l.f.v, l.f.b, l.f.voff, l.f.sums, l.f.b2,
-                  l.d_ft, l.d_fv, l.d_fo, l.d_pr, l.f.ag_bits, l.f.ag_pre, l.f.ag_cnt, l.d_at, l.d_av, l.d_ao, l.fo1_s};
+                  l.d_ft, l.d_fv, l.d_fo, l.d_pr, l.f.ag_bits, l.f.ag_pre, l.f.ag_cnt, l.d_at, l.d_av, l.d_ao, l.fo1_s,
+                  l.f.dp_cnt, l.f.dp_off, l.f.dp_tot, l.d_dt, l.d_dv, l.d_ds};
     for (void *p : dv) if (p) (void)hipFree(p);
     void *pins[] = {l.pin_in, l.pin_out, l.pin_vals, l.fo1_h};
     for (void *p : pins) if (p) (void)hipHostFree(p);
@@ -2130,7 +2140,7 @@ struct HostBatch {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 15u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 16u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 
@@ -2245,7 +2255,7 @@ int tm_destroy(tm_index *ix) {
     for (int g = 0; g < ix->ngroups; g++) {
         for (int r = 0; r < ix->nrep; r++)
             if (ix->rep[r].group == g) { (void)hipSetDevice(ix->rep[r].device); break; }
-        for (auto *D : {&ix->dest[g], &ix->filt[g]}) {
+        for (auto *D : {&ix->dest[g], &ix->filt[g], &ix->sub_pool[g], &ix->sub_span[g]}) {
             if (D->d) (void)hipFree(D->d);
             if (D->pin) (void)hipHostFree(D->pin);
             if (D->ev) (void)hipEventDestroy(D->ev);
@@ -2568,9 +2578,8 @@ int ensure_fanout(tm_index *ix, Lane &ln, uint32_t n_dests, uint64_t cap, bool p
 // since the group's last upload go up through pinned staging, in stream
 // order, after the fan-outs of other streams that may still read them; a
 // fan-out on another stream waits for the upload's event.
-int table_upload(tm_index *ix, const std::vector<uint32_t> &host, tm_index::DestDev &D, int g, hipStream_t s,
-                 const uint32_t *&d, uint64_t &len) {
-    std::lock_guard<std::mutex> dg(ix->dst_mu);
+int table_upload_locked(tm_index *ix, const std::vector<uint32_t> &host, tm_index::DestDev &D, int g, hipStream_t s,
+                        const uint32_t *&d, uint64_t &len) {   // (caller holds ix->dst_mu)
     const uint64_t hl = host.size();
     if (!D.ev) HIPCHK(ix, hipEventCreateWithFlags(&D.ev, hipEventDisableTiming));
     if (D.ev_set && hipEventQuery(D.ev) == hipSuccess) D.ev_set = false;
@@ -2619,6 +2628,12 @@ int table_upload(tm_index *ix, const std::vector<uint32_t> &host, tm_index::Dest
     return TM_OK;
 }
 
+int table_upload(tm_index *ix, const std::vector<uint32_t> &host, tm_index::DestDev &D, int g, hipStream_t s,
+                 const uint32_t *&d, uint64_t &len) {
+    std::lock_guard<std::mutex> dg(ix->dst_mu);
+    return table_upload_locked(ix, host, D, g, s, d, len);
+}
+
 int dest_upload(tm_index *ix, int g, hipStream_t s, const uint32_t *&d, uint64_t &len) {
     return table_upload(ix, ix->dest_h, ix->dest[g], g, s, d, len);
 }
@@ -2626,6 +2641,56 @@ int dest_upload(tm_index *ix, int g, hipStream_t s, const uint32_t *&d, uint64_t
 // the same for the index's value -> filter id table (tm_set_route_filters)
 int filter_upload(tm_index *ix, int g, hipStream_t s, const uint32_t *&d, uint64_t &len) {
     return table_upload(ix, ix->filt_h, ix->filt[g], g, s, d, len);
+}
+
+// the index's subscriber table (tm_set_subscribers) on group g: the pool, then
+// the spans, in one hold of the lock -- a tm_set_subscribers between the two
+// would leave new spans over an old pool.  span_len in values.
+int subs_upload(tm_index *ix, int g, hipStream_t s, const uint32_t *&span, uint64_t &span_len, const uint32_t *&pool,
+                uint64_t &pool_len) {
+    std::lock_guard<std::mutex> dg(ix->dst_mu);
+    if (int rc = table_upload_locked(ix, ix->subs_h.pool, ix->sub_pool[g], g, s, pool, pool_len)) return rc;
+    if (int rc = table_upload_locked(ix, ix->subs_h.span, ix->sub_span[g], g, s, span, span_len)) return rc;
+    span_len /= 2;
+    return TM_OK;
+}
+
+// the dispatch's scratch on a lane (grow-only; freed with the lane): a count
+// per entry below cap, the offsets when the caller takes none, the chunk sums
+int ensure_dispatch(tm_index *ix, Lane &ln, uint64_t cap, bool offsets) {
+    FanoutScratch &f = ln.f;
+    if (!f.dp_tot && hipMalloc(&f.dp_tot, ((uint64_t)FO_GRID + 1) * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        f.dp_tot = nullptr;
+        return fail(ix, TM_ENOMEM, "dispatch: no device memory for the pass's chunk sums (32 KiB)");
+    }
+    if (!(cap <= f.dp_cap && f.dp_cnt)) {
+        HIPCHK(ix, hipStreamSynchronize(ln.s));   // only this lane's stream uses them
+        if (f.dp_cnt) (void)hipFree(f.dp_cnt);
+        f.dp_cnt = nullptr;
+        f.dp_cap = 0;
+        const uint64_t c = std::max<uint64_t>(std::min<uint64_t>(cap + cap / 4, 0xFFFFFFFFull), 4096);
+        if (hipMalloc(&f.dp_cnt, c * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            f.dp_cnt = nullptr;
+            return fail(ix, TM_ENOMEM, "dispatch: no device memory for the entries' list lengths (4 bytes x cap)");
+        }
+        f.dp_cap = c;
+    }
+    if (offsets && !(cap <= f.dp_off_cap && f.dp_off)) {
+        HIPCHK(ix, hipStreamSynchronize(ln.s));
+        if (f.dp_off) (void)hipFree(f.dp_off);
+        f.dp_off = nullptr;
+        f.dp_off_cap = 0;
+        const uint64_t c = std::max<uint64_t>(std::min<uint64_t>(cap + cap / 4, 0xFFFFFFFFull), 4096);
+        if (hipMalloc(&f.dp_off, (c + 1) * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            f.dp_off = nullptr;
+            return fail(ix, TM_ENOMEM, "dispatch: no device memory for the delivery offsets (8 bytes x (cap + 1))");
+        }
+        f.dp_off_cap = c;
+    }
+    return TM_OK;
 }
 
 // tm_set_dests / tm_set_route_filters: n entries into a host table and every
@@ -2709,6 +2774,70 @@ int tm_set_route_filters(tm_index *ix, uint64_t n, const uint32_t *values, const
     if (!n) return TM_OK;
     return table_set(ix, ix->filt_h, ix->filt, n, values, filter_ids,
                      "tm_set_route_filters: out of host memory (the table has one entry per value up to the largest)");
+}
+
+int tm_set_subscribers(tm_index *ix, uint64_t n, const uint32_t *values, const uint64_t *list_offsets,
+                       const uint32_t *subs) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_set_subscribers: null handle");
+    if (n && (!values || !list_offsets)) return fail(ix, TM_EINVAL, "tm_set_subscribers: null buffer");
+    if (!n) return TM_OK;
+    for (uint64_t i = 0; i < n; i++) {
+        if (list_offsets[i + 1] < list_offsets[i]) return fail(ix, TM_EINVAL, "tm_set_subscribers: decreasing offsets");
+        if (list_offsets[i + 1] - list_offsets[i] > 0xFFFFFFFFull)
+            return fail(ix, TM_EINVAL, "tm_set_subscribers: a list of more than 2^32 - 1 subscribers");
+    }
+    if (list_offsets[n] > list_offsets[0] && !subs) return fail(ix, TM_EINVAL, "tm_set_subscribers: null buffer");
+    std::lock_guard<std::mutex> dg(ix->dst_mu);
+    SubPool &sp = ix->subs_h;
+    bool ok = true;
+    try {
+        for (uint64_t i = 0; i < n && ok; i++)
+            ok = sp.set(values[i], subs + list_offsets[i], (uint32_t)(list_offsets[i + 1] - list_offsets[i]));
+    } catch (const std::bad_alloc &) {
+        ok = false;
+    }
+    // (what was written before a failure is written: the device copies follow it)
+    uint64_t slo, shi, plo, phi;
+    bool whole;
+    sp.take_dirty(slo, shi, plo, phi, whole);
+    for (int g = 0; g < ix->ngroups; g++) {
+        auto &S = ix->sub_span[g], &P = ix->sub_pool[g];
+        if (whole) {   // compacted: the pool may have shrunk under an older range
+            S.lo = P.lo = 0;
+            S.hi = sp.span.size();
+            P.hi = sp.pool.size();
+        } else {
+            SubPool::widen(S.lo, S.hi, slo, shi);
+            SubPool::widen(P.lo, P.hi, plo, phi);
+        }
+    }
+    if (!ok)
+        return fail(ix, TM_ENOMEM, "tm_set_subscribers: out of host memory (a span per value up to the largest, the "
+                                   "lists in a pool of at most 2^32 - 1 words)");
+    return TM_OK;
+}
+
+int tm_dispatch_dev(tm_index *ix, uint32_t n_dests, const uint64_t *dest_offs, uint32_t bucket, const uint32_t *topic,
+                    const uint32_t *value, uint64_t cap, const uint32_t *sub_span, uint64_t span_len,
+                    const uint32_t *sub_pool, uint64_t pool_len, uint64_t *out_head, uint64_t *out_offsets,
+                    uint32_t *out_topic, uint32_t *out_value, uint32_t *out_sub, uint64_t out_cap, void *stream) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_dispatch_dev: null handle");
+    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_dispatch_dev: n_dests must be 1 .. 65536");
+    if (bucket > n_dests) return fail(ix, TM_EINVAL, "tm_dispatch_dev: bucket must be 0 .. n_dests");
+    if (!dest_offs || !out_head || (cap && (!topic || !value)) || (out_cap && (!out_topic || !out_value || !out_sub)))
+        return fail(ix, TM_EINVAL, "tm_dispatch_dev: null buffer");
+    if (sub_span && !sub_pool && pool_len) return fail(ix, TM_EINVAL, "tm_dispatch_dev: d_sub_span without d_sub_pool");
+    if ((uintptr_t)sub_span & 7) return fail(ix, TM_EINVAL, "tm_dispatch_dev: d_sub_span must be 8-byte aligned");
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
+    if (out_cap > 0xFFFFFFFFull) out_cap = 0xFFFFFFFFull;
+    DevBatch b(ix, stream);
+    int rc;
+    if ((rc = b.open_fanout())) return rc;
+    if ((rc = ensure_dispatch(ix, *b.ln, cap, !out_offsets))) return rc;
+    if (!sub_span && (rc = subs_upload(ix, b.grp, b.s, sub_span, span_len, sub_pool, pool_len))) return rc;
+    HIPCHK(ix, launch_dispatch(b.ln->f, n_dests, dest_offs, bucket, topic, value, cap, sub_span, span_len, sub_pool,
+                               pool_len, out_head, out_offsets, out_topic, out_value, out_sub, out_cap, b.s));
+    return b.done();
 }
 
 int tm_aggre_dev(tm_index *ix, uint32_t n_dests, const uint64_t *dest_offs, const uint32_t *topic, const uint32_t *value,
@@ -3295,6 +3424,41 @@ static int queue_grid_fanout(tm_index *ix, Lane &ln, uint64_t n, const uint64_t 
     return TM_OK;
 }
 
+// tm_dispatch_batch's dispatch half: which bucket, the caller's outputs, and
+// where on the device the head words land (with the batch's results)
+struct RouteDispatch {
+    uint32_t local_dest;
+    uint64_t *out_head;
+    uint32_t *out_topic, *out_value, *out_sub;
+    uint64_t dcap;
+};
+
+// queues the dispatch of bucket `bucket` of the lane's fan-out results (d_fo /
+// d_ft / d_fv, under aggre d_ao / d_at / d_av) with the index's own subscriber
+// table into d_dt / d_dv / d_ds, at most out_cap deliveries; head = [M, T]
+// (caller holds ix->mu)
+static int queue_dispatch(tm_index *ix, Lane &ln, uint32_t n_dests, uint32_t bucket, bool aggre, uint64_t vcap,
+                          uint64_t out_cap, uint64_t *d_head) {
+    int rc;
+    const hipStream_t s = ln.s;
+    const uint32_t *span = nullptr, *pool = nullptr;
+    uint64_t span_len = 0, pool_len = 0;
+    if ((rc = subs_upload(ix, ix->rep[ln.r].group, s, span, span_len, pool, pool_len))) return rc;
+    HIPCHK(ix, launch_dispatch(ln.f, n_dests, aggre ? ln.d_ao : ln.d_fo, bucket, aggre ? ln.d_at : ln.d_ft,
+                               aggre ? ln.d_av : ln.d_fv, vcap, span, span_len, pool, pool_len, d_head, nullptr, ln.d_dt,
+                               ln.d_dv, ln.d_ds, out_cap, s));
+    return TM_OK;
+}
+
+// room for `want` deliveries on the lane
+static int dispatch_scratch(tm_index *ix, Lane &ln, uint64_t vcap, uint64_t want) {
+    int rc;
+    if ((rc = ensure_dispatch(ix, ln, vcap, true))) return rc;
+    if ((rc = grow_dev(ix, ln.s, ln.d_dt, ln.d_dt_cap, want))) return rc;
+    if ((rc = grow_dev(ix, ln.s, ln.d_dv, ln.d_dv_cap, want))) return rc;
+    return grow_dev(ix, ln.s, ln.d_ds, ln.d_ds_cap, want);
+}
+
 // The lane's fan-out results to the caller (the lock is not held; the lane is
 // still checked out: its buffers are this caller's).  `fo`: n_dests + 2 u64
 // the offsets land in -- the caller's own array, or narrowed into fo32.
@@ -3336,9 +3500,13 @@ static int copy_route_out(tm_index *ix, Lane &ln, uint32_t n_dests, uint64_t tot
 // complete whatever `cap` is; cap only bounds what is copied out.
 // TM_ROUTE_AGGRE: the aggre pass runs on the fan-out's results in the lane's
 // scratch, and only the kept entries are copied back.
-int tm_route_batch_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
-                      uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
-                      uint8_t *out_err, uint32_t flags) {
+// dp (tm_dispatch_batch): in the same run, on the same lane, the dispatch of
+// bucket dp->local_dest over the results; the lane's delivery scratch grows
+// from the T that comes back with the results, and then only the dispatch
+// kernels are queued again.
+static int route_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
+                            uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                            uint8_t *out_err, uint32_t flags, const RouteDispatch *dp) {
     if (!ix) return fail(nullptr, TM_EINVAL, "tm_route_batch: null handle");
     if (flags & ~(uint32_t)TM_ROUTE_AGGRE) return fail(ix, TM_EINVAL, "tm_route_batch: unknown flag");
     const bool aggre = flags & TM_ROUTE_AGGRE;
@@ -3355,16 +3523,22 @@ int tm_route_batch_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_
     const uint8_t *dbytes;
     const uint64_t *doffs;
     if ((rc = stage_in(ix, ln, n, tb, to, nullptr, dbytes, doffs))) return rc;
-    const uint64_t rbytes = (n + 1) * 8 + n;   // hit offsets, then the err flags
+    // hit offsets, then the err flags; with a dispatch its two head words after them
+    const uint64_t hoff = ((n + 1) * 8 + n + 7) & ~7ull;
+    const uint64_t rbytes = dp ? hoff + 16 : (n + 1) * 8 + n;
     uint8_t *dres;
     if ((rc = stage_out(ix, ln, n, rbytes, dres))) return rc;
     uint64_t *dhit = reinterpret_cast<uint64_t *>(dres);
     uint8_t *derr = dres + (n + 1) * 8;
+    uint64_t *dhead = reinterpret_cast<uint64_t *>(dres + hoff);
+    const uint64_t dcap = dp ? std::min<uint64_t>(dp->dcap, 0xFFFFFFFFull) : 0;
     uint64_t total = 0, vcap = std::max<uint64_t>({ln.d_vals_cap, 4 * n, 1 << 16});
+    uint64_t dwant = dp ? std::max<uint64_t>(ln.d_ds_cap, 1 << 16) : 0;   // deliveries the lane has room for
     for (int attempt = 0;; attempt++) {
         if (vcap > 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch: more than 2^32 - 1 hits in one batch");
         if ((rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, vcap))) return rc;
         if ((rc = route_scratch(ix, ln, n_dests, vcap, aggre, false, 0))) return rc;
+        if (dp && (rc = dispatch_scratch(ix, ln, vcap, dwant))) return rc;
         rc = hb.run([&](const DevIndex &d, uint32_t tag) -> int {
             int path = PATH_PHASES;
             HIPCHK(ix, launch_match(d, ln.w, n, dbytes, doffs, dhit, derr, ln.d_vals, vcap, tag, next_lb(ix),
@@ -3372,6 +3546,9 @@ int tm_route_batch_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_
             ix->path_batches[path]++;
             // (aggre before the total is known: no second wait when it fits)
             if (int rc = queue_grid_fanout(ix, ln, n, dhit, nullptr, vcap, n_dests, aggre)) return rc;
+            if (dp)
+                if (int rc = queue_dispatch(ix, ln, n_dests, dp->local_dest, aggre, vcap, std::min(dwant, dcap), dhead))
+                    return rc;
             return fetch_out(ix, ln, n, rbytes);
         });
         if (rc) return rc;
@@ -3381,11 +3558,59 @@ int tm_route_batch_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_
         vcap = total + total / 4;
         if ((rc = hb.relock())) return rc;
     }
+    uint64_t head[2] = {0, 0};
+    if (dp) {
+        std::memcpy(head, ln.pin_out + hoff, 16);
+        for (int attempt = 0; std::min(head[1], dcap) > dwant; attempt++) {
+            // more deliveries than the lane had room for: the scratch grows and the
+            // dispatch alone runs again on the results still in the lane (no walk)
+            if (attempt >= 2) return fail(ix, TM_EDEVICE, "tm_dispatch_batch: the delivery total kept growing past the scratch");
+            dwant = std::min(head[1] + head[1] / 4, dcap);
+            if ((rc = hb.relock())) return rc;
+            if ((rc = dispatch_scratch(ix, ln, vcap, dwant))) return rc;
+            if ((rc = queue_dispatch(ix, ln, n_dests, dp->local_dest, aggre, vcap, dwant, dhead))) return rc;
+            if (n > ZC_TOPICS) HIPCHK(ix, hipMemcpyAsync(ln.pin_out + hoff, dhead, 16, hipMemcpyDeviceToHost, s));
+            if ((rc = batch_done(ix, ln))) return rc;
+            hb.g.unlock();
+            HIPCHK(ix, hipStreamSynchronize(s));
+            std::memcpy(head, ln.pin_out + hoff, 16);
+        }
+    }
     rc = copy_route_out(ix, ln, n_dests, total, cap, aggre, aggre && total <= cap, out_dest_offsets, nullptr, out_topic,
                         out_values);
     if (rc != TM_OK && rc != TM_ECAP) return rc;
     if (out_err && n) std::memcpy(out_err, ln.pin_out + (n + 1) * 8, n);
+    if (dp) {
+        dp->out_head[0] = head[0];
+        dp->out_head[1] = head[1];
+        const uint64_t keep = std::min(head[1], dcap);
+        if (keep) {
+            HIPCHK(ix, hipMemcpyAsync(dp->out_topic, ln.d_dt, keep * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipMemcpyAsync(dp->out_value, ln.d_dv, keep * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipMemcpyAsync(dp->out_sub, ln.d_ds, keep * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipStreamSynchronize(s));
+        }
+        if (head[1] > dp->dcap) rc = TM_ECAP;
+    }
     return rc;
+}
+
+int tm_route_batch_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
+                      uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                      uint8_t *out_err, uint32_t flags) {
+    return route_batch_impl(ix, n, tb, to, n_dests, out_dest_offsets, out_topic, out_values, cap, out_err, flags, nullptr);
+}
+
+int tm_dispatch_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
+                      uint32_t local_dest, uint32_t flags, uint64_t *out_dest_offsets, uint32_t *out_topic,
+                      uint32_t *out_values, uint64_t cap, uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue,
+                      uint32_t *out_dsub, uint64_t dcap, uint8_t *out_err) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_dispatch_batch: null handle");
+    if (n_dests && local_dest >= n_dests) return fail(ix, TM_EINVAL, "tm_dispatch_batch: local_dest must be below n_dests");
+    if (!out_head || (dcap && (!out_dtopic || !out_dvalue || !out_dsub)))
+        return fail(ix, TM_EINVAL, "tm_dispatch_batch: null buffer");
+    const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
+    return route_batch_impl(ix, n, tb, to, n_dests, out_dest_offsets, out_topic, out_values, cap, out_err, flags, &dp);
 }
 
 int tm_route_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
@@ -3823,6 +4048,11 @@ int tm_debug_get(tm_index *ix, uint32_t key, uint64_t *value) {
     case TM_DEBUG_FANOUT_GRID: *value = FO_GRID; break;
     case TM_DEBUG_ROUTE_ONE: *value = ix->route_one.load(); break;
     case TM_DEBUG_ROUTE_GRID: *value = ix->route_grid.load(); break;
+    case TM_DEBUG_SUB_COMPACTIONS: {
+        std::lock_guard<std::mutex> dg(ix->dst_mu);
+        *value = ix->subs_h.compactions;
+        break;
+    }
     case TM_DEBUG_COMMIT_WAITS: *value = ix->commit_waits.load(); break;
     case TM_DEBUG_COMMIT_FORCED: *value = ix->commit_forced.load(); break;
     case TM_DEBUG_COMBINED_LAUNCHES: *value = ix->cmb_launches.load(); break;

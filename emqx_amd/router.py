@@ -142,11 +142,17 @@ class MirrorDown(RuntimeError):
 
 class Router:
     def __init__(self, node="node", device: int = -1, mirror=None, mirror_factory=None,
-                 route_in_place: bool = False):
+                 route_in_place: bool = False, local_subs=None):
         """route_in_place: match_routes_by_dest goes through the mirror's
         route_kids32 (tm_route_batch32 on pooled pinned buffers: a micro-batch
-        is matched and fanned out in place) instead of route_kids."""
+        is matched and fanned out in place) instead of route_kids.
+        local_subs: this node's subscribers.LocalSubs; the device list of every
+        route key {Filter, node()} then follows it (tm_set_subscribers), for
+        match_routes_dispatch."""
         self.node = node
+        self.local_subs = local_subs
+        if local_subs is not None:
+            local_subs.on_change = self._subs_changed
         self._route_in_place = route_in_place
         self._bag: dict[bytes, dict] = {}        # emqx_route: Topic -> {Dest: seq} (insertion order)
         self._seq = 0
@@ -245,7 +251,29 @@ class Router:
                 self._filter_ids, self._filter_live = {}, set()
             mirror.filter_fn = self.filter_id
             mirror.filter_release = self.filter_release
+        if hasattr(mirror, "sub_fn") and self.local_subs is not None:
+            mirror.sub_fn = self._key_subs
         return mirror
+
+    # ------------------------------------------------------ local subscribers
+    def _key_subs(self, key):
+        """The device list of a route key: for {Filter, node()} the ids of the
+        pids do_dispatch2/2 visits for Filter on this node; nothing for a route
+        to another destination."""
+        if ti.get_id(key) != self.node:
+            return ()
+        return self.local_subs.dispatch_ids(ti.get_topic(key))
+
+    def _subs_changed(self, topic):
+        """LocalSubs' hook: a wildcard topic's rows changed -- the list of the
+        key {Filter, node()} follows, if the mirror holds the key (else the
+        mirror asks _key_subs when it inserts it).  An exact topic's rows stay
+        on the host, as its route does."""
+        words = tfilter(bytes(topic))
+        if words is False or not self._alive or not hasattr(self._mirror, "set_subscribers"):
+            return
+        key = make_key(words, self.node)
+        self._mirror.set_subscribers(key, self._key_subs(key))
 
     # ------------------------------------------------------- filter interning
     def filter_id(self, key) -> int:
@@ -513,17 +541,53 @@ class Router:
         the same rule here, per class, when they are resolved.  The bag's rows
         are as without it; .host_rows names their positions, for a caller that
         still has to deduplicate them (Broker.publish_batch_by_dest)."""
+        return self._routes_by_dest(topics, errors, aggre, False)[0]
+
+    def match_routes_dispatch(self, topics, errors: str = "raise", aggre: bool = False):
+        """match_routes_by_dest plus the local dispatch, in one device call
+        (tm_dispatch_batch) -> (ByDest, deliveries): deliveries = [(message
+        index, To, subscriber pid)], what do_route2/2's dispatch/2 ->
+        do_dispatch2/2 (emqx_broker.erl:726-760) sends on this node, one
+        {deliver, To, Msg} each.  In message order; inside a message the Tos in
+        the order match_routes_batch lists the routes (the bag's exact-topic
+        row first, expanded here from local_subs, then the filter matches, from
+        the device); per (message, To) the pids in local_subs.dispatch_order.
+        Needs local_subs."""
+        if self.local_subs is None:
+            raise ValueError("match_routes_dispatch: the router has no local_subs")
+        return self._routes_by_dest(topics, errors, aggre, True)
+
+    def _routes_by_dest(self, topics, errors, aggre, dispatch):
         topics = [bytes(t) for t in topics]
         mirror = self._live_mirror()
         out = ByDest()
+        deliveries: list = []
+        dev_del: dict = {}   # message index -> [[To, [pid]]] in entry (traversal) order
         groups: dict = {}    # class -> {message index: [Route]}
+        local = self.dest_id(self.node) if dispatch else None
         ticket = mirror.read_begin()
         try:
             with self._dest_lock:
                 classes = list(self._dest_classes)
             n_dests = max(len(classes), 1)
-            route = mirror.route_kids32 if self._route_in_place else mirror.route_kids
-            doff, tidx, kids, err = route(topics, n_dests, aggre=True) if aggre else route(topics, n_dests)
+            if dispatch:
+                if local == UNROUTED:
+                    raise ValueError("match_routes_dispatch: this node has no destination id")
+                (doff, tidx, kids, err), (dt, dk, ds) = mirror.dispatch_kids(topics, n_dests, local, aggre=aggre)
+                last = None
+                for j, (i, kid, sub) in enumerate(zip(dt.tolist(), dk.tolist(), ds.tolist())):
+                    if last != (i, kid):
+                        last = (i, kid)
+                        k = mirror.decode(dk[j:j + 1])
+                        cur = None
+                        if k:   # (a key deleted since the batch began is dropped, as decode drops it)
+                            cur = [ti.get_topic(k[0]), []]
+                            dev_del.setdefault(i, []).append(cur)
+                    if cur is not None:
+                        cur[1].append(self.local_subs.pid_of(sub))
+            else:
+                route = mirror.route_kids32 if self._route_in_place else mirror.route_kids
+                doff, tidx, kids, err = route(topics, n_dests, aggre=True) if aggre else route(topics, n_dests)
             if len(err) and (err == 4).any():   # (the library returns TM_EDEVICE instead; never a client error)
                 raise ti.DeviceError(-3, "batch failed on the device (err flag 4)")
             for i in map(int, err.nonzero()[0]):
@@ -575,7 +639,16 @@ class Router:
                 rows.extend((i, Route(ti.get_topic(k), ti.get_id(k))) for k in ti.traversal_order(list(keys))[::-1])
             if rows:
                 out[cls] = rows
-        return out
+        if dispatch:
+            for i, t in enumerate(topics):
+                if i in out.errors:
+                    continue
+                if self.node in self._bag.get(t, ()):   # the bag's row {Topic, node()}: first
+                    deliveries.extend((i, t, p) for p in self.local_subs.dispatch_order(t))
+                # matches/3's order: the reverse of the traversal
+                for to, pids in reversed(dev_del.get(i, ())):
+                    deliveries.extend((i, to, p) for p in pids)
+        return out, deliveries
 
     def topics(self):
         """topics/0 = list_topics_v2 (emqx_router.erl:627-630): the bag's topics,

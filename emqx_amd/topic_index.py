@@ -74,6 +74,12 @@ class Tab:
         self.filter_fn = None
         self.filter_release = None
         self._filts: list = []          # pending (kid, filter id)
+        # local dispatch on the device: sub_fn(key) -> the u32 subscriber ids of the key's
+        # value in dispatch order, shipped with tm_set_subscribers in the same flush, ahead
+        # of the insert; set_subscribers(key, ids) for later changes
+        self.sub_fn = None
+        self._subs: list = []           # pending (kid, [subscriber ids])
+        self._with_subs: set = set()    # kids whose device list is not empty
         self._route_pool: list = []     # route_kids32: idle sets of pinned batch buffers (host_array)
 
     # -- key <-> device encoding
@@ -122,6 +128,9 @@ class Tab:
             f = np.array(self._filts, dtype=np.uint32).reshape(-1, 2)
             self._filts = []
             self._index.set_route_filters(f[:, 0], f[:, 1])
+        if self._subs:
+            subs, self._subs = self._subs, []
+            self._index.set_subscribers([k for k, _ in subs], [ids for _, ids in subs])
         if not self._ops:
             return
         ops = np.array([o[0] for o in self._ops], dtype=np.uint8)
@@ -166,6 +175,8 @@ class Tab:
                 self._dests.append((kid, self.dest_fn(key)))
             if self.filter_fn is not None:
                 self._filts.append((kid, self.filter_fn(key)))
+            if self.sub_fn is not None:
+                self._set_subs_locked(kid, self.sub_fn(key))
             self._queue(_native.TM_OP_INSERT, key, kid)
         self._records[key] = record
 
@@ -177,8 +188,25 @@ class Tab:
             self._queue(_native.TM_OP_DELETE, key, kid)
             self._keys[kid] = None
             self._released.append(kid)
+            self._set_subs_locked(kid, ())   # the key's list goes with it
             if self.filter_release is not None:
                 self.filter_release(key)
+
+    def _set_subs_locked(self, kid, sub_ids):
+        ids = [int(x) for x in sub_ids]
+        if not ids and kid not in self._with_subs:
+            return   # (empty is what the device holds for it)
+        (self._with_subs.add if ids else self._with_subs.discard)(kid)
+        self._subs.append((kid, ids))
+
+    def set_subscribers(self, key, sub_ids):
+        """The local subscriber list of `key`'s value becomes sub_ids (u32s, in
+        dispatch order), shipped with tm_set_subscribers at the next flush.  A
+        key not in the table: nothing to do (sub_fn is asked when it is inserted)."""
+        with self._lock:
+            kid = self._kid.get(key)
+            if kid is not None:
+                self._set_subs_locked(kid, sub_ids)
 
     def attach(self, rows, batch_size: int = 1000) -> int:
         """Boot the device mirror from an existing table (emqx_topic_index_gpu:
@@ -233,6 +261,15 @@ class Tab:
         self.flush()
         blob, offs = _native.pack_strings(topics)
         return self._index.route_batch(blob, offs, n_dests, aggre=aggre)
+
+    def dispatch_kids(self, topics, n_dests: int, local_dest: int, aggre: bool = False):
+        """tm_dispatch_batch -> (route_kids' result, (topic index u32[T], kid u32[T],
+        subscriber id u32[T])): the buckets, and bucket local_dest expanded to one
+        delivery per subscriber of each entry's kid, in entry order and list
+        order (the lists of sub_fn / set_subscribers)."""
+        self.flush()
+        blob, offs = _native.pack_strings(topics)
+        return self._index.dispatch_batch(blob, offs, n_dests, local_dest, aggre=aggre)
 
     def _route_set(self, n: int, nbytes: int, n_dests: int, cap: int) -> dict:
         """A set of pinned buffers (host_array) large enough for the batch, from

@@ -558,6 +558,92 @@ int tm_route_batch32_ex(tm_index *h, uint64_t n, const uint8_t *topic_bytes, con
                         uint32_t n_dests, uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
                         uint64_t cap, uint8_t *out_err, uint32_t flags);
 
+/* Local dispatch on the device (ABI minor 16): route hits expanded to
+ * subscribers.  For a route on the local node do_route2/2 calls
+ * emqx_broker:dispatch/2, and do_dispatch2/2 (emqx_broker.erl:726-760) looks
+ * (message, To) up in the ?SUBSCRIBER bag and sends {deliver, To, Msg} to every
+ * pid, shard rows {shard, I} expanded where they stand.  The calls above end
+ * with the local node's bucket of (message, route) entries; these turn it into
+ * the deliveries (message, route, subscriber).
+ *
+ * tm_set_subscribers: the index's value -> local subscriber list table, the
+ * twin of tm_set_dests / tm_set_route_filters (it replaces the ?SUBSCRIBER
+ * lookups of do_dispatch2/2).  For each i < n the list of route value
+ * values[i] becomes subs[list_offsets[i] .. list_offsets[i + 1]), in the order
+ * given -- the order do_dispatch2/2 visits, shard rows flattened by the caller.
+ * An empty range is "no subscribers"; a value never set has none; a value named
+ * twice in one call takes its last list.  Subscriber ids are the caller's
+ * opaque u32s (interned pids), every u32 is legal.  Thread safe with every
+ * other call; a dispatch queued after it returns sees the new lists (only the
+ * words changed since a device's last use are uploaded, the pool before the
+ * spans, in stream order before the dispatch and after the dispatches of other
+ * streams that may still read the old copy), one already queued sees the old
+ * or the new list of a value, never a mixture and never another value's words.
+ * Set a value's subscribers before inserting its key.  On the host: 8 bytes per
+ * value up to the largest one set, and the lists in a pool of power-of-two
+ * blocks (at most 2^32 - 1 words) that is rewritten tight when more of it is
+ * garbage than lists (TM_DEBUG_SUB_COMPACTIONS counts that).  TM_EINVAL before
+ * any work: a null handle, a null required buffer with n > 0, decreasing
+ * offsets, a list of more than 2^32 - 1 ids.  TM_ENOMEM as tm_set_dests.
+ *
+ * tm_dispatch_dev: device buffers, asynchronous on `stream`.  The input is what
+ * tm_fanout_dev* or tm_aggre_dev wrote; `bucket` in [0, n_dests] (the unrouted
+ * bucket is allowed), its bounds are read on the device.  d_sub_span[2 v],
+ * d_sub_span[2 v + 1] = the position and count of value v's list in d_sub_pool
+ * (span_len values, pool_len words; d_sub_span == NULL: the index's own table,
+ * the other three ignored; else it must be 8-byte aligned).  cap and out_cap
+ * are clamped to 2^32 - 1.  In numpy:
+ *   E = min(doff[n_dests+1], cap); q0 = min(doff[bucket], E); q1 = min(doff[bucket+1], E); M = q1 - q0
+ *   t, v = topic[q0:q1], value[q0:q1]
+ *   pos, cnt = span[2v], span[2v+1] where v < span_len, else 0, 0
+ *   cnt = 0 where pos + cnt > pool_len     (64-bit sum: a span outside the pool is empty, never read)
+ *   off = [0] + cumsum(cnt) as u64;  T = off[M]
+ *   src = repeat(arange(M), cnt);  r = arange(T) - off[src]
+ *   out_topic, out_value, out_sub = t[src], v[src], pool[pos[src] + r]    -- the first W = min(T, out_cap)
+ *   head = [M, T];  d_out_offsets[0..M] = off  (when given)
+ * Nothing at or past W is written in the three output arrays, nothing past
+ * d_out_offsets[M] and nothing past head[1]; the inputs are not modified; no
+ * input position >= E and no pool word >= pool_len is read.  T > out_cap: the
+ * caller reruns with room for T; head is exact either way.  The outputs MUST
+ * NOT overlap the inputs.  Four launches over the fan-out's fixed grid, no
+ * block waiting for another; the expansion shares out the OUTPUT positions, so
+ * a 10^5-subscriber list is written by many blocks.  The stream's scratch
+ * (kept with the fan-out's, tm_stream_release) holds 4 bytes x cap, 8 bytes x
+ * (cap + 1) more when d_out_offsets is NULL, and 32 KiB (TM_ENOMEM if that
+ * cannot be had).  It is sized from cap, not from the bucket, which only the
+ * device knows when the call is queued: pass the size of the buffers, never
+ * 2^32 - 1 for "no bound" -- that asks for about 50 GB a stream.
+ * TM_EINVAL before any device work: a null handle, a null required pointer,
+ * n_dests == 0 or n_dests > 65536, bucket > n_dests, d_sub_span given without
+ * d_sub_pool while pool_len > 0, d_sub_span not 8-byte aligned.
+ *
+ * tm_dispatch_batch: the host product path -- tm_route_batch_ex(.., flags)
+ * (flags 0 or TM_ROUTE_AGGRE; the index's own tables) followed, on the same
+ * lane and in the same run, by the dispatch of bucket local_dest over the
+ * fan-out's arrays (the aggre pass's under TM_ROUTE_AGGRE) with the index's
+ * own subscriber table.  The route outputs and their TM_ECAP rule are exactly
+ * tm_route_batch_ex's; out_head = [M, T] and the first min(T, dcap)
+ * deliveries (out_dtopic, out_dvalue, out_dsub) are copied out as well;
+ * TM_ECAP also when T > dcap, out_head[1] sizes the retry.  The lane's
+ * delivery scratch grows from the T fetched with the results and only the
+ * dispatch kernels are queued again: no second walk.  TM_EINVAL for
+ * local_dest >= n_dests, a null out_head, null delivery buffers with dcap > 0,
+ * and whatever tm_route_batch_ex refuses.  Lanes, read-your-writes, the
+ * device-failure retry and the out_err rules are unchanged. */
+int tm_set_subscribers(tm_index *h, uint64_t n, const uint32_t *values, const uint64_t *list_offsets,
+                       const uint32_t *subs);
+int tm_dispatch_dev(tm_index *h, uint32_t n_dests, const uint64_t *d_dest_offsets, uint32_t bucket,
+                    const uint32_t *d_topic, const uint32_t *d_value, uint64_t cap,
+                    const uint32_t *d_sub_span, uint64_t span_len, const uint32_t *d_sub_pool, uint64_t pool_len,
+                    uint64_t *d_out_head, uint64_t *d_out_offsets,
+                    uint32_t *d_out_topic, uint32_t *d_out_value, uint32_t *d_out_sub, uint64_t out_cap,
+                    void *stream);
+int tm_dispatch_batch(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint64_t *topic_offsets,
+                      uint32_t n_dests, uint32_t local_dest, uint32_t flags,
+                      uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                      uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
+                      uint64_t dcap, uint8_t *out_err);
+
 /* Release the batch scratch kept for `stream` (after its batches finish);
  * a caller that retires a stream calls this.  No reference counterpart. */
 int tm_stream_release(tm_index *h, void *stream);
@@ -657,7 +743,8 @@ int tm_profile_read(tm_index *h, double *walk_ms, double *batch_ms, uint64_t *ba
  * node annexed to that vocab-hint slot as depth << 32 | literal children, or
  * all ones while the slot is unused; TM_DEBUG_HINT_AUDIT (get only): vocab
  * entries whose hint of an annexed node differs from what that node's child
- * slot gives, in the host image (always 0). */
+ * slot gives, in the host image (always 0).  TM_DEBUG_SUB_COMPACTIONS (get
+ * only): how often tm_set_subscribers rewrote its pool tight. */
 enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES = 3, TM_DEBUG_PHASES = 4,
        TM_DEBUG_FAILED_BATCHES = 5, TM_DEBUG_RETRIED_BATCHES = 6, TM_DEBUG_PATH_PHASES = 7,
        TM_DEBUG_PATH_SMALL = 8, TM_DEBUG_PATH_LANE = 9, TM_DEBUG_SMALL_KERNEL = 10,
@@ -666,7 +753,7 @@ enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES =
        TM_DEBUG_COMMITS = 19, TM_DEBUG_COMMIT_WAITS = 20, TM_DEBUG_COMMIT_FORCED = 21, TM_DEBUG_SMALL_TICKET = 22,
        TM_DEBUG_CMB_SPIN = 23, TM_DEBUG_PATCH_ZC = 24, TM_DEBUG_FANOUT_GRID = 25,
        TM_DEBUG_ROUTE_ONE = 26, TM_DEBUG_ROUTE_GRID = 27, TM_DEBUG_ANNEX0 = 28, TM_DEBUG_ANNEX1 = 29,
-       TM_DEBUG_HINT_AUDIT = 30 };
+       TM_DEBUG_HINT_AUDIT = 30, TM_DEBUG_SUB_COMPACTIONS = 31 };
 int tm_debug_set(tm_index *h, uint32_t key, uint64_t value);
 int tm_debug_get(tm_index *h, uint32_t key, uint64_t *value);
 

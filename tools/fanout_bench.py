@@ -69,6 +69,19 @@ pairs were merged and what was dropped.  The call's median stands beside
 tm_fanout_dev_pairs' on the same entries, timed the same way.  With --small: a fourth leg, tm_route_batch32_ex with
 TM_ROUTE_AGGRE (the index's filter table: one id per distinct filter), its
 outputs compared with the numpy definition applied to (c)'s.
+
+--dispatch: local dispatch on the device (nothing of the first part runs).  The
+batch is matched as pairs and fanned out over 16 uniform destinations with
+tm_fanout_dev_pairs; bucket 0 (the local node) is then expanded with
+tm_dispatch_dev over two explicit subscriber tables -- uniform: 1 to 4
+subscribers per value; skewed: the same, plus 0.1 % of the values with 10,000
+-- against the torch composition on the same device arrays (gather the spans,
+cumsum, repeat_interleave, three gathers), outputs compared first (identical).
+tm_fanout_dev_pairs and tm_aggre_dev (filter_of[v] = v) are timed on the same
+entries in the same run.  One JSON line per table: both medians and spreads,
+deliveries/s, the algorithmic bytes (12 written + 4 read per delivery, 8 + 8 +
+12 per entry) per second, and the last line the skewed table's time per
+delivery over the uniform one's.
 """
 import argparse
 import json
@@ -360,6 +373,88 @@ def aggre_legs(torch, ix, a, s, n, d_blob, d_offs, d_err, total, most, nvals, fs
             assert h["p90_ms"] < t["p10_ms"], f"n_dests {n_dests} {name}: tm_aggre_dev is not clearly below the torch composition"
 
 
+def dispatch_legs(torch, ix, a, s, n, d_blob, d_offs, d_err, total, most, nvals, fs_len, n_dests=16):
+    """--dispatch: tm_dispatch_dev on the local bucket against the torch composition"""
+    dev = d_blob.device
+    cap_p = total + 4096 * most
+    d_pairs = torch.zeros(2 * n + 2, dtype=torch.int32, device=dev)
+    d_pv = torch.zeros(cap_p, dtype=torch.int32, device=dev)
+    ix.match_batch_dev_pairs(n, d_blob.data_ptr(), d_offs.data_ptr(), d_pairs.data_ptr(), d_pv.data_ptr(), cap_p,
+                             d_err.data_ptr(), s)
+    torch.cuda.synchronize()
+    assert int(d_pairs[2 * n]) & 0xFFFFFFFF == total and int(d_pairs[2 * n + 1]) & 0xFFFFFFFF <= cap_p
+    rng = np.random.default_rng(7)
+    dest_of = torch.from_numpy(rng.integers(0, n_dests, nvals, dtype=np.int64).astype(np.int32)).to(dev)
+    fof = torch.arange(nvals, dtype=torch.int32, device=dev)
+    fo, ag = ((torch.zeros(n_dests + 2, dtype=torch.int64, device=dev), torch.zeros(total, dtype=torch.int32, device=dev),
+               torch.zeros(total, dtype=torch.int32, device=dev)) for _ in range(2))
+
+    def fanout():
+        ix.fanout_dev_pairs(n, d_pairs.data_ptr(), d_pv.data_ptr(), cap_p, n_dests, fo[0].data_ptr(), fo[1].data_ptr(),
+                            fo[2].data_ptr(), dest_of.data_ptr(), nvals, s)
+
+    def aggre():
+        ix.aggre_dev(n_dests, fo[0].data_ptr(), fo[1].data_ptr(), fo[2].data_ptr(), total, ag[0].data_ptr(),
+                     ag[1].data_ptr(), ag[2].data_ptr(), fof.data_ptr(), nvals, s)
+
+    fanout()
+    torch.cuda.synchronize()
+    q0, q1 = int(fo[0][0]), int(fo[0][1])
+    M = q1 - q0
+    tf, ta = timed_pair(torch, fanout, aggre, a.warmup, a.reps)
+    beside = {"fanout_dev_pairs": stats(tf), "aggre_dev": stats(ta)}
+    per_delivery = {}
+    for name in ("uniform", "skewed"):
+        cnt = rng.integers(1, 5, nvals)
+        if name == "skewed":
+            cnt[rng.choice(nvals, max(nvals // 1000, 1), replace=False)] = 10_000
+        pos = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+        pool_len = int(cnt.sum())
+        assert pool_len < 1 << 31
+        span = torch.from_numpy(np.stack([pos, cnt], axis=1).astype(np.int32).reshape(-1)).to(dev)
+        pool = torch.from_numpy(rng.integers(0, 1 << 31, pool_len, dtype=np.int64).astype(np.int32)).to(dev)
+        span2 = span.view(nvals, 2)
+        T = int(span2[fo[2][q0:q1].long(), 1].sum())
+        head = torch.zeros(2, dtype=torch.int64, device=dev)
+        out = tuple(torch.zeros(T, dtype=torch.int32, device=dev) for _ in range(3))
+
+        def hip():
+            ix.dispatch_dev(n_dests, fo[0].data_ptr(), 0, fo[1].data_ptr(), fo[2].data_ptr(), total, head.data_ptr(),
+                            out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), T, d_sub_span=span.data_ptr(),
+                            span_len=nvals, d_sub_pool=pool.data_ptr(), pool_len=pool_len, stream=s)
+
+        def tor():
+            # (the bucket's bounds and T as host integers: no synchronisation inside the composition)
+            t, v = fo[1][q0:q1], fo[2][q0:q1]
+            sp = span2[v.long()]
+            c = sp[:, 1].long()
+            first = torch.cumsum(c, 0) - c
+            src = torch.repeat_interleave(torch.arange(M, device=dev), c, output_size=T)
+            at = sp[:, 0].long()[src] + (torch.arange(T, device=dev) - first[src])
+            return t[src], v[src], pool[at]
+
+        hip()
+        r = tor()
+        torch.cuda.synchronize()
+        assert head.tolist() == [M, T] and all(torch.equal(x, y) for x, y in zip(out, r)), f"{name}: the two paths differ"
+        del r
+        th, tt = timed_pair(torch, hip, tor, a.warmup, a.reps)
+        h, t = stats(th), stats(tt)
+        nbytes = 16 * T + 28 * M
+        per_delivery[name] = h["median_ms"] * 1e6 / T   # ns
+        print(json.dumps({"tool": "fanout_bench", "kind": "dispatch", "filters": fs_len, "topics": n, "entries": total,
+                          "n_dests": n_dests, "lists": name, "bucket_entries": M, "deliveries": T,
+                          "longest_list": int(cnt.max()), "pool_words": pool_len, "reps": a.reps, "hip": h, "torch": t,
+                          "torch_over_hip": round(t["median_ms"] / h["median_ms"], 2),
+                          "hip_deliveries_per_s": round(T / (h["median_ms"] * 1e-3), 1),
+                          "algorithmic_bytes": nbytes,
+                          "hip_algorithmic_GBps": round(nbytes / (h["median_ms"] * 1e-3) / 1e9, 1),
+                          "hip_ns_per_delivery": round(per_delivery[name], 4), **beside, "identical": True}), flush=True)
+    print(json.dumps({"tool": "fanout_bench", "kind": "dispatch_skew",
+                      "skewed_over_uniform_per_delivery": round(per_delivery["skewed"] / per_delivery["uniform"], 3)}),
+          flush=True)
+
+
 def _np_aggre(doff, t, v, fof, n_dests):
     """include/tmatch.h's numpy definition on a whole fan-out"""
     doff = doff.astype(np.int64)
@@ -479,6 +574,7 @@ def main():
     p.add_argument("--form", choices=["csr", "pairs", "both"], default="csr")
     p.add_argument("--small", action="store_true", help="the NIF's micro-batches, host to host (see above)")
     p.add_argument("--aggre", action="store_true", help="aggre/1 on the device (see above); with --small: a fourth leg")
+    p.add_argument("--dispatch", action="store_true", help="local dispatch on the device (see above)")
     p.add_argument("--sizes", type=int, nargs="+", default=None, help="--small: the batch sizes")
     a = p.parse_args()
     import torch
@@ -509,6 +605,9 @@ def main():
     nvals = int(fs.vals.max()) + 1
     assert int(d_vals[:total].max()) < nvals and int(d_vals[:total].min()) >= 0
     most = int((d_hit[1:] - d_hit[:-1]).max())
+    if a.dispatch:
+        dispatch_legs(torch, ix, a, s, n, d_blob, d_offs, d_err, total, most, nvals, len(fs))
+        return
     if a.aggre:
         aggre_legs(torch, ix, a, s, n, d_blob, d_offs, d_err, total, most, nvals, len(fs))
         return
