@@ -33,6 +33,10 @@ typedef struct tmn_set {         /* one caller's batch buffers (tm_host_alloc: t
     tmn_buf offs64;                              /* tm_first_batch's u64 offsets */
     tmn_buf rdoff, rtopic;                       /* tmn_route (tmatch_nif_route.h): bucket offsets, topic indices (u32) */
     uint32_t route_dests;                        /* n_dests of the set's last tmn_route */
+    tmn_buf dhead, dtopic, dvalue, dsub;         /* tmn_dispatch (tmatch_nif_dispatch.h): [M, T] (u64), the deliveries (u32);
+                                                    allocated by its first call only */
+    uint64_t deliveries;                         /* T of the set's last tmn_dispatch */
+    uint32_t dispatched;                         /* that call succeeded: tmn_deliveries has something to read */
     uint32_t in_flags;           /* the pool's input placement (tmn_pool.in_flags) */
     uint64_t reruns;             /* batches rerun after TM_ECAP (diagnostics) */
     struct tmn_set *next;

@@ -29,7 +29,8 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_match_batch32_dev", "tm_matches_filter_ex", "tm_host_alloc_ex", "tm_commit",
            "tm_match_batch32_pairs", "tm_match_batch_dev_pairs", "tm_set_dests", "tm_fanout_dev", "tm_route_batch",
            "tm_fanout_dev_pairs", "tm_route_batch32", "tm_set_route_filters", "tm_aggre_dev", "tm_route_batch_ex",
-           "tm_route_batch32_ex", "tm_set_subscribers", "tm_dispatch_dev", "tm_dispatch_batch")
+           "tm_route_batch32_ex", "tm_set_subscribers", "tm_dispatch_dev", "tm_dispatch_batch",
+           "tm_dispatch_batch32")
 TM_ALLOC_VRAM = 1
 TM_ROUTE_AGGRE = 1          # tm_route_batch_ex / tm_route_batch32_ex: aggre/1 applied to the buckets
 NO_FILTER = 0xFFFFFFFF      # tm_set_route_filters: no filter known (equal to nothing)
@@ -50,6 +51,9 @@ TM_DEBUG_ROUTE_ONE, TM_DEBUG_ROUTE_GRID = 26, 27   # (get only) route_batch32 ca
 # (get only) the node annexed to a vocab-hint slot (depth << 32 | children; all ones: none); hints that disagree (0)
 TM_DEBUG_ANNEX0, TM_DEBUG_ANNEX1, TM_DEBUG_HINT_AUDIT = 28, 29, 30
 TM_DEBUG_SUB_COMPACTIONS = 31   # (get only) rewrites of tm_set_subscribers' pool
+TM_DEBUG_DISPATCH_ONE, TM_DEBUG_DISPATCH_GRID = 32, 33   # (get only) dispatch_batch32 calls per finishing leg
+TM_DEBUG_DP1_MAX = 34   # deliveries the one-launch dispatch kernel expands itself (clamped to DP1_DELIVERIES)
+DP1_DELIVERIES = 32768
 MAX_DESTS = 65536           # tm_fanout_dev / tm_route_batch: n_dests is 1 .. MAX_DESTS
 
 
@@ -141,6 +145,7 @@ def load_library(path: Path | None = None):
         "tm_set_subscribers": (i32, [vp, u64, vp, vp, vp]),
         "tm_dispatch_dev": (i32, [vp, u32, vp, u32, vp, vp, u64, vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, vp]),
         "tm_dispatch_batch": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp]),
+        "tm_dispatch_batch32": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp]),
         "tm_debug_set": (i32, [vp, u32, u64]),
         "tm_debug_get": (i32, [vp, u32, C.POINTER(u64)]),
     }
@@ -579,6 +584,37 @@ class Index:
             total, T = int(doff[-1]), int(head[1])
             return (doff, topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T])
         raise TmError(TM_ECAP, "dispatch_batch: the totals kept growing")
+
+    def dispatch_batch32(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, local_dest: int, out,
+                         cap: int | None = None, dcap: int | None = None, aggre: bool = False):
+        """tm_dispatch_batch32: dispatch_batch with u32 topic offsets in and u32
+        bucket offsets out.  out = (dest_offsets u32[>= n_dests+2], topic
+        u32[cap], values u32[cap], err u8[>= n], head u64[2], dtopic u32[dcap],
+        dvalue u32[dcap], dsub u32[dcap]) -> ((dest_offsets[:n_dests+2],
+        topic[:total], values[:total], err[:n]), (dtopic[:T], dvalue[:T],
+        dsub[:T])) as views; in place (no staging, one synchronisation) when
+        every array comes from host_array() and the batch is a micro-batch
+        (include/tmatch.h).  cap / dcap: use only that many entries /
+        deliveries of the arrays (default: all).  Raises TmError(TM_ECAP) when
+        something does not fit: dest_offsets[n_dests+1] (before aggregation
+        under aggre) and head[1] size the retry."""
+        n = len(offs) - 1
+        doff, topic, vals, err, head, dt, dv, ds = out
+        if offs.dtype != np.uint32 or doff.dtype != np.uint32 or err.dtype != np.uint8 or head.dtype != np.uint64 \
+                or any(a.dtype != np.uint32 for a in (topic, vals, dt, dv, ds)) or len(doff) < n_dests + 2 \
+                or len(err) < n or len(head) < 2:
+            raise ValueError("dispatch_batch32: u32 offsets and large enough outputs of the right dtype expected")
+        if cap is None:
+            cap = min(len(topic), len(vals))
+        if dcap is None:
+            dcap = min(len(dt), len(dv), len(ds))
+        if cap > min(len(topic), len(vals)) or dcap > min(len(dt), len(dv), len(ds)):
+            raise ValueError("dispatch_batch32: cap / dcap exceeds the output arrays")
+        self._check(self._lib.tm_dispatch_batch32(self._h, n, _ptr(blob), _ptr(offs), n_dests, local_dest,
+                                                  TM_ROUTE_AGGRE if aggre else 0, _ptr(doff), _ptr(topic), _ptr(vals),
+                                                  cap, _ptr(head), _ptr(dt), _ptr(dv), _ptr(ds), dcap, _ptr(err)))
+        total, T = int(doff[n_dests + 1]), int(head[1])
+        return (doff[: n_dests + 2], topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T])
 
     def release_stream(self, stream: int | None):
         """Drop the batch scratch the library keeps for `stream`."""

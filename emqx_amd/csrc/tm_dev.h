@@ -360,6 +360,33 @@ hipError_t launch_dispatch(const FanoutScratch &fs, uint32_t n_dests, const uint
                            uint64_t span_len, const uint32_t *pool, uint64_t pool_len, uint64_t *head,
                            uint64_t *out_offsets, uint32_t *out_topic, uint32_t *out_value, uint32_t *out_sub,
                            uint64_t out_cap, hipStream_t s);
+// A micro-batch's route outputs and local dispatch in ONE launch of ONE
+// workgroup (k_dp_one; tm_dispatch_batch32), from what launch_fanout_one left in
+// device memory (fo_*: u32 offsets, the entries, its status words) and, when
+// ag_offsets is given, what launch_aggre_one made of it (ag_*; status_in is
+// that launch's then).  Writes the caller's route outputs as
+// tm_route_batch32_ex defines them (under aggre with more than `cap`
+// un-aggregated entries: the fan-out's offsets, no entry), out_head = [M, T]
+// of bucket `bucket` of the final arrays with the subscriber table given
+// (launch_dispatch's definition), and the first min(T, dcap) deliveries; every
+// output may be mapped host memory, none is read.  status[FO1_ST_STATE] =
+// FO1_DONE; DP1_TOO_LARGE when T > min(dp1_max, DP1_DELIVERIES): everything
+// but the deliveries is written, and the caller takes launch_dispatch on the
+// same arrays; a status_in that is not FO1_DONE is passed on and nothing else
+// is written.  status[FO1_ST_TOTAL] as launch_fanout_one;
+// status[DP1_ST_T_LO / _HI] = T.  span and out_head must be 8-byte aligned.
+// (DP1_DELIVERIES: where the one workgroup stops winning against the grid
+// kernels' second run, measured host to host: DESIGN.md 4e)
+constexpr uint64_t DP1_DELIVERIES = 32768;
+enum { DP1_ST_T_LO = FO1_ST_WORDS, DP1_ST_T_HI = FO1_ST_WORDS + 1, DP1_ST_WORDS = FO1_ST_WORDS + 2 };
+enum : uint32_t { DP1_TOO_LARGE = 3 };
+hipError_t launch_dispatch_one(const uint32_t *status_in, const uint32_t *fo_offsets, const uint32_t *fo_topic,
+                               const uint32_t *fo_value, const uint32_t *ag_offsets, const uint32_t *ag_topic,
+                               const uint32_t *ag_value, uint32_t n_dests, uint32_t bucket, const uint32_t *span,
+                               uint64_t span_len, const uint32_t *pool, uint64_t pool_len, uint32_t *out_dest_offsets,
+                               uint32_t *out_topic, uint32_t *out_value, uint64_t cap, uint64_t *out_head,
+                               uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub, uint64_t dcap,
+                               uint64_t dp1_max, uint32_t *status, hipStream_t s);
 // delta upload: run i copies runs[i].n u32 words from data + runs[i].src to
 // word (dst & PATCH_OFF) of table (dst >> 48), whose device address on the
 // replica being patched is bases.b[table] (the same runs patch every replica)

@@ -123,11 +123,13 @@ struct Lane {
     uint32_t *d_ft = nullptr, *d_fv = nullptr; uint64_t d_ft_cap = 0, d_fv_cap = 0;
     uint64_t *d_fo = nullptr; uint64_t d_fo_cap = 0;
     // tm_route_batch32 in place: the match's pairs (its values go to d_vals) and
-    // the one-launch fan-out's status words (mapped pinned, FO1_ST_WORDS)
+    // the one-launch kernels' status words (mapped pinned: DP1_ST_WORDS, then
+    // the [M, T] of a tm_dispatch_batch32 the grid kernels finished)
     uint32_t *d_pr = nullptr; uint64_t d_pr_cap = 0;
     uint32_t *fo1_h = nullptr, *fo1_d = nullptr;
     // TM_ROUTE_AGGRE: the aggregated device results of the grid kernels, and the
-    // one-launch fan-out's status words in device memory (k_ag_one passes them on)
+    // one-launch fan-out's status words in device memory (k_ag_one passes them
+    // on; under tm_dispatch_batch32 into a second pair, which k_dp_one reads)
     uint32_t *d_at = nullptr, *d_av = nullptr; uint64_t d_at_cap = 0, d_av_cap = 0;
     uint64_t *d_ao = nullptr; uint64_t d_ao_cap = 0;
     uint32_t *fo1_s = nullptr;
@@ -331,6 +333,9 @@ struct tm_index {
     std::atomic<uint64_t> path_batches[PATH_COUNT] = {};             // match launches per kernel path
     // tm_route_batch32 batches whose fan-out k_fo_one completed / that the grid kernels or the staged path finished
     std::atomic<uint64_t> route_one{0}, route_grid{0};
+    // tm_dispatch_batch32 calls k_dp_one completed / that the grid kernels or the staged path finished
+    std::atomic<uint64_t> dispatch_one{0}, dispatch_grid{0};
+    uint64_t dp1_max = DP1_DELIVERIES;   // TM_DEBUG_DP1_MAX: deliveries k_dp_one expands itself
     // The host-batch combiner (small_combined): small in-place 32-bit batches
     // of concurrent callers queue here; up to cmb_leaders callers at a time
     // each take what is queued and run it as ONE k_walk_small launch
@@ -2140,7 +2145,7 @@ struct HostBatch {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 16u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 17u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 
@@ -3436,18 +3441,25 @@ struct RouteDispatch {
 // queues the dispatch of bucket `bucket` of the lane's fan-out results (d_fo /
 // d_ft / d_fv, under aggre d_ao / d_at / d_av) with the index's own subscriber
 // table into d_dt / d_dv / d_ds, at most out_cap deliveries; head = [M, T]
-// (caller holds ix->mu)
-static int queue_dispatch(tm_index *ix, Lane &ln, uint32_t n_dests, uint32_t bucket, bool aggre, uint64_t vcap,
-                          uint64_t out_cap, uint64_t *d_head) {
+// (caller holds ix->mu).  queue_dispatch_to: the bucket offsets and the outputs
+// as given (tm_dispatch_batch32: the caller's own buffers).
+static int queue_dispatch_to(tm_index *ix, Lane &ln, uint32_t n_dests, uint32_t bucket, const uint64_t *doff,
+                             bool aggre, uint64_t vcap, uint64_t out_cap, uint64_t *d_head, uint32_t *dt, uint32_t *dv,
+                             uint32_t *ds) {
     int rc;
     const hipStream_t s = ln.s;
     const uint32_t *span = nullptr, *pool = nullptr;
     uint64_t span_len = 0, pool_len = 0;
     if ((rc = subs_upload(ix, ix->rep[ln.r].group, s, span, span_len, pool, pool_len))) return rc;
-    HIPCHK(ix, launch_dispatch(ln.f, n_dests, aggre ? ln.d_ao : ln.d_fo, bucket, aggre ? ln.d_at : ln.d_ft,
-                               aggre ? ln.d_av : ln.d_fv, vcap, span, span_len, pool, pool_len, d_head, nullptr, ln.d_dt,
-                               ln.d_dv, ln.d_ds, out_cap, s));
+    HIPCHK(ix, launch_dispatch(ln.f, n_dests, doff, bucket, aggre ? ln.d_at : ln.d_ft, aggre ? ln.d_av : ln.d_fv, vcap,
+                               span, span_len, pool, pool_len, d_head, nullptr, dt, dv, ds, out_cap, s));
     return TM_OK;
+}
+
+static int queue_dispatch(tm_index *ix, Lane &ln, uint32_t n_dests, uint32_t bucket, bool aggre, uint64_t vcap,
+                          uint64_t out_cap, uint64_t *d_head) {
+    return queue_dispatch_to(ix, ln, n_dests, bucket, aggre ? ln.d_ao : ln.d_fo, aggre, vcap, out_cap, d_head, ln.d_dt,
+                             ln.d_dv, ln.d_ds);
 }
 
 // room for `want` deliveries on the lane
@@ -3749,11 +3761,21 @@ int tm_match_batch32_pairs(tm_index *ix, uint64_t n, const uint8_t *tb, const ui
 // synchronisation, no copy.  ROUTE32_OTHER: the batch is not eligible (the
 // caller takes tm_route_batch).  A batch k_fo_one reports as too large is
 // finished here by launch_fanout_pairs on the pairs already matched.
+// dp (tm_dispatch_batch32): k_fo_one's results stay on the lane, as under
+// aggre, k_ag_one's too, and ONE more launch of one workgroup (k_dp_one) writes
+// the route outputs, the head and the deliveries into the caller's buffers --
+// still one synchronisation and no copy; the device never reads a caller's
+// output.  More than dp1_max deliveries (DP1_TOO_LARGE), or more entries than
+// k_fo_one takes: the grid kernels (launch_dispatch) run on the arrays already
+// on the lane and write the deliveries straight into the caller's buffers.
 constexpr int ROUTE32_OTHER = 1;   // (not a TM_ code)
+constexpr int DP1_GRID_HEAD = DP1_ST_WORDS;   // status word of the [M, T] a grid dispatch leaves (8-byte aligned)
+constexpr int DP1_HOST_WORDS = DP1_GRID_HEAD + 4;
+static_assert(DP1_GRID_HEAD % 2 == 0, "the grid dispatch's head is two u64");
 
 static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint64_t nbytes,
                             uint32_t n_dests, uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
-                            uint64_t cap, uint8_t *out_err, bool aggre) {
+                            uint64_t cap, uint8_t *out_err, bool aggre, const RouteDispatch *dp = nullptr) {
     HostBatch hb(ix);
     bool ok = tb || !nbytes;
     uint8_t *db = opt_dev(ix, tb, nbytes, ok);
@@ -3762,7 +3784,12 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     uint8_t *dt = opt_dev(ix, out_topic, cap * 4, ok);
     uint8_t *dv = opt_dev(ix, out_values, cap * 4, ok);
     uint8_t *de = pinned_dev(ix, out_err, n);   // (required even for no topics)
-    if (!ok || !de) return ROUTE32_OTHER;
+    const uint64_t dcap = dp ? std::min<uint64_t>(dp->dcap, 0xFFFFFFFFull) : 0;
+    uint64_t *dhd = dp ? reinterpret_cast<uint64_t *>(pinned_dev(ix, dp->out_head, 16)) : nullptr;
+    uint32_t *ddt = dp ? reinterpret_cast<uint32_t *>(opt_dev(ix, dp->out_topic, dcap * 4, ok)) : nullptr;
+    uint32_t *ddv = dp ? reinterpret_cast<uint32_t *>(opt_dev(ix, dp->out_value, dcap * 4, ok)) : nullptr;
+    uint32_t *dds = dp ? reinterpret_cast<uint32_t *>(opt_dev(ix, dp->out_sub, dcap * 4, ok)) : nullptr;
+    if (!ok || !de || (dp && !dhd)) return ROUTE32_OTHER;
     int rc;
     if ((rc = hb.open(n + (uint64_t)SMALL_SEGS * SM_TOPICS))) return rc;
     Lane &ln = *hb.ln;
@@ -3770,20 +3797,26 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     if (n && !small_path_ok(dev_view(ix, ln.r), n)) return ROUTE32_OTHER;
     ix->rep[ln.r].batches++;
     if (!ln.fo1_h) {
-        HIPCHK(ix, hipHostMalloc(&ln.fo1_h, FO1_ST_WORDS * 4, hipHostMallocMapped));
+        HIPCHK(ix, hipHostMalloc(&ln.fo1_h, DP1_HOST_WORDS * 4, hipHostMallocMapped));
         HIPCHK(ix, hipHostGetDevicePointer(reinterpret_cast<void **>(&ln.fo1_d), ln.fo1_h, 0));
     }
-    if (aggre && !ln.fo1_s) HIPCHK(ix, hipMalloc(&ln.fo1_s, FO1_ST_WORDS * 4));
+    if ((aggre || dp) && !ln.fo1_s) HIPCHK(ix, hipMalloc(&ln.fo1_s, 2 * FO1_ST_WORDS * 4));
     volatile uint32_t *st = ln.fo1_h;
+    uint64_t *ghead = reinterpret_cast<uint64_t *>(ln.fo1_d + DP1_GRID_HEAD);
     uint64_t total = 0, vcap = std::max<uint64_t>({ln.d_vals_cap, 4 * n, 1 << 16});
     for (int attempt = 0;; attempt++) {
         if (vcap > 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch32: more than 2^32 - 1 hits in one batch");
         if ((rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, vcap))) return rc;
         if ((rc = grow_dev(ix, s, ln.d_pr, ln.d_pr_cap, 2 * n + 2))) return rc;
-        if (aggre) {   // k_fo_one's results stay on the device: k_ag_one writes the caller's buffers
+        if (aggre || dp) {   // k_fo_one's results stay on the device: k_ag_one / k_dp_one writes the caller's buffers
             if ((rc = grow_dev(ix, s, ln.d_ft, ln.d_ft_cap, FO1_ENTRIES))) return rc;
             if ((rc = grow_dev(ix, s, ln.d_fv, ln.d_fv_cap, FO1_ENTRIES))) return rc;
             if ((rc = grow_dev(ix, s, ln.d_fo, ln.d_fo_cap, (uint64_t)n_dests + 2))) return rc;
+        }
+        if (aggre && dp) {   // and k_ag_one's
+            if ((rc = grow_dev(ix, s, ln.d_at, ln.d_at_cap, FO1_ENTRIES))) return rc;
+            if ((rc = grow_dev(ix, s, ln.d_av, ln.d_av_cap, FO1_ENTRIES))) return rc;
+            if ((rc = grow_dev(ix, s, ln.d_ao, ln.d_ao_cap, (uint64_t)n_dests + 2))) return rc;
         }
         rc = hb.run([&](const DevIndex &d, uint32_t tag) -> int {
             int rc;
@@ -3803,16 +3836,32 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
             st[FO1_ST_STATE] = 0;   // (the lane's stream is idle: nothing else writes the words)
             uint32_t *fo32 = reinterpret_cast<uint32_t *>(dfo), *t32 = reinterpret_cast<uint32_t *>(dt),
                      *v32 = reinterpret_cast<uint32_t *>(dv);
-            if (!aggre) {
+            if (!aggre && !dp) {
                 HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, fo32, t32, v32, cap, ln.fo1_d, s));
                 return TM_OK;
             }
-            if ((rc = filter_upload(ix, grp, s, ftab, flen))) return rc;
+            if (aggre && (rc = filter_upload(ix, grp, s, ftab, flen))) return rc;
             uint32_t *lfo = reinterpret_cast<uint32_t *>(ln.d_fo);
             HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, lfo, ln.d_ft, ln.d_fv,
                                          FO1_ENTRIES, ln.fo1_s, s));
-            HIPCHK(ix, launch_aggre_one(ln.fo1_s, lfo, n_dests, ln.d_ft, ln.d_fv, ftab, flen, fo32, t32, v32, cap,
-                                        ln.fo1_d, s));
+            if (!dp) {
+                HIPCHK(ix, launch_aggre_one(ln.fo1_s, lfo, n_dests, ln.d_ft, ln.d_fv, ftab, flen, fo32, t32, v32, cap,
+                                            ln.fo1_d, s));
+                return TM_OK;
+            }
+            uint32_t *lao = nullptr, *st_dev = ln.fo1_s;
+            if (aggre) {   // (room for every entry k_fo_one completes: the pass always compacts)
+                lao = reinterpret_cast<uint32_t *>(ln.d_ao);
+                st_dev = ln.fo1_s + FO1_ST_WORDS;
+                HIPCHK(ix, launch_aggre_one(ln.fo1_s, lfo, n_dests, ln.d_ft, ln.d_fv, ftab, flen, lao, ln.d_at, ln.d_av,
+                                            FO1_ENTRIES, st_dev, s));
+            }
+            const uint32_t *span = nullptr, *pool = nullptr;
+            uint64_t span_len = 0, pool_len = 0;
+            if ((rc = subs_upload(ix, grp, s, span, span_len, pool, pool_len))) return rc;
+            HIPCHK(ix, launch_dispatch_one(st_dev, lfo, ln.d_ft, ln.d_fv, lao, ln.d_at, ln.d_av, n_dests, dp->local_dest,
+                                           span, span_len, pool, pool_len, fo32, t32, v32, cap, dhd, ddt, ddv, dds, dcap,
+                                           ix->dp1_max, ln.fo1_d, s));
             return TM_OK;
         });
         if (rc) return rc;
@@ -3824,13 +3873,45 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     }
     const uint32_t state = st[FO1_ST_STATE];
     if (state == FO1_DONE) {
-        ix->route_one++;
-        return total > cap ? TM_ECAP : TM_OK;
+        if (!dp) {
+            ix->route_one++;
+            return total > cap ? TM_ECAP : TM_OK;
+        }
+        ix->dispatch_one++;
+        const uint64_t T = (uint64_t)st[DP1_ST_T_HI] << 32 | st[DP1_ST_T_LO];
+        return total > cap || T > dp->dcap ? TM_ECAP : TM_OK;
+    }
+    // the [M, T] a grid dispatch left with the lane's status words, to the caller
+    const auto grid_head = [&]() -> int {
+        const volatile uint64_t *gh = reinterpret_cast<const volatile uint64_t *>(ln.fo1_h + DP1_GRID_HEAD);
+        dp->out_head[0] = gh[0];
+        dp->out_head[1] = gh[1];
+        ix->dispatch_grid++;
+        return total > cap || gh[1] > dp->dcap ? TM_ECAP : TM_OK;
+    };
+    if (dp && state == DP1_TOO_LARGE) {
+        // more deliveries than one workgroup should write: the route outputs are
+        // in place; the grid kernels expand the bucket of the arrays on the lane
+        // (their u32 offsets widened beside them) into the caller's buffers
+        if ((rc = hb.relock())) return rc;
+        if ((rc = ensure_dispatch(ix, ln, FO1_ENTRIES, true))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_o64, ln.d_o64_cap, (uint64_t)n_dests + 2))) return rc;
+        HIPCHK(ix, launch_offs_widen(reinterpret_cast<const uint32_t *>(aggre ? ln.d_ao : ln.d_fo), ln.d_o64,
+                                     (uint64_t)n_dests + 2, s));
+        if ((rc = queue_dispatch_to(ix, ln, n_dests, dp->local_dest, ln.d_o64, aggre, FO1_ENTRIES, dcap, ghead, ddt, ddv,
+                                    dds)))
+            return rc;
+        if ((rc = batch_done(ix, ln))) return rc;
+        hb.g.unlock();
+        HIPCHK(ix, hipStreamSynchronize(s));
+        return grid_head();
     }
     if (state != FO1_TOO_LARGE) return fail(ix, TM_EDEVICE, "tm_route_batch32: the fan-out kernel left no status");
     // more entries than k_fo_one takes: the grid kernels on the same pairs (no
     // second walk), into the lane's scratch, copied out and narrowed
-    const bool ag = aggre && total <= cap;   // (else TM_ECAP: the un-aggregated sizes, no entries)
+    // (under aggre with total > cap: TM_ECAP, the un-aggregated sizes, no
+    // entries; a dispatch reads the aggregated arrays all the same)
+    const bool ag_out = aggre && total <= cap, ag = aggre && (dp || ag_out);
     std::vector<uint64_t> fo;
     try {
         fo.resize((uint64_t)n_dests + 2);
@@ -3839,11 +3920,19 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     }
     if ((rc = hb.relock())) return rc;
     if ((rc = route_scratch(ix, ln, n_dests, vcap, ag, true, n))) return rc;
+    if (dp && (rc = ensure_dispatch(ix, ln, vcap, true))) return rc;
     if ((rc = queue_grid_fanout(ix, ln, n, nullptr, ln.d_pr, vcap, n_dests, ag))) return rc;
+    if (dp) {
+        if ((rc = queue_dispatch_to(ix, ln, n_dests, dp->local_dest, ag ? ln.d_ao : ln.d_fo, ag, vcap, dcap, ghead, ddt,
+                                    ddv, dds)))
+            return rc;
+    }
     if ((rc = batch_done(ix, ln))) return rc;
     hb.g.unlock();
-    rc = copy_route_out(ix, ln, n_dests, total, cap, aggre, ag, fo.data(), out_dest_offsets, out_topic, out_values);
-    if (rc == TM_OK || rc == TM_ECAP) ix->route_grid++;
+    rc = copy_route_out(ix, ln, n_dests, total, cap, aggre, ag_out, fo.data(), out_dest_offsets, out_topic, out_values);
+    if (rc != TM_OK && rc != TM_ECAP) return rc;
+    if (dp) return grid_head();
+    ix->route_grid++;
     return rc;
 }
 
@@ -3884,6 +3973,47 @@ int tm_route_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t
                      uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
                      uint8_t *out_err) {
     return tm_route_batch32_ex(ix, n, tb, to, n_dests, out_dest_offsets, out_topic, out_values, cap, out_err, 0);
+}
+
+// tm_dispatch_batch with 32-bit offsets (include/tmatch.h): in place under
+// tm_route_batch32's conditions when the head and the delivery arrays lie in
+// tm_host_alloc memory too; every other batch widened, run by
+// tm_dispatch_batch, and narrowed.
+int tm_dispatch_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint32_t n_dests,
+                        uint32_t local_dest, uint32_t flags, uint32_t *out_dest_offsets, uint32_t *out_topic,
+                        uint32_t *out_values, uint64_t cap, uint64_t *out_head, uint32_t *out_dtopic,
+                        uint32_t *out_dvalue, uint32_t *out_dsub, uint64_t dcap, uint8_t *out_err) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_dispatch_batch32: null handle");
+    if (flags & ~(uint32_t)TM_ROUTE_AGGRE) return fail(ix, TM_EINVAL, "tm_dispatch_batch32: unknown flag");
+    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_dispatch_batch32: n_dests must be 1 .. 65536");
+    if (local_dest >= n_dests) return fail(ix, TM_EINVAL, "tm_dispatch_batch32: local_dest must be below n_dests");
+    if (!to || !out_dest_offsets || !out_err || (cap && (!out_topic || !out_values)) || !out_head ||
+        (dcap && (!out_dtopic || !out_dvalue || !out_dsub)))
+        return fail(ix, TM_EINVAL, "tm_dispatch_batch32: null buffer");
+    if ((uintptr_t)out_head & 7) return fail(ix, TM_EINVAL, "tm_dispatch_batch32: out_head must be 8-byte aligned");
+    if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_dispatch_batch32: batch too large");
+    const uint64_t nbytes = n ? to[n] : 0;   // (before the lock: in TM_ALLOC_VRAM memory a host read is a PCIe round trip)
+    if (n && !tb && nbytes != to[0]) return fail(ix, TM_EINVAL, "tm_dispatch_batch32: null buffer");
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
+    if (n <= FO1_TOPICS && n_dests <= FO1_MAX_DESTS && ((uintptr_t)tb & 15) == 0) {
+        const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
+        const int rc = route32_in_place(ix, n, tb, to, nbytes, n_dests, out_dest_offsets, out_topic, out_values, cap,
+                                        out_err, flags & TM_ROUTE_AGGRE, &dp);
+        if (rc != ROUTE32_OTHER) return rc;
+    }
+    static thread_local std::vector<uint64_t> o64, fo;
+    try {
+        o64.assign(to, to + n + 1);
+        fo.resize((uint64_t)n_dests + 2);
+    } catch (const std::bad_alloc &) {
+        return fail(ix, TM_ENOMEM, "tm_dispatch_batch32: out of host memory");
+    }
+    const int rc = tm_dispatch_batch(ix, n, tb, o64.data(), n_dests, local_dest, flags, fo.data(), out_topic, out_values,
+                                     cap, out_head, out_dtopic, out_dvalue, out_dsub, dcap, out_err);
+    if (rc != TM_OK && rc != TM_ECAP) return rc;
+    for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
+    ix->dispatch_grid++;
+    return rc;
 }
 
 int tm_match_batch32_dev(tm_index *ix, uint64_t n, const uint8_t *bytes, const uint32_t *offs, uint32_t *hit_offs,
@@ -4020,6 +4150,7 @@ int tm_debug_set(tm_index *ix, uint32_t key, uint64_t value) {
     case TM_DEBUG_CMB_SPIN: ix->cmb_spin_us = value > 1000 ? 1000 : (int)value; break;
     case TM_DEBUG_SMALL_TICKET: ix->small_ticket = value != 0; break;
     case TM_DEBUG_PATCH_ZC: ix->patch_zc = value != 0; break;
+    case TM_DEBUG_DP1_MAX: ix->dp1_max = std::min<uint64_t>(value, DP1_DELIVERIES); break;
     case TM_DEBUG_SMALL_KERNEL:
         if (value != SMALL_AUTO && value != SMALL_WAVE && value != SMALL_WAVE8)
             return fail(ix, TM_EINVAL, "tm_debug_set: TM_DEBUG_SMALL_KERNEL is 0, 1 or 3 (2, the lane kernel, was removed)");
@@ -4048,6 +4179,13 @@ int tm_debug_get(tm_index *ix, uint32_t key, uint64_t *value) {
     case TM_DEBUG_FANOUT_GRID: *value = FO_GRID; break;
     case TM_DEBUG_ROUTE_ONE: *value = ix->route_one.load(); break;
     case TM_DEBUG_ROUTE_GRID: *value = ix->route_grid.load(); break;
+    case TM_DEBUG_DISPATCH_ONE: *value = ix->dispatch_one.load(); break;
+    case TM_DEBUG_DISPATCH_GRID: *value = ix->dispatch_grid.load(); break;
+    case TM_DEBUG_DP1_MAX: {
+        std::lock_guard<std::mutex> g(ix->mu);
+        *value = ix->dp1_max;
+        break;
+    }
     case TM_DEBUG_SUB_COMPACTIONS: {
         std::lock_guard<std::mutex> dg(ix->dst_mu);
         *value = ix->subs_h.compactions;

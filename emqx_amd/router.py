@@ -145,7 +145,9 @@ class Router:
                  route_in_place: bool = False, local_subs=None):
         """route_in_place: match_routes_by_dest goes through the mirror's
         route_kids32 (tm_route_batch32 on pooled pinned buffers: a micro-batch
-        is matched and fanned out in place) instead of route_kids.
+        is matched and fanned out in place) instead of route_kids, and
+        match_routes_dispatch through dispatch_kids32 (tm_dispatch_batch32)
+        instead of dispatch_kids.
         local_subs: this node's subscribers.LocalSubs; the device list of every
         route key {Filter, node()} then follows it (tm_set_subscribers), for
         match_routes_dispatch."""
@@ -545,8 +547,9 @@ class Router:
 
     def match_routes_dispatch(self, topics, errors: str = "raise", aggre: bool = False):
         """match_routes_by_dest plus the local dispatch, in one device call
-        (tm_dispatch_batch) -> (ByDest, deliveries): deliveries = [(message
-        index, To, subscriber pid)], what do_route2/2's dispatch/2 ->
+        (tm_dispatch_batch; tm_dispatch_batch32 with route_in_place) ->
+        (ByDest, deliveries): deliveries = [(message index, To, subscriber
+        pid)], what do_route2/2's dispatch/2 ->
         do_dispatch2/2 (emqx_broker.erl:726-760) sends on this node, one
         {deliver, To, Msg} each.  In message order; inside a message the Tos in
         the order match_routes_batch lists the routes (the bag's exact-topic
@@ -573,7 +576,8 @@ class Router:
             if dispatch:
                 if local == UNROUTED:
                     raise ValueError("match_routes_dispatch: this node has no destination id")
-                (doff, tidx, kids, err), (dt, dk, ds) = mirror.dispatch_kids(topics, n_dests, local, aggre=aggre)
+                disp = mirror.dispatch_kids32 if self._route_in_place else mirror.dispatch_kids
+                (doff, tidx, kids, err), (dt, dk, ds) = disp(topics, n_dests, local, aggre=aggre)
                 last = None
                 for j, (i, kid, sub) in enumerate(zip(dt.tolist(), dk.tolist(), ds.tolist())):
                     if last != (i, kid):

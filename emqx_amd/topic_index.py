@@ -271,14 +271,19 @@ class Tab:
         blob, offs = _native.pack_strings(topics)
         return self._index.dispatch_batch(blob, offs, n_dests, local_dest, aggre=aggre)
 
-    def _route_set(self, n: int, nbytes: int, n_dests: int, cap: int) -> dict:
+    def _route_set(self, n: int, nbytes: int, n_dests: int, cap: int, dcap: int | None = None) -> dict:
         """A set of pinned buffers (host_array) large enough for the batch, from
         the pool or new -- what a NIF keeps per scheduler.  Arrays too small are
-        replaced; the set goes back with _route_put."""
+        replaced; the set goes back with _route_put.  dcap: the head and the
+        three delivery arrays of dispatch_kids32 as well (a set that never
+        dispatched has none)."""
         with self._lock:
             s = self._route_pool.pop() if self._route_pool else {}
         want = {"blob": (nbytes + 16, np.uint8), "offs": (n + 1, np.uint32), "doff": (n_dests + 2, np.uint32),
                 "topic": (cap, np.uint32), "vals": (cap, np.uint32), "err": (max(n, 1), np.uint8)}
+        if dcap is not None:
+            want.update({"head": (2, np.uint64), "dtopic": (dcap, np.uint32), "dvals": (dcap, np.uint32),
+                         "dsubs": (dcap, np.uint32)})
         for name, (need, dt) in want.items():
             if name not in s or len(s[name]) < need:
                 if name in s:
@@ -323,6 +328,41 @@ class Tab:
                         self._index.host_free(s.pop(name))
                         s[name] = self._index.host_array(total + total // 4, np.uint32)
             return doff.astype(np.uint64), tidx.copy(), kids.copy(), err.copy()
+        finally:
+            self._route_put(s)
+
+    def dispatch_kids32(self, topics, n_dests: int, local_dest: int, aggre: bool = False):
+        """dispatch_kids through tm_dispatch_batch32 on pooled pinned buffers: a
+        micro-batch is matched, fanned out and dispatched in place (one
+        synchronisation, no staging copy).  One retry on TM_ECAP, sized from the
+        bucket offsets and the head.  Returns what dispatch_kids returns
+        (copies: the buffers go back to the pool)."""
+        self.flush()
+        blob, offs = _native.pack_strings(topics)
+        n, nbytes = len(offs) - 1, int(offs[-1])
+        if nbytes >= 1 << 32:
+            return self._index.dispatch_batch(blob, offs, n_dests, local_dest, aggre=aggre)
+        s = self._route_set(n, nbytes, n_dests, max(4 * n, 1024), max(4 * n, 1024))
+        try:
+            s["blob"][:nbytes] = blob[:nbytes]
+            s["offs"][: n + 1] = offs
+            for attempt in (0, 1):
+                out = (s["doff"], s["topic"], s["vals"], s["err"], s["head"], s["dtopic"], s["dvals"], s["dsubs"])
+                try:
+                    (doff, tidx, kids, err), dl = self._index.dispatch_batch32(s["blob"], s["offs"][: n + 1], n_dests,
+                                                                               local_dest, out, aggre=aggre)
+                    break
+                except _native.TmError as e:
+                    if e.code != _native.TM_ECAP or attempt:
+                        raise
+                    total, T = int(s["doff"][n_dests + 1]), int(s["head"][1])
+                    for names, need in ((("topic", "vals"), total), (("dtopic", "dvals", "dsubs"), T)):
+                        if need <= len(s[names[0]]):
+                            continue
+                        for name in names:   # the offsets hold the full bucket sizes, the head the deliveries
+                            self._index.host_free(s.pop(name))
+                            s[name] = self._index.host_array(need + need // 4, np.uint32)
+            return (doff.astype(np.uint64), tidx.copy(), kids.copy(), err.copy()), tuple(a.copy() for a in dl)
         finally:
             self._route_put(s)
 

@@ -629,7 +629,36 @@ int tm_route_batch32_ex(tm_index *h, uint64_t n, const uint8_t *topic_bytes, con
  * dispatch kernels are queued again: no second walk.  TM_EINVAL for
  * local_dest >= n_dests, a null out_head, null delivery buffers with dcap > 0,
  * and whatever tm_route_batch_ex refuses.  Lanes, read-your-writes, the
- * device-failure retry and the out_err rules are unchanged. */
+ * device-failure retry and the out_err rules are unchanged.
+ *
+ * tm_dispatch_batch32 (ABI minor 17): tm_dispatch_batch with 32-bit offsets in
+ * and out, for a NIF's micro-batches.  For the same index state, topics,
+ * n_dests, local_dest, flags, cap and dcap every output array and the return
+ * code are what tm_dispatch_batch writes and returns, out_dest_offsets narrowed
+ * to u32 (n_dests + 2 entries); out_head stays u64[2] = [M, T] (T is a 64-bit
+ * sum) and must be 8-byte aligned.  Nothing is written at or past min(total,
+ * cap) in out_topic / out_values, nothing at or past min(T, dcap) in the three
+ * delivery arrays.  out_err is required.  TM_ECAP as tm_dispatch_batch: when
+ * total > cap (the offsets hold the full sizes, before aggregation under
+ * TM_ROUTE_AGGRE) and when T > dcap (out_head[1] sizes the retry).  TM_EINVAL:
+ * whatever tm_route_batch32_ex refuses, local_dest >= n_dests, a null
+ * out_head, null delivery buffers with dcap > 0, out_head not 8-byte aligned.
+ * Lanes, read-your-writes and the device-failure retry are unchanged.
+ * In place -- no staging copy in, no copy out, one synchronisation -- under
+ * exactly tm_route_batch32's conditions, with out_head and the three delivery
+ * arrays in this index's tm_host_alloc memory as well: the one-launch pairs
+ * walk and the one-launch fan-out (and with TM_ROUTE_AGGRE the one-workgroup
+ * aggre pass) write the lane's scratch, and ONE more launch of one workgroup
+ * copies the route outputs, counts and scans the local bucket's subscriber
+ * lists and expands them into the caller's buffers, which the device never
+ * reads.  That workgroup expands at most 32768 deliveries (TM_DEBUG_DP1_MAX
+ * lowers the bound); a local bucket with more, or a batch with more than 16384
+ * entries, is finished on the same lane by tm_dispatch_dev's grid kernels on the
+ * arrays already there (no second walk), which write the deliveries straight
+ * into the caller's buffers.  Every other batch is widened on the host, run by
+ * tm_dispatch_batch, and narrowed.  TM_DEBUG_DISPATCH_ONE /
+ * TM_DEBUG_DISPATCH_GRID (tm_debug_get) count the calls the one-launch kernel
+ * completed / the grid kernels or the staged path finished. */
 int tm_set_subscribers(tm_index *h, uint64_t n, const uint32_t *values, const uint64_t *list_offsets,
                        const uint32_t *subs);
 int tm_dispatch_dev(tm_index *h, uint32_t n_dests, const uint64_t *d_dest_offsets, uint32_t bucket,
@@ -643,6 +672,11 @@ int tm_dispatch_batch(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const
                       uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
                       uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
                       uint64_t dcap, uint8_t *out_err);
+int tm_dispatch_batch32(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint32_t *topic_offsets,
+                        uint32_t n_dests, uint32_t local_dest, uint32_t flags,
+                        uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                        uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
+                        uint64_t dcap, uint8_t *out_err);
 
 /* Release the batch scratch kept for `stream` (after its batches finish);
  * a caller that retires a stream calls this.  No reference counterpart. */
@@ -744,7 +778,12 @@ int tm_profile_read(tm_index *h, double *walk_ms, double *batch_ms, uint64_t *ba
  * all ones while the slot is unused; TM_DEBUG_HINT_AUDIT (get only): vocab
  * entries whose hint of an annexed node differs from what that node's child
  * slot gives, in the host image (always 0).  TM_DEBUG_SUB_COMPACTIONS (get
- * only): how often tm_set_subscribers rewrote its pool tight. */
+ * only): how often tm_set_subscribers rewrote its pool tight.
+ * TM_DEBUG_DISPATCH_ONE / TM_DEBUG_DISPATCH_GRID (get only): tm_dispatch_batch32
+ * calls the one-launch kernel completed / that the grid kernels or the staged
+ * path finished.  TM_DEBUG_DP1_MAX (set / get): the deliveries of the local
+ * bucket up to which the one-launch kernel expands them itself, clamped to the
+ * compiled bound (32768). */
 enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES = 3, TM_DEBUG_PHASES = 4,
        TM_DEBUG_FAILED_BATCHES = 5, TM_DEBUG_RETRIED_BATCHES = 6, TM_DEBUG_PATH_PHASES = 7,
        TM_DEBUG_PATH_SMALL = 8, TM_DEBUG_PATH_LANE = 9, TM_DEBUG_SMALL_KERNEL = 10,
@@ -753,7 +792,8 @@ enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES =
        TM_DEBUG_COMMITS = 19, TM_DEBUG_COMMIT_WAITS = 20, TM_DEBUG_COMMIT_FORCED = 21, TM_DEBUG_SMALL_TICKET = 22,
        TM_DEBUG_CMB_SPIN = 23, TM_DEBUG_PATCH_ZC = 24, TM_DEBUG_FANOUT_GRID = 25,
        TM_DEBUG_ROUTE_ONE = 26, TM_DEBUG_ROUTE_GRID = 27, TM_DEBUG_ANNEX0 = 28, TM_DEBUG_ANNEX1 = 29,
-       TM_DEBUG_HINT_AUDIT = 30, TM_DEBUG_SUB_COMPACTIONS = 31 };
+       TM_DEBUG_HINT_AUDIT = 30, TM_DEBUG_SUB_COMPACTIONS = 31, TM_DEBUG_DISPATCH_ONE = 32,
+       TM_DEBUG_DISPATCH_GRID = 33, TM_DEBUG_DP1_MAX = 34 };
 int tm_debug_set(tm_index *h, uint32_t key, uint64_t value);
 int tm_debug_get(tm_index *h, uint32_t key, uint64_t *value);
 

@@ -81,7 +81,24 @@ tm_fanout_dev_pairs and tm_aggre_dev (filter_of[v] = v) are timed on the same
 entries in the same run.  One JSON line per table: both medians and spreads,
 deliveries/s, the algorithmic bytes (12 written + 4 read per delivery, 8 + 8 +
 12 per entry) per second, and the last line the skewed table's time per
-delivery over the uniform one's.
+delivery over the uniform one's.  With --small: the NIF's call instead, host to
+host as above, per batch size and per table (uniform / skewed, installed with
+tm_set_subscribers; --subs LO HI changes the uniform range), four legs
+interleaved:
+
+  dispatch_batch32       tm_dispatch_batch32, in place (--dp1-max N sets
+                         TM_DEBUG_DP1_MAX for it: the deliveries the one-launch
+                         kernel expands itself)
+  dispatch_batch32_grid  the same call with TM_DEBUG_DP1_MAX 0: the route
+                         outputs in one launch, the deliveries by the grid
+                         kernels -- the other side of the crossover
+  dispatch_batch         tm_dispatch_batch on the same topics, the staged path
+  route_batch32          tm_route_batch32_ex alone: what dispatch adds
+
+Outputs are compared before anything is timed (identical); the line says which
+leg finished each call (TM_DEBUG_DISPATCH_ONE / _GRID).  --aggre passes
+TM_ROUTE_AGGRE to every leg.  Under TM_LIB naming a library without
+tm_dispatch_batch32 only the last two legs run (the yardstick of an A/B).
 """
 import argparse
 import json
@@ -490,6 +507,9 @@ def small_batches(a, sizes=(64, 1024, 4096, 16384), n_dests=16, warmup=20, reps=
     ix.sync(None)
     P = _native._ptr
     lib, h = ix._lib, ix._h
+    if a.dispatch:
+        small_dispatch(a, ix, len(fs), nvals, sizes, n_dests, warmup, reps)
+        return
     for n in sizes:
         tp = wl.topics(3, a.filters, n)
         assert len(tp) == n
@@ -564,6 +584,105 @@ def small_batches(a, sizes=(64, 1024, 4096, 16384), n_dests=16, warmup=20, reps=
             ix.host_free(x)
 
 
+def small_dispatch(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=0):
+    """--small --dispatch: host-to-host latency of a micro-batch's route fan-out plus local dispatch"""
+    import time
+    P = _native._ptr
+    lib, h = ix._lib, ix._h
+    has32 = hasattr(lib, "tm_dispatch_batch32")
+    flags = _native.TM_ROUTE_AGGRE if a.aggre else 0
+    ONE, GRID, DP1 = _native.TM_DEBUG_DISPATCH_ONE, _native.TM_DEBUG_DISPATCH_GRID, _native.TM_DEBUG_DP1_MAX
+    dp1 = a.dp1_max if a.dp1_max is not None else _native.DP1_DELIVERIES
+    rng = np.random.default_rng(7)
+    for name in ("uniform", "skewed"):
+        cnt = rng.integers(a.subs[0], a.subs[1] + 1, nvals)
+        if name == "skewed":
+            cnt[rng.choice(nvals, max(nvals // 1000, 1), replace=False)] = 10_000
+        loffs = np.zeros(nvals + 1, np.uint64)
+        loffs[1:] = np.cumsum(cnt)
+        subs = rng.integers(0, 1 << 31, int(loffs[-1]), dtype=np.int64).astype(np.uint32)
+        vals = np.arange(nvals, dtype=np.uint32)
+        assert lib.tm_set_subscribers(h, nvals, P(vals), P(loffs), P(subs)) == 0
+        for n in sizes:
+            tp = wl.topics(3, a.filters, n)
+            nb = int(tp.offs[-1])
+            blob, offs32, offs64 = ix.host_array(nb + 16, np.uint8), ix.host_array(n + 1, np.uint32), \
+                ix.host_array(n + 1, np.uint64)
+            blob[:nb] = tp.blob[:nb]
+            offs32[:], offs64[:] = tp.offs.astype(np.uint32), tp.offs
+            err = ix.host_array(n, np.uint8)
+            cap = 16 * n + 1024
+            # the sizes first (TM_ECAP with full offsets and the exact head), then buffers that fit
+            d64, head = ix.host_array(n_dests + 2, np.uint64), ix.host_array(2, np.uint64)
+            rc = lib.tm_dispatch_batch(h, n, P(blob), P(offs64), n_dests, local, flags, P(d64), None, None, 0, P(head),
+                                       None, None, None, 0, P(err))
+            assert rc in (0, _native.TM_ECAP)
+            M, T = int(head[0]), int(head[1])
+            dcap = T + 1024
+            ra, rb, rc_ = ((ix.host_array(cap, np.uint32), ix.host_array(cap, np.uint32)) for _ in range(3))
+            da, db = (tuple(ix.host_array(dcap, np.uint32) for _ in range(3)) for _ in range(2))
+            d32, r32, head32 = ix.host_array(n_dests + 2, np.uint32), ix.host_array(n_dests + 2, np.uint32), \
+                ix.host_array(2, np.uint64)
+
+            def leg_x():
+                return lib.tm_dispatch_batch32(h, n, P(blob), P(offs32), n_dests, local, flags, P(d32), P(ra[0]),
+                                               P(ra[1]), cap, P(head32), P(da[0]), P(da[1]), P(da[2]), dcap, P(err))
+
+            def leg_y():
+                return lib.tm_dispatch_batch(h, n, P(blob), P(offs64), n_dests, local, flags, P(d64), P(rb[0]), P(rb[1]),
+                                             cap, P(head), P(db[0]), P(db[1]), P(db[2]), dcap, P(err))
+
+            def leg_z():
+                return lib.tm_route_batch32_ex(h, n, P(blob), P(offs32), n_dests, P(r32), P(rc_[0]), P(rc_[1]), cap,
+                                               P(err), flags)
+
+            assert leg_y() == 0 and leg_z() == 0, "a leg failed (or cap too small)"
+            total = int(d64[n_dests + 1])
+            took = {}
+            if has32:
+                for key, bound in (("dispatch_batch32", dp1), ("dispatch_batch32_grid", 0)):
+                    ix.debug_set(DP1, bound)
+                    for x in (*ra, *da):
+                        x[:] = 0xC0FFEE11
+                    c0 = (ix.debug_get(ONE), ix.debug_get(GRID))
+                    assert leg_x() == 0
+                    took[key] = "one_launch" if ix.debug_get(ONE) > c0[0] else "grid"
+                    assert ix.debug_get(ONE) + ix.debug_get(GRID) == sum(c0) + 1
+                    assert head32.tolist() == [M, T] == head.tolist() and np.array_equal(d64, d32.astype(np.uint64)) and \
+                        all(np.array_equal(x[:total], y[:total]) for x, y in zip(ra, rb)) and \
+                        all(np.array_equal(x[:T], y[:T]) for x, y in zip(da, db)) and \
+                        all((x[total:] == 0xC0FFEE11).all() for x in ra) and \
+                        all((x[T:] == 0xC0FFEE11).all() for x in da), \
+                        f"n {n}: tm_dispatch_batch and tm_dispatch_batch32 ({key}) differ"
+            legs = [("dispatch_batch", leg_y, None), ("route_batch32", leg_z, None)]
+            if has32:
+                legs = [("dispatch_batch32", leg_x, dp1), ("dispatch_batch32_grid", leg_x, 0)] + legs
+            ms = {k: [] for k, _, _ in legs}
+            for r in range(warmup + reps):
+                for k, f, bound in legs:
+                    if bound is not None:
+                        ix.debug_set(DP1, bound)
+                    t0 = time.perf_counter_ns()
+                    f()
+                    t1 = time.perf_counter_ns()
+                    if r >= warmup:
+                        ms[k].append((t1 - t0) * 1e-6)
+            if has32:
+                ix.debug_set(DP1, dp1)
+            st = {k: dict(stats(v), p50_ms=round(float(np.median(v)), 4)) for k, v in ms.items()}
+            line = {"tool": "fanout_bench", "kind": "small_dispatch", "filters": fs_len, "topics": n, "entries": total,
+                    "n_dests": n_dests, "lists": name, "subs": list(a.subs), "aggre": bool(a.aggre), "bucket_entries": M,
+                    "deliveries": T, "dp1_max": dp1 if has32 else None, "warmup": warmup, "reps": reps, "finished_by": took,
+                    **st, "dispatch_minus_route32_ms": round(st["dispatch_batch"]["p50_ms"] - st["route_batch32"]["p50_ms"], 4),
+                    "identical": True if has32 else None}
+            if has32:
+                line["batch32_minus_route32_ms"] = round(st["dispatch_batch32"]["p50_ms"] - st["route_batch32"]["p50_ms"], 4)
+                line["batch_over_batch32"] = round(st["dispatch_batch"]["p50_ms"] / st["dispatch_batch32"]["p50_ms"], 2)
+            print(json.dumps(line), flush=True)
+            for x in (blob, offs32, offs64, err, d64, head, d32, r32, head32, *ra, *rb, *rc_, *da, *db):
+                ix.host_free(x)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--filters", type=int, default=1_000_000)
@@ -576,6 +695,10 @@ def main():
     p.add_argument("--aggre", action="store_true", help="aggre/1 on the device (see above); with --small: a fourth leg")
     p.add_argument("--dispatch", action="store_true", help="local dispatch on the device (see above)")
     p.add_argument("--sizes", type=int, nargs="+", default=None, help="--small: the batch sizes")
+    p.add_argument("--dp1-max", type=int, default=None,
+                   help="--small --dispatch: TM_DEBUG_DP1_MAX for the dispatch_batch32 leg (default: the compiled bound)")
+    p.add_argument("--subs", type=int, nargs=2, default=[1, 4], metavar=("LO", "HI"),
+                   help="--small --dispatch: subscribers per value of the uniform table")
     a = p.parse_args()
     import torch
     if not torch.cuda.is_available():
