@@ -30,10 +30,15 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_match_batch32_pairs", "tm_match_batch_dev_pairs", "tm_set_dests", "tm_fanout_dev", "tm_route_batch",
            "tm_fanout_dev_pairs", "tm_route_batch32", "tm_set_route_filters", "tm_aggre_dev", "tm_route_batch_ex",
            "tm_route_batch32_ex", "tm_set_subscribers", "tm_dispatch_dev", "tm_dispatch_batch",
-           "tm_dispatch_batch32")
+           "tm_dispatch_batch32", "tm_set_share_slots", "tm_set_share_members", "tm_share_state_set",
+           "tm_share_state_get", "tm_share_pick_dev", "tm_publish_batch")
 TM_ALLOC_VRAM = 1
 TM_ROUTE_AGGRE = 1          # tm_route_batch_ex / tm_route_batch32_ex: aggre/1 applied to the buckets
 NO_FILTER = 0xFFFFFFFF      # tm_set_route_filters: no filter known (equal to nothing)
+# shared-subscription pick (include/tmatch.h): no slot / no pick, a state never set, the strategy bytes
+TM_SHARE_NONE = TM_SHARE_UNDEF = 0xFFFFFFFF
+(TM_SHARE_RANDOM, TM_SHARE_ROUND_ROBIN, TM_SHARE_ROUND_ROBIN_PER_GROUP, TM_SHARE_STICKY, TM_SHARE_LOCAL,
+ TM_SHARE_HASH_CLIENTID, TM_SHARE_HASH_TOPIC) = range(7)
 TM_DEBUG_LB_SPINS, TM_DEBUG_LB_FAIL_BLOCK, TM_DEBUG_LB_LAUNCHES, TM_DEBUG_PHASES = 1, 2, 3, 4
 TM_DEBUG_FAILED_BATCHES, TM_DEBUG_RETRIED_BATCHES = 5, 6
 TM_DEBUG_PATH_PHASES, TM_DEBUG_PATH_SMALL, TM_DEBUG_PATH_LANE = 7, 8, 9
@@ -146,6 +151,13 @@ def load_library(path: Path | None = None):
         "tm_dispatch_dev": (i32, [vp, u32, vp, u32, vp, vp, u64, vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, vp]),
         "tm_dispatch_batch": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp]),
         "tm_dispatch_batch32": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp]),
+        "tm_set_share_slots": (i32, [vp, u64, vp, vp]),
+        "tm_set_share_members": (i32, [vp, u64, vp, vp, vp, vp, vp]),
+        "tm_share_state_set": (i32, [vp, u64, vp, vp]),
+        "tm_share_state_get": (i32, [vp, u32, u64, vp, vp]),
+        "tm_share_pick_dev": (i32, [vp, u32, vp, vp, vp, u64, vp, vp, u64, u32, vp, u64, vp, u64, vp, u64, vp, vp, vp, vp]),
+        "tm_publish_batch": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u32, vp,
+                                   vp]),
         "tm_debug_set": (i32, [vp, u32, u64]),
         "tm_debug_get": (i32, [vp, u32, C.POINTER(u64)]),
     }
@@ -615,6 +627,109 @@ class Index:
                                                   cap, _ptr(head), _ptr(dt), _ptr(dv), _ptr(ds), dcap, _ptr(err)))
         total, T = int(doff[n_dests + 1]), int(head[1])
         return (doff[: n_dests + 2], topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T])
+
+    # ---- shared-subscription pick (include/tmatch.h "Shared-subscription pick on the device")
+    def set_share_slots(self, values, slots):
+        """tm_set_share_slots: route value values[i] belongs to slot slots[i] (the
+        caller's dense id of a {Group, To} pair; TM_SHARE_NONE: none)."""
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        if len(values) != len(slots):
+            raise ValueError("set_share_slots: one slot per value")
+        self._check(self._lib.tm_set_share_slots(self._h, len(values), _ptr(values), _ptr(slots)))
+
+    def set_share_members(self, slots, lists, n_local, meta):
+        """tm_set_share_members: lists[i] (u32 member ids in subscribers/2's order,
+        the n_local[i] local ones first) becomes slot slots[i]'s member list,
+        meta[i] = strategy | init_strategy << 8.  Never touches a slot's state."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        n_local = np.ascontiguousarray(n_local, dtype=np.uint32)
+        meta = np.ascontiguousarray(meta, dtype=np.uint32)
+        if not len(slots) == len(lists) == len(n_local) == len(meta):
+            raise ValueError("set_share_members: one list, n_local and meta per slot")
+        offs = np.zeros(len(slots) + 1, dtype=np.uint64)
+        if len(slots):
+            offs[1:] = np.cumsum([len(x) for x in lists], dtype=np.uint64)
+        mem = np.zeros(max(int(offs[-1]), 1), dtype=np.uint32)
+        for i, x in enumerate(lists):
+            mem[int(offs[i]):int(offs[i + 1])] = np.asarray(x, dtype=np.uint32)
+        self._check(self._lib.tm_set_share_members(self._h, len(slots), _ptr(slots), _ptr(offs), _ptr(mem), _ptr(n_local),
+                                                   _ptr(meta)))
+
+    def share_state_set(self, slots, states):
+        """tm_share_state_set: the slots' state words, on every device entry."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        states = np.ascontiguousarray(states, dtype=np.uint32)
+        if len(slots) != len(states):
+            raise ValueError("share_state_set: one state per slot")
+        self._check(self._lib.tm_share_state_set(self._h, len(slots), _ptr(slots), _ptr(states)))
+
+    def share_state_get(self, slots, dev: int = 0) -> np.ndarray:
+        """tm_share_state_get: the slots' state words on device entry `dev`, after
+        every pick queued there so far (TM_SHARE_UNDEF: never set)."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        out = np.zeros(max(len(slots), 1), dtype=np.uint32)
+        self._check(self._lib.tm_share_state_get(self._h, dev, len(slots), _ptr(slots), _ptr(out)))
+        return out[:len(slots)]
+
+    def share_pick_dev(self, n_dests: int, d_dest_offs: int, d_topic: int, d_value: int, cap: int, d_out_head: int,
+                       d_out_member: int, d_key_clientid: int | None = None, d_key_topic: int | None = None,
+                       n_topics: int = 0, seed: int = 0, d_slot_of: int | None = None, slot_of_len: int = 0,
+                       d_slot_rec: int | None = None, n_slots: int = 0, d_pool: int | None = None, pool_len: int = 0,
+                       d_state: int | None = None, stream: int | None = None):
+        """tm_share_pick_dev on device pointers: one member (or TM_SHARE_NONE) per
+        entry of an aggre pass's output into d_out_member, d_out_head u64[2] =
+        (entries with a slot, entries with a pick); the slots' state words
+        advance once.  d_slot_of None: the tables of set_share_slots /
+        set_share_members and the index's own state."""
+        self._check(self._lib.tm_share_pick_dev(self._h, n_dests, d_dest_offs, d_topic, d_value, cap, d_key_clientid,
+                                                d_key_topic, n_topics, seed, d_slot_of, slot_of_len, d_slot_rec, n_slots,
+                                                d_pool, pool_len, d_state, d_out_head, d_out_member, stream))
+
+    def publish_batch(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, local_dest: int, cap: int | None = None,
+                      dcap: int | None = None, key_clientid=None, key_topic=None, seed: int = 0):
+        """tm_publish_batch -> (dispatch_batch's two tuples under aggre, member
+        u32[K]): member[q] is the shared-subscription pick of kept entry q
+        (TM_SHARE_NONE: none).  A cap that proves too small is retried, sized
+        from what the call returned; the state moves only in the call that
+        stands, unless dcap alone was short (the picks of that call stand, the
+        retry picks again)."""
+        n = len(offs) - 1
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        kc = None if key_clientid is None else np.ascontiguousarray(key_clientid, dtype=np.uint32)
+        kt = None if key_topic is None else np.ascontiguousarray(key_topic, dtype=np.uint32)
+        if any(k is not None and len(k) < n for k in (kc, kt)):
+            raise ValueError("publish_batch: one key word per topic")
+        doff = np.zeros(n_dests + 2, dtype=np.uint64)
+        head = np.zeros(2, dtype=np.uint64)
+        err = np.zeros(max(n, 1), dtype=np.uint8)
+        if cap is None:
+            cap = max(4 * n, 1024)
+        if dcap is None:
+            dcap = max(4 * n, 1024)
+        for _ in range(4):
+            topic = np.empty(max(cap, 1), dtype=np.uint32)
+            vals = np.empty(max(cap, 1), dtype=np.uint32)
+            member = np.empty(max(cap, 1), dtype=np.uint32)
+            dt, dv, ds = (np.empty(max(dcap, 1), dtype=np.uint32) for _ in range(3))
+            rc = self._lib.tm_publish_batch(self._h, n, _ptr(blob), _ptr(offs), n_dests, local_dest, TM_ROUTE_AGGRE,
+                                            _ptr(doff), _ptr(topic), _ptr(vals), cap, _ptr(head), _ptr(dt), _ptr(dv),
+                                            _ptr(ds), dcap, _ptr(kc), _ptr(kt), seed, _ptr(member), _ptr(err))
+            if rc == TM_ECAP and int(doff[-1]) > cap:
+                # (no pick was made: the state has not moved)
+                cap = max(cap, int(doff[-1]))
+                dcap = max(dcap, int(head[1]))
+                continue
+            if rc != TM_ECAP:
+                self._check(rc)
+            total, T = int(doff[-1]), int(head[1])
+            if rc == TM_ECAP:
+                # dcap alone: the picks stand; only the dispatch is fetched again
+                (_, _, _, _), (dt, dv, ds) = self.dispatch_batch(blob, offs, n_dests, local_dest, cap=cap, dcap=T,
+                                                                 aggre=True)
+            return (doff, topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T]), member[:total]
+        raise TmError(TM_ECAP, "publish_batch: the totals kept growing")
 
     def release_stream(self, stream: int | None):
         """Drop the batch scratch the library keeps for `stream`."""

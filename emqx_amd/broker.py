@@ -11,9 +11,12 @@ the per-route dispatch (do_route2, :400-406) then run per message exactly as
 in the reference, so each message gets the same route list and the same
 deliveries as an unbatched publish.
 
-Delivery itself (sessions, shared-subscription pick, cluster RPC) is out of
-scope: ``dispatch(To, Msg)``, ``forward(Node, To, Msg)`` and
-``share_dispatch(Group, To, Msg)`` are caller-supplied callbacks.  With
+Delivery itself (sessions, cluster RPC) is out of scope: ``dispatch(To,
+Msg)``, ``forward(Node, To, Msg)`` and ``share_dispatch(Group, To, Msg)`` are
+caller-supplied callbacks.  With ``share_on_device`` the shared-subscription
+pick of emqx_shared_sub:dispatch/3 has run on the device too, and the callback
+is ``share_send(SubPid, To, Msg)``; a failed send falls back to the
+reference's dispatch/4 recursion on the host (SharedSubs.pick with FailedSubs).  With
 ``dispatch_on_device`` the local node's ``dispatch/2`` -- the ?SUBSCRIBER
 lookups of do_dispatch2/2 (:726-760) -- has run on the device as well, and the
 callback is ``deliver(SubPid, To, Msg)``, the ``SubPid ! {deliver, To, Msg}``.
@@ -56,13 +59,25 @@ def aggre(routes):
 class Broker:
     def __init__(self, router, node=None, dispatch=None, forward=None, share_dispatch=None,
                  max_batch: int = 4096, max_wait_ms: float = 0.2, start: bool = False,
-                 aggre_on_device: bool = False, dispatch_on_device: bool = False, deliver=None):
+                 aggre_on_device: bool = False, dispatch_on_device: bool = False, deliver=None,
+                 share_on_device: bool = False, share_send=None, share_keys=None, share_seed: int = 0):
         """aggre_on_device: publish_batch_by_dest asks the router for buckets
         the device has already applied aggre/1 to (TM_ROUTE_AGGRE).
         dispatch_on_device: publish_batch_by_dest asks the router for the local
         node's deliveries too (Router.match_routes_dispatch); the local node's
         plan is then [(message index, To, subscriber)], each handed to
-        deliver(subscriber, To, message), and dispatch is not called."""
+        deliver(subscriber, To, message), and dispatch is not called.
+        share_on_device: publish_batch_by_dest asks the router for the picks
+        as well (Router.match_routes_publish: aggre/1, the local dispatch and
+        the pick in one device call); a group's plan is then [(message index,
+        To, pid)], each handed to share_send(pid, To, message) -> "ok" or an
+        error reason, and share_dispatch is not called.  share_keys(message) ->
+        (phash2(ClientId), phash2(Topic)) for the two hash strategies (default:
+        zeros); share_seed: the seed of the batch's random picks."""
+        self.share_on_device = share_on_device
+        self.share_send = share_send or (lambda pid, to, msg: "ok")
+        self.share_keys = share_keys or (lambda msg: (0, 0))
+        self.share_seed = share_seed
         self.router = router
         self.aggre_on_device = aggre_on_device
         self.dispatch_on_device = dispatch_on_device
@@ -137,8 +152,13 @@ class Broker:
         if not msgs:
             return {}, {}
         on_dev = self.aggre_on_device
-        deliveries = None
-        if self.dispatch_on_device:
+        deliveries = picks = keys = None
+        if self.share_on_device:
+            keys = [self.share_keys(m) for m in msgs]
+            by_dest, deliveries, picks = self.router.match_routes_publish(
+                [m.topic for m in msgs], [k[0] for k in keys], [k[1] for k in keys], seed=self.share_seed, errors="return")
+            on_dev = True
+        elif self.dispatch_on_device:
             by_dest, deliveries = self.router.match_routes_dispatch([m.topic for m in msgs], errors="return",
                                                                     aggre=on_dev)
         elif on_dev:
@@ -152,6 +172,9 @@ class Broker:
             if deliveries is not None and cls == self.node:
                 continue   # the local node's routes are already expanded: its plan is the deliveries
             node = not isinstance(rows[0][1].dest, tuple)
+            if picks is not None and not node and not isinstance(cls, tuple) and cls in picks:
+                continue   # a group's routes are already picked: its plan is the picks (a group no pick
+                           # came back for keeps the host path: share_dispatch)
             dest = cls[0] if isinstance(cls, tuple) else cls   # aggre/1: {Group, _Node} -> Group, whatever the pair
             plan = plans.setdefault(dest, [])
             # rows the device has aggregated need no check: all but the bag's, unless classes merge here
@@ -170,7 +193,40 @@ class Broker:
             for i, to, sub in deliveries:
                 self.deliver(sub, to, msgs[i])
             out[self.node] = list(deliveries)
+        for group, rows in (picks or {}).items():
+            out[group] = [(i, to, self._share_deliver(group, to, i, pid, msgs[i], keys[i])) for i, to, pid in rows]
         return out, by_dest.errors
+
+    def _share_deliver(self, group, to, i, pid, msg, hashes):
+        """do_dispatch/5 to the device's pick; when the send fails, dispatch/4's
+        recursion on the host: the slot's state word read back, SharedSubs.pick
+        with the failed pids in FailedSubs until a send succeeds (or a {retry,
+        _} pick, which is sent without an ack), and the word written back.
+        -> the pid the message went to, or ("error", "no_subscribers")."""
+        if pid is None:
+            return ("error", "no_subscribers")
+        reason = self.share_send(pid, to, msg)
+        if reason == "ok":
+            return pid
+        ss = self.router.shared_subs
+        slot = ss.slot(group, to)
+        if slot is not None:
+            ss.adopt_state(group, to, self.router.share_state(slot))
+        failed = {pid: reason}
+        result = ("error", "no_subscribers")
+        while True:
+            res = ss.pick(group, to, hashes[0], hashes[1], failed, i)
+            if not res:
+                break
+            kind, p = res
+            reason = self.share_send(p, to, msg)
+            if reason == "ok" or kind == "retry":
+                result = p
+                break
+            failed[p] = reason
+        if slot is not None:
+            self.router.set_share_state(slot, ss.device_state(group, to))
+        return result
 
     # ---- asynchronous micro-batching
     def publish(self, msg) -> Future:

@@ -226,6 +226,11 @@ struct FanoutScratch {
     uint32_t *dp_cnt;
     uint64_t *dp_off, *dp_tot;
     uint64_t dp_cap, dp_off_cap;
+    // shared-subscription pick (launch_share_pick; tab and tot above carry its digit passes): per entry
+    // below sh_cap the slot of a ranked entry, two (slot, q) pair arrays for the passes' ping-pong, the
+    // FO_GRID ranked / with-slot / picked block counts (3 * FO_GRID + 1 words)
+    uint32_t *sh_key, *sh_s[2], *sh_q[2], *sh_cnt;
+    uint64_t sh_cap;
 };
 constexpr uint32_t FP_TILES = 1024;
 #if defined(__HIPCC__)
@@ -387,6 +392,20 @@ hipError_t launch_dispatch_one(const uint32_t *status_in, const uint32_t *fo_off
                                uint32_t *out_topic, uint32_t *out_value, uint64_t cap, uint64_t *out_head,
                                uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub, uint64_t dcap,
                                uint64_t dp1_max, uint32_t *status, hipStream_t s);
+// Shared-subscription pick (tm_share.hip; include/tmatch.h tm_share_pick_dev has
+// the definition): one member per entry below E = min(dest_offsets[n_dests + 1],
+// cap) of an aggre pass's output into out_member, head = [entries with a slot,
+// entries with a pick], the slots' state words advanced once.  slot_rec must be
+// 16-byte aligned.  Needs fs.sh_cap >= min(cap, 2^32 - 1), fs.tab and fs.tot.
+// The strategy byte of a slot record's meta word (tmatch.h TM_SHARE_*):
+enum : uint32_t { SH_RANDOM = 0, SH_ROUND_ROBIN = 1, SH_ROUND_ROBIN_PER_GROUP = 2, SH_STICKY = 3, SH_LOCAL = 4,
+                  SH_HASH_CLIENTID = 5, SH_HASH_TOPIC = 6, SH_STRATEGIES = 7 };
+uint32_t share_passes(uint64_t n_slots);   // digit passes a call with that many slots runs
+hipError_t launch_share_pick(const FanoutScratch &fs, uint32_t n_dests, const uint64_t *dest_offsets,
+                             const uint32_t *in_topic, const uint32_t *in_value, uint64_t cap, const uint32_t *key_clientid,
+                             const uint32_t *key_topic, uint64_t n_topics, uint32_t seed, const uint32_t *slot_of,
+                             uint64_t slot_of_len, const uint32_t *slot_rec, uint64_t n_slots, const uint32_t *pool,
+                             uint64_t pool_len, uint32_t *state, uint64_t *head, uint32_t *out_member, hipStream_t s);
 // delta upload: run i copies runs[i].n u32 words from data + runs[i].src to
 // word (dst & PATCH_OFF) of table (dst >> 48), whose device address on the
 // replica being patched is bases.b[table] (the same runs patch every replica)

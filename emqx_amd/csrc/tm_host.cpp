@@ -135,6 +135,9 @@ struct Lane {
     uint32_t *fo1_s = nullptr;
     // tm_dispatch_batch: the local bucket's deliveries (topic, value, subscriber)
     uint32_t *d_dt = nullptr, *d_dv = nullptr, *d_ds = nullptr; uint64_t d_dt_cap = 0, d_dv_cap = 0, d_ds_cap = 0;
+    // tm_publish_batch: the picked member of every kept entry, then the pick's two head words
+    uint32_t *d_sm = nullptr; uint64_t d_sm_cap = 0;
+    uint32_t *d_sk = nullptr; uint64_t d_sk_cap = 0;   // its two key words per topic
 };
 
 // Patch log: a ring of the last PATCH_RING patches (numbered 1, 2, ... in the
@@ -295,6 +298,17 @@ struct tm_index {
     // first (subs_upload)
     SubPool subs_h;
     DestDev sub_pool[MAX_REPLICAS], sub_span[MAX_REPLICAS];
+    // shared subscriptions (tm_set_share_slots / tm_set_share_members): value ->
+    // slot as the tables above; the slots' member lists in a second pool of
+    // tm_subs.h, whose spans become the first two words of the 16-byte slot
+    // records (pos, cnt, n_local, meta) the device gathers; all under the same
+    // lock, a pick takes the three in one hold of it (share_upload).  The
+    // slots' state words live on the device alone, one array per group, UNDEF
+    // where never set; it grows with its contents kept (share_state_grow).
+    std::vector<uint32_t> share_slot_h, share_rec_h;
+    SubPool share_h;
+    DestDev share_slot[MAX_REPLICAS], share_rec[MAX_REPLICAS], share_pool[MAX_REPLICAS];
+    struct ShareState { uint32_t *d = nullptr; uint64_t cap = 0; } share_state[MAX_REPLICAS];
 
     // caller buffers from tm_host_alloc (host address -> size, device address;
     // vram: TM_ALLOC_VRAM device memory, the same address on both sides)
@@ -1801,7 +1815,7 @@ void free_lane(Lane &l) {
     free_workspace(l.w);
     void *dv[] = {l.d_in, l.d_res, l.d_vals, l.d_o64, l.d_h64, l.f.tab, l.f.tot, l.f.t, l.f.v, l.f.b, l.f.voff, l.f.sums, l.f.b2,
                   l.d_ft, l.d_fv, l.d_fo, l.d_pr, l.f.ag_bits, l.f.ag_pre, l.f.ag_cnt, l.d_at, l.d_av, l.d_ao, l.fo1_s,
-                  l.f.dp_cnt, l.f.dp_off, l.f.dp_tot, l.d_dt, l.d_dv, l.d_ds};
+                  l.f.dp_cnt, l.f.dp_off, l.f.dp_tot, l.d_dt, l.d_dv, l.d_ds, l.f.sh_key, l.f.sh_cnt, l.d_sm, l.d_sk};
     for (void *p : dv) if (p) (void)hipFree(p);
     void *pins[] = {l.pin_in, l.pin_out, l.pin_vals, l.fo1_h};
     for (void *p : pins) if (p) (void)hipHostFree(p);
@@ -2145,7 +2159,7 @@ struct HostBatch {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 17u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 18u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 
@@ -2260,11 +2274,13 @@ int tm_destroy(tm_index *ix) {
     for (int g = 0; g < ix->ngroups; g++) {
         for (int r = 0; r < ix->nrep; r++)
             if (ix->rep[r].group == g) { (void)hipSetDevice(ix->rep[r].device); break; }
-        for (auto *D : {&ix->dest[g], &ix->filt[g], &ix->sub_pool[g], &ix->sub_span[g]}) {
+        for (auto *D : {&ix->dest[g], &ix->filt[g], &ix->sub_pool[g], &ix->sub_span[g], &ix->share_slot[g],
+                        &ix->share_rec[g], &ix->share_pool[g]}) {
             if (D->d) (void)hipFree(D->d);
             if (D->pin) (void)hipHostFree(D->pin);
             if (D->ev) (void)hipEventDestroy(D->ev);
         }
+        if (ix->share_state[g].d) (void)hipFree(ix->share_state[g].d);
     }
     (void)hipSetDevice(ix->rep[0].device);
     mf_free_keys(ix->mf);
@@ -2698,6 +2714,103 @@ int ensure_dispatch(tm_index *ix, Lane &ln, uint64_t cap, bool offsets) {
     return TM_OK;
 }
 
+// the pick's scratch on a lane (grow-only; freed with the lane): the digit
+// passes' table (the fan-out's), the block counts, and five words per entry
+// below cap -- the ranked entries' slots and the two (slot, q) pair arrays
+int ensure_share(tm_index *ix, Lane &ln, uint64_t cap) {
+    FanoutScratch &f = ln.f;
+    if (!f.tab) {
+        HIPCHK(ix, hipMalloc(&f.tab, (uint64_t)FO_BINS * FO_GRID * 4));
+        HIPCHK(ix, hipMalloc(&f.tot, FO_BINS * 4));
+    }
+    if (!f.sh_cnt && hipMalloc(&f.sh_cnt, (3ull * FO_GRID + 1) * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        f.sh_cnt = nullptr;
+        return fail(ix, TM_ENOMEM, "share pick: no device memory for the pass's block counts (48 KiB)");
+    }
+    if (cap <= f.sh_cap && f.sh_key) return TM_OK;
+    HIPCHK(ix, hipStreamSynchronize(ln.s));   // only this lane's stream uses them
+    if (f.sh_key) (void)hipFree(f.sh_key);
+    f.sh_key = nullptr;
+    f.sh_cap = 0;
+    const uint64_t c = std::max<uint64_t>(std::min<uint64_t>(cap + cap / 4, 0xFFFFFFFFull), 4096);
+    if (hipMalloc(&f.sh_key, c * 20) != hipSuccess) {
+        (void)hipGetLastError();
+        f.sh_key = nullptr;
+        return fail(ix, TM_ENOMEM, "share pick: no device memory for the batch's scratch (20 bytes x cap)");
+    }
+    f.sh_s[0] = f.sh_key + c;
+    f.sh_q[0] = f.sh_key + 2 * c;
+    f.sh_s[1] = f.sh_key + 3 * c;
+    f.sh_q[1] = f.sh_key + 4 * c;
+    f.sh_cap = c;
+    return TM_OK;
+}
+
+// group g's state array holds `need` slots (caller holds ix->mu and
+// ix->dst_mu; the calling thread is on the group's device).  It grows with
+// its contents kept and the new words UNDEF: no pick may still use the old
+// array, so the group's lanes with a batch in flight are waited for first.
+int share_state_grow(tm_index *ix, int g, uint64_t need) {
+    auto &S = ix->share_state[g];
+    if (need <= S.cap) return TM_OK;
+    for (auto &l : ix->lanes)
+        if (ix->rep[l->r].group == g && lane_busy(*l)) HIPCHK(ix, hipEventSynchronize(l->done));
+    const uint64_t c = std::max<uint64_t>(need + need / 2, 4096);
+    uint32_t *nd = nullptr;
+    if (hipMalloc(&nd, c * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ix, TM_ENOMEM, "share state: no device memory for the slots' state words (4 bytes x slots)");
+    }
+    hipError_t e = hipMemset(nd, 0xFF, c * 4);
+    if (e == hipSuccess && S.d) e = hipMemcpy(nd, S.d, S.cap * 4, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // (before any lane's stream reads it)
+    if (e != hipSuccess) {
+        (void)hipFree(nd);
+        HIPCHK(ix, e);
+    }
+    if (S.d) HIPCHK(ix, hipFree(S.d));
+    S.d = nd;
+    S.cap = c;
+    return TM_OK;
+}
+
+// the index's shared-subscription tables on group g, for a pick about to be
+// queued on stream s: the pool, the slot records, the value -> slot table, in
+// one hold of the lock (subs_upload's reason), and the state array grown to
+// the records' slots.  slot_len in values, n_slots in records.
+int share_upload(tm_index *ix, int g, hipStream_t s, const uint32_t *&slot_of, uint64_t &slot_len, const uint32_t *&rec,
+                 uint64_t &n_slots, const uint32_t *&pool, uint64_t &pool_len, uint32_t *&state) {
+    std::lock_guard<std::mutex> dg(ix->dst_mu);
+    if (int rc = table_upload_locked(ix, ix->share_h.pool, ix->share_pool[g], g, s, pool, pool_len)) return rc;
+    if (int rc = table_upload_locked(ix, ix->share_rec_h, ix->share_rec[g], g, s, rec, n_slots)) return rc;
+    if (int rc = table_upload_locked(ix, ix->share_slot_h, ix->share_slot[g], g, s, slot_of, slot_len)) return rc;
+    n_slots /= 4;
+    if (int rc = share_state_grow(ix, g, n_slots)) return rc;
+    state = ix->share_state[g].d;
+    return TM_OK;
+}
+
+// the calling thread's HIP device, put back when the scope ends
+struct DeviceScope {
+    int dev = -1;
+    DeviceScope() { if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; } }
+    ~DeviceScope() { if (dev >= 0) (void)hipSetDevice(dev); }
+};
+
+int group_device(tm_index *ix, int g) {
+    for (int r = 0; r < ix->nrep; r++)
+        if (ix->rep[r].group == g) return ix->rep[r].device;
+    return ix->rep[0].device;
+}
+
+// every batch queued on group g so far is over (caller holds ix->mu)
+int drain_group(tm_index *ix, int g) {
+    for (auto &l : ix->lanes)
+        if (ix->rep[l->r].group == g && lane_busy(*l)) HIPCHK(ix, hipEventSynchronize(l->done));
+    return TM_OK;
+}
+
 // tm_set_dests / tm_set_route_filters: n entries into a host table and every
 // group's dirty range
 int table_set(tm_index *ix, std::vector<uint32_t> &host, tm_index::DestDev *dev, uint64_t n, const uint32_t *values,
@@ -2842,6 +2955,189 @@ int tm_dispatch_dev(tm_index *ix, uint32_t n_dests, const uint64_t *dest_offs, u
     if (!sub_span && (rc = subs_upload(ix, b.grp, b.s, sub_span, span_len, sub_pool, pool_len))) return rc;
     HIPCHK(ix, launch_dispatch(b.ln->f, n_dests, dest_offs, bucket, topic, value, cap, sub_span, span_len, sub_pool,
                                pool_len, out_head, out_offsets, out_topic, out_value, out_sub, out_cap, b.s));
+    return b.done();
+}
+
+int tm_set_share_slots(tm_index *ix, uint64_t n, const uint32_t *values, const uint32_t *slots) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_set_share_slots: null handle");
+    if (n && (!values || !slots)) return fail(ix, TM_EINVAL, "tm_set_share_slots: null buffer");
+    if (!n) return TM_OK;
+    return table_set(ix, ix->share_slot_h, ix->share_slot, n, values, slots,
+                     "tm_set_share_slots: out of host memory (the table has one entry per value up to the largest)");
+}
+
+int tm_set_share_members(tm_index *ix, uint64_t n, const uint32_t *slots, const uint64_t *list_offsets,
+                         const uint32_t *members, const uint32_t *n_local, const uint32_t *meta) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_set_share_members: null handle");
+    if (n && (!slots || !list_offsets || !n_local || !meta))
+        return fail(ix, TM_EINVAL, "tm_set_share_members: null buffer");
+    if (!n) return TM_OK;
+    for (uint64_t i = 0; i < n; i++) {
+        if (slots[i] == NONE) return fail(ix, TM_EINVAL, "tm_set_share_members: slot 0xFFFFFFFF means none");
+        if (list_offsets[i + 1] < list_offsets[i]) return fail(ix, TM_EINVAL, "tm_set_share_members: decreasing offsets");
+        if (list_offsets[i + 1] - list_offsets[i] > 0xFFFFFFFFull)
+            return fail(ix, TM_EINVAL, "tm_set_share_members: a list of more than 2^32 - 1 members");
+    }
+    if (list_offsets[n] > list_offsets[0] && !members) return fail(ix, TM_EINVAL, "tm_set_share_members: null buffer");
+    for (uint64_t k = list_offsets[0]; k < list_offsets[n]; k++)
+        if (members[k] == NONE)
+            return fail(ix, TM_EINVAL, "tm_set_share_members: member id 0xFFFFFFFF means no pick");
+    std::lock_guard<std::mutex> dg(ix->dst_mu);
+    SubPool &sp = ix->share_h;
+    auto &rec = ix->share_rec_h;
+    bool ok = true;
+    uint64_t done = 0, rlo = 0, rhi = 0;
+    try {
+        for (; done < n && ok; done += ok)
+            ok = sp.set(slots[done], members + list_offsets[done],
+                        (uint32_t)(list_offsets[done + 1] - list_offsets[done]));
+        const uint64_t old = rec.size();
+        rec.resize(4 * sp.values(), 0);
+        SubPool::widen(rlo, rhi, old, rec.size());
+    } catch (const std::bad_alloc &) {
+        ok = false;
+    }
+    // (what was written before a failure is written: the device copies follow it)
+    for (uint64_t i = 0; i < done; i++) {
+        const uint64_t at = 4 * (uint64_t)slots[i];
+        if (at + 4 > rec.size()) continue;   // (the records could not grow)
+        rec[at + 2] = n_local[i];
+        rec[at + 3] = meta[i];
+        SubPool::widen(rlo, rhi, at, at + 4);
+    }
+    uint64_t slo, shi, plo, phi;
+    bool whole;
+    sp.take_dirty(slo, shi, plo, phi, whole);
+    if (whole) { slo = 0; shi = sp.span.size(); }
+    for (uint64_t v = slo / 2; v < (shi + 1) / 2 && 4 * v + 4 <= rec.size(); v++) {
+        rec[4 * v] = sp.span[2 * v];
+        rec[4 * v + 1] = sp.span[2 * v + 1];
+    }
+    SubPool::widen(rlo, rhi, 4 * (slo / 2), std::min<uint64_t>(4 * ((shi + 1) / 2), rec.size()));
+    for (int g = 0; g < ix->ngroups; g++) {
+        auto &R = ix->share_rec[g], &P = ix->share_pool[g];
+        SubPool::widen(R.lo, R.hi, rlo, rhi);
+        if (whole) {   // compacted: the pool may have shrunk under an older range
+            P.lo = 0;
+            P.hi = sp.pool.size();
+        } else {
+            SubPool::widen(P.lo, P.hi, plo, phi);
+        }
+    }
+    if (!ok)
+        return fail(ix, TM_ENOMEM, "tm_set_share_members: out of host memory (a record per slot up to the largest, the "
+                                   "lists in a pool of at most 2^32 - 1 words)");
+    return TM_OK;
+}
+
+// (slot, word) pairs in slot order, a slot named twice keeping its last word
+static bool share_sorted(uint64_t n, const uint32_t *slots, const uint32_t *words,
+                         std::vector<std::pair<uint32_t, uint32_t>> &out) {
+    try {
+        out.resize(n);
+    } catch (const std::bad_alloc &) {
+        return false;
+    }
+    for (uint64_t i = 0; i < n; i++) out[i] = {slots[i], words ? words[i] : 0u};
+    std::stable_sort(out.begin(), out.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+    uint64_t k = 0;
+    for (uint64_t i = 0; i < n; i++)
+        if (i + 1 == n || out[i + 1].first != out[i].first) out[k++] = out[i];
+    out.resize(k);
+    return true;
+}
+
+int tm_share_state_set(tm_index *ix, uint64_t n, const uint32_t *slots, const uint32_t *states) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_share_state_set: null handle");
+    if (n && (!slots || !states)) return fail(ix, TM_EINVAL, "tm_share_state_set: null buffer");
+    if (!n) return TM_OK;
+    for (uint64_t i = 0; i < n; i++)
+        if (slots[i] == NONE) return fail(ix, TM_EINVAL, "tm_share_state_set: slot 0xFFFFFFFF means none");
+    std::vector<std::pair<uint32_t, uint32_t>> sw;
+    std::vector<uint32_t> run;
+    if (!share_sorted(n, slots, states, sw)) return fail(ix, TM_ENOMEM, "tm_share_state_set: out of host memory");
+    std::lock_guard<std::mutex> g(ix->mu);
+    std::lock_guard<std::mutex> dg(ix->dst_mu);
+    DeviceScope scope;
+    for (int grp = 0; grp < ix->ngroups; grp++) {
+        HIPCHK(ix, hipSetDevice(group_device(ix, grp)));
+        // after every pick queued so far, before every pick queued later: both sides wait
+        if (int rc = drain_group(ix, grp)) return rc;
+        if (int rc = share_state_grow(ix, grp, (uint64_t)sw.back().first + 1)) return rc;
+        uint32_t *d = ix->share_state[grp].d;
+        // one copy per run of consecutive slots: what is moved is bounded by n, however far apart the slots lie
+        for (size_t i = 0; i < sw.size();) {
+            size_t j = i + 1;
+            while (j < sw.size() && sw[j].first == sw[j - 1].first + 1) j++;
+            run.clear();
+            for (size_t k = i; k < j; k++) run.push_back(sw[k].second);
+            HIPCHK(ix, hipMemcpy(d + sw[i].first, run.data(), (j - i) * 4, hipMemcpyHostToDevice));
+            i = j;
+        }
+        HIPCHK(ix, hipStreamSynchronize(nullptr));
+    }
+    return TM_OK;
+}
+
+int tm_share_state_get(tm_index *ix, uint32_t dev, uint64_t n, const uint32_t *slots, uint32_t *out) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_share_state_get: null handle");
+    if (n && (!slots || !out)) return fail(ix, TM_EINVAL, "tm_share_state_get: null buffer");
+    if ((int64_t)dev >= ix->ngroups) return fail(ix, TM_EINVAL, "tm_share_state_get: no such device entry");
+    if (!n) return TM_OK;
+    std::vector<std::pair<uint32_t, uint32_t>> sw;   // (slot, its word once read)
+    std::vector<uint32_t> run;
+    if (!share_sorted(n, slots, nullptr, sw)) return fail(ix, TM_ENOMEM, "tm_share_state_get: out of host memory");
+    std::lock_guard<std::mutex> g(ix->mu);
+    std::lock_guard<std::mutex> dg(ix->dst_mu);
+    DeviceScope scope;
+    const auto &S = ix->share_state[dev];
+    HIPCHK(ix, hipSetDevice(group_device(ix, (int)dev)));
+    if (int rc = drain_group(ix, (int)dev)) return rc;
+    for (size_t i = 0; i < sw.size();) {   // one copy per run of consecutive slots inside the array
+        if (sw[i].first >= S.cap) {
+            sw[i++].second = NONE;
+            continue;
+        }
+        size_t j = i + 1;
+        while (j < sw.size() && sw[j].first == sw[j - 1].first + 1 && sw[j].first < S.cap) j++;
+        run.resize(j - i);
+        HIPCHK(ix, hipMemcpy(run.data(), S.d + sw[i].first, (j - i) * 4, hipMemcpyDeviceToHost));
+        for (size_t k = i; k < j; k++) sw[k].second = run[k - i];
+        i = j;
+    }
+    for (uint64_t i = 0; i < n; i++) {
+        const auto it = std::lower_bound(sw.begin(), sw.end(), slots[i],
+                                         [](const auto &a, uint32_t v) { return a.first < v; });
+        out[i] = it->second;
+    }
+    return TM_OK;
+}
+
+int tm_share_pick_dev(tm_index *ix, uint32_t n_dests, const uint64_t *dest_offs, const uint32_t *topic,
+                      const uint32_t *value, uint64_t cap, const uint32_t *key_clientid, const uint32_t *key_topic,
+                      uint64_t n_topics, uint32_t seed, const uint32_t *slot_of, uint64_t slot_of_len,
+                      const uint32_t *slot_rec, uint64_t n_slots, const uint32_t *pool, uint64_t pool_len, uint32_t *state,
+                      uint64_t *out_head, uint32_t *out_member, void *stream) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_share_pick_dev: null handle");
+    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_share_pick_dev: n_dests must be 1 .. 65536");
+    if (!dest_offs || !out_head || (cap && (!topic || !value || !out_member)))
+        return fail(ix, TM_EINVAL, "tm_share_pick_dev: null buffer");
+    if (slot_of) {
+        if (n_slots && (!slot_rec || !state))
+            return fail(ix, TM_EINVAL, "tm_share_pick_dev: d_slot_of without d_slot_rec and d_state");
+        if (!pool && pool_len) return fail(ix, TM_EINVAL, "tm_share_pick_dev: d_slot_rec without d_pool");
+        if ((uintptr_t)slot_rec & 15) return fail(ix, TM_EINVAL, "tm_share_pick_dev: d_slot_rec must be 16-byte aligned");
+        if (n_slots > 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_share_pick_dev: more than 2^32 - 1 slots");
+    }
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
+    DevBatch b(ix, stream);
+    int rc;
+    if ((rc = b.open_fanout())) return rc;
+    if ((rc = ensure_share(ix, *b.ln, cap))) return rc;
+    if (!slot_of && (rc = share_upload(ix, b.grp, b.s, slot_of, slot_of_len, slot_rec, n_slots, pool, pool_len, state)))
+        return rc;
+    HIPCHK(ix, launch_share_pick(b.ln->f, n_dests, dest_offs, topic, value, cap, key_clientid, key_topic, n_topics, seed,
+                                 slot_of, slot_of_len, slot_rec, n_slots, pool, pool_len, state, out_head, out_member, b.s));
     return b.done();
 }
 
@@ -3471,6 +3767,45 @@ static int dispatch_scratch(tm_index *ix, Lane &ln, uint64_t vcap, uint64_t want
     return grow_dev(ix, ln.s, ln.d_ds, ln.d_ds_cap, want);
 }
 
+// tm_publish_batch's pick half: the per-topic key words (host, n each, may be
+// null), the seed, and the caller's member array (aligned with out_topic)
+struct RoutePick {
+    const uint32_t *key_clientid, *key_topic;
+    uint32_t seed;
+    uint32_t *out_member;
+};
+
+// queues the shared-subscription pick over the lane's aggregated results (d_ao
+// / d_at / d_av) with the index's own tables and state into d_sm (caller
+// holds ix->mu).  Queued ONCE per call, after the run that stands: the state
+// words move once, and only for entries the caller gets.
+static int queue_pick(tm_index *ix, Lane &ln, uint64_t n, uint32_t n_dests, uint64_t vcap, const RoutePick &pk) {
+    int rc;
+    const hipStream_t s = ln.s;
+    const uint64_t hoff = (vcap + 1) & ~1ull;   // the two head words, 8-byte aligned
+    if ((rc = ensure_share(ix, ln, vcap))) return rc;
+    if ((rc = grow_dev(ix, s, ln.d_sm, ln.d_sm_cap, hoff + 4))) return rc;
+    const uint32_t *kc = nullptr, *kt = nullptr;
+    if (n && (pk.key_clientid || pk.key_topic)) {
+        if ((rc = grow_dev(ix, s, ln.d_sk, ln.d_sk_cap, 2 * n))) return rc;
+        if (pk.key_clientid) {
+            HIPCHK(ix, hipMemcpyAsync(ln.d_sk, pk.key_clientid, n * 4, hipMemcpyHostToDevice, s));
+            kc = ln.d_sk;
+        }
+        if (pk.key_topic) {
+            HIPCHK(ix, hipMemcpyAsync(ln.d_sk + n, pk.key_topic, n * 4, hipMemcpyHostToDevice, s));
+            kt = ln.d_sk + n;
+        }
+    }
+    const uint32_t *slot_of = nullptr, *rec = nullptr, *pool = nullptr;
+    uint64_t slot_len = 0, n_slots = 0, pool_len = 0;
+    uint32_t *state = nullptr;
+    if ((rc = share_upload(ix, ix->rep[ln.r].group, s, slot_of, slot_len, rec, n_slots, pool, pool_len, state))) return rc;
+    HIPCHK(ix, launch_share_pick(ln.f, n_dests, ln.d_ao, ln.d_at, ln.d_av, vcap, kc, kt, n, pk.seed, slot_of, slot_len, rec,
+                                 n_slots, pool, pool_len, state, reinterpret_cast<uint64_t *>(ln.d_sm + hoff), ln.d_sm, s));
+    return TM_OK;
+}
+
 // The lane's fan-out results to the caller (the lock is not held; the lane is
 // still checked out: its buffers are this caller's).  `fo`: n_dests + 2 u64
 // the offsets land in -- the caller's own array, or narrowed into fo32.
@@ -3518,7 +3853,7 @@ static int copy_route_out(tm_index *ix, Lane &ln, uint32_t n_dests, uint64_t tot
 // kernels are queued again.
 static int route_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
                             uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
-                            uint8_t *out_err, uint32_t flags, const RouteDispatch *dp) {
+                            uint8_t *out_err, uint32_t flags, const RouteDispatch *dp, const RoutePick *pk = nullptr) {
     if (!ix) return fail(nullptr, TM_EINVAL, "tm_route_batch: null handle");
     if (flags & ~(uint32_t)TM_ROUTE_AGGRE) return fail(ix, TM_EINVAL, "tm_route_batch: unknown flag");
     const bool aggre = flags & TM_ROUTE_AGGRE;
@@ -3592,6 +3927,20 @@ static int route_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const u
                         out_values);
     if (rc != TM_OK && rc != TM_ECAP) return rc;
     if (out_err && n) std::memcpy(out_err, ln.pin_out + (n + 1) * 8, n);
+    if (pk && aggre && total <= cap) {
+        // the run stands (no scratch grows, no retry is left) and the caller has
+        // the kept entries: the pick is queued now, once, over the arrays still
+        // in the lane; only the copy of its own output can fail after it
+        int prc;
+        if ((prc = hb.relock())) return prc;
+        if ((prc = queue_pick(ix, ln, n, n_dests, vcap, *pk))) return prc;
+        if ((prc = batch_done(ix, ln))) return prc;
+        hb.g.unlock();
+        // (the copy into the caller's pageable buffer may wait for the stream: never under the lock)
+        const uint64_t kept = std::min(out_dest_offsets[n_dests + 1], cap);
+        if (kept) HIPCHK(ix, hipMemcpyAsync(pk->out_member, ln.d_sm, kept * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(ix, hipStreamSynchronize(s));
+    }
     if (dp) {
         dp->out_head[0] = head[0];
         dp->out_head[1] = head[1];
@@ -3623,6 +3972,22 @@ int tm_dispatch_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_
         return fail(ix, TM_EINVAL, "tm_dispatch_batch: null buffer");
     const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
     return route_batch_impl(ix, n, tb, to, n_dests, out_dest_offsets, out_topic, out_values, cap, out_err, flags, &dp);
+}
+
+int tm_publish_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
+                     uint32_t local_dest, uint32_t flags, uint64_t *out_dest_offsets, uint32_t *out_topic,
+                     uint32_t *out_values, uint64_t cap, uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue,
+                     uint32_t *out_dsub, uint64_t dcap, const uint32_t *key_clientid, const uint32_t *key_topic,
+                     uint32_t seed, uint32_t *out_member, uint8_t *out_err) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_publish_batch: null handle");
+    if (!(flags & TM_ROUTE_AGGRE))
+        return fail(ix, TM_EINVAL, "tm_publish_batch: TM_ROUTE_AGGRE is required (aggre/1 runs before route/2)");
+    if (n_dests && local_dest >= n_dests) return fail(ix, TM_EINVAL, "tm_publish_batch: local_dest must be below n_dests");
+    if (!out_head || (dcap && (!out_dtopic || !out_dvalue || !out_dsub)) || (cap && !out_member))
+        return fail(ix, TM_EINVAL, "tm_publish_batch: null buffer");
+    const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
+    const RoutePick pk{key_clientid, key_topic, seed, out_member};
+    return route_batch_impl(ix, n, tb, to, n_dests, out_dest_offsets, out_topic, out_values, cap, out_err, flags, &dp, &pk);
 }
 
 int tm_route_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,

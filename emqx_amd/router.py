@@ -68,7 +68,10 @@ from __future__ import annotations
 import threading
 from collections import namedtuple
 
+import numpy as np
+
 from . import topic_index as ti
+from .shared_sub import pick_batch_ref
 from .trie_search import filter as tfilter, make_key, term_key
 
 Route = namedtuple("Route", "topic dest")
@@ -112,6 +115,7 @@ ROUTER_COPIES = 2   # src/emqx_router_gpu.erl ?COPIES
 MAX_DEST_CLASSES = 65536   # tm_route_batch's n_dests bound; a later class stays unrouted on the device
 UNROUTED = 0xFFFFFFFF
 NO_FILTER = 0xFFFFFFFF     # tm_set_route_filters: never a filter's id
+SHARE_UNDEF = 0xFFFFFFFF   # shared-subscription pick: no slot / no pick / a state never set
 
 
 def dest_class(dest):
@@ -142,7 +146,7 @@ class MirrorDown(RuntimeError):
 
 class Router:
     def __init__(self, node="node", device: int = -1, mirror=None, mirror_factory=None,
-                 route_in_place: bool = False, local_subs=None):
+                 route_in_place: bool = False, local_subs=None, shared_subs=None):
         """route_in_place: match_routes_by_dest goes through the mirror's
         route_kids32 (tm_route_batch32 on pooled pinned buffers: a micro-batch
         is matched and fanned out in place) instead of route_kids, and
@@ -150,9 +154,23 @@ class Router:
         instead of dispatch_kids.
         local_subs: this node's subscribers.LocalSubs; the device list of every
         route key {Filter, node()} then follows it (tm_set_subscribers), for
-        match_routes_dispatch."""
+        match_routes_dispatch.
+        shared_subs: this node's shared_sub.SharedSubs; it adds and deletes its
+        {Topic, {Group, node()}} routes here, every wildcard key {Filter,
+        {Group, Node}} carries its pair's slot to the device (tm_set_share_slots,
+        ahead of the insert), the slots' member lists and state words follow
+        its on_change hook (tm_set_share_members, tm_share_state_set), and
+        match_routes_publish returns the picks.  Exact-topic $share routes stay
+        in the host bag, as exact routes do: their pairs' state words are kept
+        here and their picks made by the same definition on the host."""
         self.node = node
         self.local_subs = local_subs
+        self.shared_subs = shared_subs
+        self._share_host_state: dict = {}        # slot -> state word of an exact-topic pair
+        if shared_subs is not None:
+            shared_subs.router = self
+            shared_subs.on_change = self._share_changed
+            shared_subs.state_reader = self.share_state
         if local_subs is not None:
             local_subs.on_change = self._subs_changed
         self._route_in_place = route_in_place
@@ -255,7 +273,115 @@ class Router:
             mirror.filter_release = self.filter_release
         if hasattr(mirror, "sub_fn") and self.local_subs is not None:
             mirror.sub_fn = self._key_subs
+        if hasattr(mirror, "share_fn") and self.shared_subs is not None:
+            mirror.share_fn = self._key_slot
+            mirror.share_release = self._key_slot_release
+            ss = self.shared_subs   # a fresh mirror is a fresh device table: every live slot anew
+            for slot, pair in enumerate(ss.slot_key):
+                if pair is not None and tfilter(bytes(pair[1])) is not False:
+                    mem, n_local = ss.members(*pair)
+                    mirror.set_share_members(slot, [ss.pid_id(p) for p in mem], n_local, ss.meta(pair[0]))
+                    mirror.set_share_state(slot, ss.device_state(*pair))
         return mirror
+
+    # ------------------------------------------------------ shared subscriptions
+    def _key_slot(self, key):
+        """The slot of a route key {Filter, {Group, Node}}: its {Group, Filter}
+        pair's, interned on first sight (a pair without members yet has an
+        empty list: no pick); None for any other key."""
+        dest = ti.get_id(key)
+        if not (isinstance(dest, tuple) and len(dest) == 2) or dest[0] == "external":
+            return None
+        return self.shared_subs.hold(dest[0], ti.get_topic(key))
+
+    def _key_slot_release(self, key):
+        dest = ti.get_id(key)
+        if isinstance(dest, tuple) and len(dest) == 2 and dest[0] != "external":
+            self.shared_subs.release(dest[0], ti.get_topic(key))
+
+    def _share_wild(self, slot):
+        pair = self.shared_subs.slot_key[slot]
+        return pair is not None and tfilter(bytes(pair[1])) is not False
+
+    def _share_changed(self, slot, ids, n_local, meta, state):
+        """SharedSubs' hook: a wildcard pair's list and state go to the device
+        with the mirror's next flush (ahead of any key inserted in it); an
+        exact-topic pair's state word is kept here."""
+        if not self._share_wild(slot):
+            if state is not None:
+                self._share_host_state[slot] = state
+            return
+        if not self._alive or not hasattr(self._mirror, "set_share_members"):
+            return
+        self._mirror.set_share_members(slot, ids, n_local, meta)
+        if state is not None:
+            self._mirror.set_share_state(slot, state)
+
+    def share_state(self, slot) -> int:
+        """A slot's state word: the device's for a wildcard pair (after every
+        pick queued so far), the host's for an exact-topic one."""
+        if not self._share_wild(slot):
+            return self._share_host_state.get(slot, SHARE_UNDEF)
+        return int(self._live_mirror().share_state([slot])[0])
+
+    def set_share_state(self, slot, word):
+        if not self._share_wild(slot):
+            self._share_host_state[slot] = int(word)
+        else:
+            self._live_mirror().set_share_state(slot, int(word))
+
+    def _host_picks(self, topics, skip, key_clientid, key_topic, seed):
+        """The picks of the bag's exact-topic $share rows, by the device's
+        definition on the host: -> {group: [(message index, To, pid or None)]}."""
+        ss = self.shared_subs
+        entries = []   # (message index, group, slot)
+        for i, t in enumerate(topics):
+            if i in skip:
+                continue
+            seen = set()
+            for r in self.lookup_route_tab(t):
+                if isinstance(r.dest, tuple) and r.dest[0] != "external" and r.dest[0] not in seen:
+                    seen.add(r.dest[0])          # aggre/1: one entry per (To, Group)
+                    entries.append((i, r.dest[0], ss.slot(r.dest[0], t)))
+        out: dict = {}
+        if not entries:
+            return out
+        slots = sorted({s for _, _, s in entries if s is not None})
+        # (R(t, s) hashes the pair's own slot id: the tables are indexed by it, as the device's are)
+        n_slots = max(slots) + 1 if slots else 0
+        full, pool = np.zeros((n_slots, 4), np.uint32), []
+        state = np.full(n_slots, SHARE_UNDEF, np.uint32)
+        for s in slots:
+            mem, n_local = ss.members(*ss.slot_key[s])
+            full[s] = (len(pool), len(mem), n_local, ss.meta(ss.slot_key[s][0]))
+            pool.extend(ss.pid_id(p) for p in mem)
+            state[s] = self._share_host_state.get(s, SHARE_UNDEF)
+        value = np.array([SHARE_UNDEF if s is None else s for _, _, s in entries], np.uint32)
+        topic = np.array([i for i, _, _ in entries], np.uint32)
+        doff = np.array([0, len(entries), len(entries)], np.uint64)
+        member, _, after = pick_batch_ref(1, doff, topic, value, len(entries), np.arange(n_slots, dtype=np.uint32), full,
+                                          np.array(pool, np.uint32), state, key_clientid, key_topic, len(topics), seed)
+        for s in slots:
+            self._share_host_state[s] = int(after[s])
+        for (i, g, _), m in zip(entries, member.tolist()):
+            out.setdefault(g, []).append((i, topics[i], None if m == SHARE_UNDEF else ss.pids[m]))
+        return out
+
+    def match_routes_publish(self, topics, key_clientid=None, key_topic=None, seed: int = 0, errors: str = "raise"):
+        """match_routes_dispatch under aggre/1 plus the shared-subscription
+        pick, in one device call (tm_publish_batch) -> (ByDest, deliveries,
+        picks): picks = {group: [(message index, To, pid or None)]}, ONE member
+        per (message, {Group, To}) -- what emqx_shared_sub:dispatch/3 would pick
+        by the group's strategy (None: {error, no_subscribers}).  In message
+        order; inside a message the bag's exact-topic row first (picked here on
+        the host), then the filter matches in the device's entry order.
+        key_clientid / key_topic: the messages' phash2 words (u32 per message).
+        Needs local_subs and shared_subs."""
+        if self.local_subs is None or self.shared_subs is None:
+            raise ValueError("match_routes_publish: the router needs local_subs and shared_subs")
+        kc = None if key_clientid is None else np.ascontiguousarray(key_clientid, dtype=np.uint32)
+        kt = None if key_topic is None else np.ascontiguousarray(key_topic, dtype=np.uint32)
+        return self._routes_by_dest(topics, errors, True, True, publish=(kc, kt, seed))
 
     # ------------------------------------------------------ local subscribers
     def _key_subs(self, key):
@@ -560,8 +686,9 @@ class Router:
             raise ValueError("match_routes_dispatch: the router has no local_subs")
         return self._routes_by_dest(topics, errors, aggre, True)
 
-    def _routes_by_dest(self, topics, errors, aggre, dispatch):
+    def _routes_by_dest(self, topics, errors, aggre, dispatch, publish=None):
         topics = [bytes(t) for t in topics]
+        member = None
         mirror = self._live_mirror()
         out = ByDest()
         deliveries: list = []
@@ -576,8 +703,11 @@ class Router:
             if dispatch:
                 if local == UNROUTED:
                     raise ValueError("match_routes_dispatch: this node has no destination id")
-                disp = mirror.dispatch_kids32 if self._route_in_place else mirror.dispatch_kids
-                (doff, tidx, kids, err), (dt, dk, ds) = disp(topics, n_dests, local, aggre=aggre)
+                if publish is not None:
+                    (doff, tidx, kids, err), (dt, dk, ds), member = mirror.publish_kids(topics, n_dests, local, *publish)
+                else:
+                    disp = mirror.dispatch_kids32 if self._route_in_place else mirror.dispatch_kids
+                    (doff, tidx, kids, err), (dt, dk, ds) = disp(topics, n_dests, local, aggre=aggre)
                 last = None
                 for j, (i, kid, sub) in enumerate(zip(dt.tolist(), dk.tolist(), ds.tolist())):
                     if last != (i, kid):
@@ -605,6 +735,44 @@ class Router:
                 for r in self.lookup_route_tab(t):
                     groups.setdefault(dest_class(r.dest), {}).setdefault(i, []).append(r)
             tidx, doff = tidx.tolist(), doff.tolist()
+            dev_picks: dict = {}
+            if member is not None:   # one pick per entry of a group, aligned with the entries
+                ss, mk, kid_l, mem_l = self.shared_subs, mirror._keys, kids.tolist(), member.tolist()
+
+                def group_of(q):
+                    """the group of entry q's key (None: a node's or an external route, or a key
+                    deleted since the batch began, which decode drops too)"""
+                    key = mk[kid_l[q]] if kid_l[q] < len(mk) else None
+                    dest = ti.get_id(key) if key is not None else None
+                    if isinstance(dest, tuple) and len(dest) == 2 and dest[0] != "external":
+                        return dest[0], key
+                    return None, key
+
+                for b in range(n_dests + 1):
+                    lo, hi = doff[b], doff[b + 1]
+                    # a routed bucket holds one class: its first live key tells whether that is a
+                    # group, whatever the group's name is made of.  The unrouted bucket (a class
+                    # beyond MAX_DEST_CLASSES) is looked at entry by entry; the device copied it
+                    # whole, so aggre/1 is applied here: a message's first entry per {To, Group}
+                    # stands (the pair's other keys advanced its state word too: the rotation
+                    # skips, it does not repeat).
+                    routed = b < len(classes)
+                    if routed and lo < hi:
+                        first = next((g for g, k in map(group_of, range(lo, hi)) if k is not None), None)
+                        if first is None:
+                            continue
+                    seen = set()
+                    for q in range(lo, hi):
+                        g, key = group_of(q)
+                        if g is None or tidx[q] in out.errors:
+                            continue
+                        to = ti.get_topic(key)
+                        if not routed:
+                            if (tidx[q], to, g) in seen:
+                                continue
+                            seen.add((tidx[q], to, g))
+                        m = mem_l[q]
+                        dev_picks.setdefault(g, []).append((tidx[q], to, None if m == SHARE_UNDEF else ss.pids[m]))
             mixed = set()
             for b in range(n_dests + 1):
                 lo, hi = doff[b], doff[b + 1]
@@ -652,7 +820,14 @@ class Router:
                 # matches/3's order: the reverse of the traversal
                 for to, pids in reversed(dev_del.get(i, ())):
                     deliveries.extend((i, to, p) for p in pids)
-        return out, deliveries
+        if publish is None:
+            return out, deliveries
+        picks = self._host_picks(topics, out.errors, *publish)
+        for g, rows in dev_picks.items():
+            picks.setdefault(g, []).extend(rows)
+        for g in picks:
+            picks[g].sort(key=lambda e: e[0])   # (stable: a message's bag row stays first)
+        return out, deliveries, picks
 
     def topics(self):
         """topics/0 = list_topics_v2 (emqx_router.erl:627-630): the bag's topics,

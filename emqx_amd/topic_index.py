@@ -80,6 +80,21 @@ class Tab:
         self.sub_fn = None
         self._subs: list = []           # pending (kid, [subscriber ids])
         self._with_subs: set = set()    # kids whose device list is not empty
+        # shared-subscription pick on the device: share_fn(key) -> the owner's slot of the
+        # key's {Group, To} pair (None: the key is no shared route), shipped with
+        # tm_set_share_slots in the same flush, ahead of the insert, and cleared with the
+        # key; set_share_members / set_share_state queue a slot's list and state word, which
+        # go up in the same flush ahead of the slots
+        self.share_fn = None
+        # share_release(key): a key that carried a slot is gone.  Called AFTER the table's lock
+        # is dropped: the owner may answer with set_share_members (a pair's last key gone, its
+        # slot emptied), which takes the lock
+        self.share_release = None
+        self._share_gone: list = []     # keys whose release is still owed
+        self._shares: list = []         # pending (kid, slot)
+        self._with_share: set = set()   # kids whose device slot is not "none"
+        self._share_members: list = []  # pending (slot, [member ids], n_local, meta)
+        self._share_states: list = []   # pending (slot, state word)
         self._route_pool: list = []     # route_kids32: idle sets of pinned batch buffers (host_array)
 
     # -- key <-> device encoding
@@ -118,6 +133,8 @@ class Tab:
                 else:
                     self._delete_locked(k)
             self._flush_locked(commit)
+            gone, self._share_gone = self._share_gone, []
+        self._released_shares(gone)
 
     def _flush_locked(self, commit: bool):
         if self._dests:
@@ -131,6 +148,17 @@ class Tab:
         if self._subs:
             subs, self._subs = self._subs, []
             self._index.set_subscribers([k for k, _ in subs], [ids for _, ids in subs])
+        if self._share_members:
+            mem, self._share_members = self._share_members, []
+            self._index.set_share_members([m[0] for m in mem], [m[1] for m in mem], [m[2] for m in mem],
+                                          [m[3] for m in mem])
+        if self._share_states:
+            st, self._share_states = self._share_states, []
+            self._index.share_state_set([x[0] for x in st], [x[1] for x in st])
+        if self._shares:
+            sh = np.array(self._shares, dtype=np.uint32).reshape(-1, 2)
+            self._shares = []
+            self._index.set_share_slots(sh[:, 0], sh[:, 1])
         if not self._ops:
             return
         ops = np.array([o[0] for o in self._ops], dtype=np.uint8)
@@ -164,6 +192,13 @@ class Tab:
     def delete_key(self, key):
         with self._lock:
             self._delete_locked(key)
+            gone, self._share_gone = self._share_gone, []
+        self._released_shares(gone)
+
+    def _released_shares(self, keys):
+        """the owner hears of the deleted keys that carried a slot -- without the lock"""
+        for key in keys:
+            self.share_release(key)
 
     def _insert_locked(self, key, record):
         if key not in self._records:
@@ -177,6 +212,11 @@ class Tab:
                 self._filts.append((kid, self.filter_fn(key)))
             if self.sub_fn is not None:
                 self._set_subs_locked(kid, self.sub_fn(key))
+            if self.share_fn is not None:
+                slot = self.share_fn(key)
+                if slot is not None:
+                    self._shares.append((kid, int(slot)))
+                    self._with_share.add(kid)
             self._queue(_native.TM_OP_INSERT, key, kid)
         self._records[key] = record
 
@@ -189,6 +229,11 @@ class Tab:
             self._keys[kid] = None
             self._released.append(kid)
             self._set_subs_locked(kid, ())   # the key's list goes with it
+            if kid in self._with_share:      # ... and its slot
+                self._with_share.discard(kid)
+                self._shares.append((kid, _native.TM_SHARE_NONE))
+                if self.share_release is not None:
+                    self._share_gone.append(key)
             if self.filter_release is not None:
                 self.filter_release(key)
 
@@ -207,6 +252,35 @@ class Tab:
             kid = self._kid.get(key)
             if kid is not None:
                 self._set_subs_locked(kid, sub_ids)
+
+    def set_share_members(self, slot: int, member_ids, n_local: int, meta: int):
+        """Slot `slot`'s member list (u32s in subscribers/2's order), its local
+        prefix and meta = strategy | init_strategy << 8, shipped with
+        tm_set_share_members at the next flush -- ahead of the slots and the
+        inserts of that flush.  A slot queued twice ships its last list."""
+        with self._lock:
+            self._share_members.append((int(slot), [int(x) for x in member_ids], int(n_local), int(meta)))
+
+    def set_share_state(self, slot: int, state: int):
+        """Slot `slot`'s state word becomes `state` on every device entry
+        (tm_share_state_set), at the next flush, after the members queued before it."""
+        with self._lock:
+            self._share_states.append((int(slot), int(state)))
+
+    def share_state(self, slots, dev: int = 0):
+        """The slots' state words on device entry `dev` (tm_share_state_get), after
+        everything queued here and every pick queued there so far."""
+        self.flush()
+        return self._index.share_state_get(slots, dev)
+
+    def publish_kids(self, topics, n_dests: int, local_dest: int, key_clientid=None, key_topic=None, seed: int = 0):
+        """tm_publish_batch -> (dispatch_kids' two tuples under aggre, member id
+        u32[K]): the picked member of every kept entry (TM_SHARE_NONE: none),
+        with the tables of share_fn / set_share_members."""
+        self.flush()
+        blob, offs = _native.pack_strings(topics)
+        return self._index.publish_batch(blob, offs, n_dests, local_dest, key_clientid=key_clientid,
+                                         key_topic=key_topic, seed=seed)
 
     def attach(self, rows, batch_size: int = 1000) -> int:
         """Boot the device mirror from an existing table (emqx_topic_index_gpu:

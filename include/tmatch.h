@@ -678,6 +678,170 @@ int tm_dispatch_batch32(tm_index *h, uint64_t n, const uint8_t *topic_bytes, con
                         uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
                         uint64_t dcap, uint8_t *out_err);
 
+/* Shared-subscription pick on the device (ABI minor 18): one member per
+ * (message, group).  do_route2/2's third arm hands a {Group, _} destination to
+ * emqx_shared_sub:dispatch/3 (apps/emqx/src/emqx_shared_sub.erl:146-163), which
+ * looks the members of {Group, Topic} up and picks ONE of them by the group's
+ * strategy (pick/6, do_pick/7, pick_subscriber/6: :335-406; the counter of
+ * round_robin_per_group: :514-524).  aggre/1 has already reduced {To, {Group,
+ * Node}} to {To, Group}, one entry per message, so the input is the aggregated
+ * arrays tm_aggre_dev writes; the output is one member (or "no pick") per entry.
+ * FailedSubs, {retry, _}, acks and the redispatch header stay on the host: a
+ * failed send re-enters dispatch/4 there with the failed pid excluded.
+ *
+ * tm_set_share_slots: the index's value -> slot table, a twin of tm_set_dests
+ * (same thread safety, upload discipline and errors).  A slot is the caller's
+ * dense u32 id of a {Group, To} pair; the k routes {To, {Group, Node_i}} of one
+ * pair share one slot.  TM_SHARE_NONE (0xFFFFFFFF): none; a value never set
+ * has none.  Set a value's slot (and the slot's members) before inserting its
+ * key.
+ *
+ * tm_set_share_members: for each i < n slot slots[i] takes the member list
+ * members[list_offsets[i] .. list_offsets[i + 1]) -- interned pids in the order
+ * of subscribers/2, which is what the exact parity of the two round robins and
+ * the two hashes needs; under TM_SHARE_LOCAL (as the strategy, or as sticky's
+ * initial pick) the caller puts the members on this node FIRST instead, since
+ * the device picks among a prefix -- with n_local[i] (how many of the leading
+ * members are local) and meta[i] = strategy | init_strategy << 8
+ * (TM_SHARE_*; init_strategy is sticky's initial pick: TM_SHARE_RANDOM, _LOCAL,
+ * _HASH_CLIENTID or _HASH_TOPIC, anything else picks as TM_SHARE_RANDOM).  A
+ * slot named twice in one call takes its last list.  Member ids must be below
+ * 0xFFFFFFFF, which is "no pick".  The call never touches a slot's state.
+ * Thread safety and uploads as tm_set_subscribers (the lists live in a second
+ * pool of the same kind; a pick takes the pool, the records and the slot table
+ * in one hold of the lock); on the device one 16-byte record (pos, cnt,
+ * n_local, meta) per slot up to the largest one set.  TM_EINVAL before any
+ * work: a null handle, a null buffer with n > 0, decreasing offsets, a list of
+ * more than 2^32 - 1 ids, slot 0xFFFFFFFF, member id 0xFFFFFFFF.  TM_ENOMEM as
+ * tm_set_subscribers.
+ *
+ * tm_share_state_set / tm_share_state_get: one u32 state word per slot,
+ * resident on the device, one array per device entry (`dev`: the position in
+ * tm_create_replicas' device list, 0 after tm_create); it grows with its
+ * contents kept, and a slot never set holds TM_SHARE_UNDEF (0xFFFFFFFF).  What
+ * the word means is the strategy's business (the table below): round_robin's
+ * last idx, round_robin_per_group's counter in [0, cnt], sticky's idx.  set is
+ * seen by every pick queued after it returns, on every device entry, and by
+ * none queued before; get returns the state after every pick queued before it
+ * on that entry (a slot beyond the array: TM_SHARE_UNDEF).  Both wait for the
+ * entry's batches in flight: control-plane calls.  Both move one copy per run
+ * of consecutive slots among those named, so the cost follows n, not the
+ * distance between the slots; the array itself holds 4 bytes per slot up to
+ * the largest one set or named by a record.  With topic-sharded replicas
+ * each device entry advances its OWN state from the messages it is given: the
+ * entries' round robins are independent, as the reference's publishing
+ * processes are.
+ *
+ * tm_share_pick_dev: device buffers, asynchronous on `stream`.  d_slot_of ==
+ * NULL: the index's own tables and state (the six arguments after it are
+ * ignored); else slot_of_len values, n_slots records (16-byte aligned) and
+ * n_slots state words, pool_len pool words.  d_key_clientid / d_key_topic: the
+ * BEAM's phash2 of the message's sender / topic, one word per topic (NULL: all
+ * zero).  cap is clamped to 2^32 - 1.  In numpy:
+ *   E = min(doff[n_dests+1], cap);  t, v = topic[:E], value[:E]
+ *   s = slot_of[v] where v < slot_of_len, else NONE;  s = NONE where s >= n_slots
+ *   pos, cnt, n_local, meta = rec[s];  cnt = 0 where pos + cnt > pool_len
+ *                                      (64-bit sum: such a list is never read)
+ *   n_local = min(n_local, cnt);  strategy = meta & 0xFF
+ *   out_member[q] = 0xFFFFFFFF where s is NONE, cnt == 0 or strategy >= 7; no
+ *     state moves for those
+ *   cnt == 1: out_member[q] = pool[pos]; no state moves, but under
+ *     TM_SHARE_STICKY state[s] = 0
+ *   else the entry is active: k = its rank among the active entries of slot s in
+ *     ascending q, m = their number, c0 = state[s] before the call; all sums in
+ *     64 bits; key_*[t] = 0 for a NULL array or t >= n_topics:
+ *       strategy               idx of rank k                            state[s] after
+ *       ROUND_ROBIN            c0 == UNDEF: (R(~0, s) % cnt + k) % cnt  idx of rank m - 1
+ *                              else (c0 + 1 + k) % cnt
+ *       ROUND_ROBIN_PER_GROUP  (min(c0 == UNDEF ? 0 : c0, cnt) + k)     idx of rank m - 1,
+ *                                % cnt                                    plus 1
+ *       STICKY                 c0 < cnt: c0; else the init_strategy     that idx
+ *                              idx of the rank-0 entry, for every rank
+ *       RANDOM                 R(t_q, s) % cnt                          unchanged
+ *       LOCAL                  n_local == 0: R(t_q, s) % cnt;           unchanged
+ *                              n_local == 1: 0; else R(t_q, s) % n_local
+ *       HASH_CLIENTID          key_clientid[t_q] % cnt                  unchanged
+ *       HASH_TOPIC             key_topic[t_q] % cnt                     unchanged
+ *     out_member[q] = pool[pos + idx]
+ *   head = [entries with a slot, entries with a pick]
+ *   R(a, b): x = seed ^ a * 0x9E3779B1 ^ b * 0x85EBCA77 (u32); x ^= x >> 16;
+ *     x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16
+ * Nothing at or past E is written; the inputs are not modified; no input
+ * position >= E and no pool word >= pool_len is read.  The two round-robin rows
+ * and the two hash rows are the reference's arithmetic exactly, given the same
+ * start state and the same phash2 words (round_robin: Rem = (N + 1) rem Count,
+ * Nth = Rem + 1, a fresh process starting at rand:uniform(Count) - 1;
+ * per_group: ets:update_counter(.., {2, 1, Count, 1}, {.., 0})); random and
+ * local can match it only in distribution.  Two calls on different streams of
+ * one device each apply their whole transition of a slot's state atomically --
+ * one lane per (call, slot) runs a compare-and-swap loop on the word, no block
+ * waits for another -- so the result is that of the two calls in some order.
+ * The rank comes from a stable least-significant-digit-first sort of the active
+ * entries' (slot, q) pairs, ceil(bits(n_slots - 1) / 9) digit passes of the
+ * fan-out's kind over its fixed grid: it does not depend on timing.  The
+ * stream's scratch (kept with the fan-out's, tm_stream_release) holds 20 bytes
+ * x cap, the fan-out's 8 MiB pass table and 48 KiB (TM_ENOMEM if that cannot be
+ * had); size cap from the buffers, as for tm_dispatch_dev.  With the index's
+ * own tables one more thing can wait: when the records name more slots than
+ * the entry's state array holds, the array grows here -- it is copied, so the
+ * call first waits for the entry's batches in flight on every stream (once per
+ * growth by half; every other device-API call waits for nothing).  TM_EINVAL before
+ * any device work: a null handle, a null required pointer, n_dests == 0 or
+ * n_dests > 65536, d_slot_of given with n_slots > 0 but without d_slot_rec or
+ * d_state, d_pool NULL while pool_len > 0, d_slot_rec not 16-byte aligned,
+ * n_slots > 2^32 - 1.
+ *
+ * tm_publish_batch: the host product path -- tm_dispatch_batch plus the pick,
+ * on the same lane.  flags must hold TM_ROUTE_AGGRE (the reference always runs
+ * aggre/1 before route/2): TM_EINVAL without it.  key_clientid / key_topic:
+ * host arrays of n words (may be NULL); out_member has cap words, aligned with
+ * out_topic / out_values: out_member[q] is the pick of kept entry q with the
+ * index's own tables and the state of the device entry the batch ran on; only
+ * the first K = out_dest_offsets[n_dests + 1] words are written.  Everything
+ * else -- the route outputs, the head and the deliveries, TM_ECAP, lanes,
+ * read-your-writes, the retry after a device failure -- is tm_dispatch_batch's
+ * to the letter.  The state advances exactly once per successful call: the
+ * pick is queued once, after the run that stands (a value scratch that grew, a
+ * look-back retry and a delivery scratch that grew all lie before it) and after
+ * the route outputs have reached the caller's buffers.  What can still fail
+ * behind it is the copy of out_member itself and of the deliveries: the call
+ * then returns TM_EDEVICE with the state moved, and the caller reads the words
+ * back (tm_share_state_get) rather than resubmitting blindly.  Snapshots: the
+ * match, the fan-out, aggre/1 and the dispatch see the index and its tables as
+ * of the run; the pick sees the share tables (slots, members, state) as of the
+ * moment it is queued, behind that run -- the index lock is not held in
+ * between, so a tm_set_share_* or tm_share_state_set that returns meanwhile is
+ * seen by the pick though not by the route.  A caller that needs one snapshot
+ * keeps such writes out of a batch's call, as the reference's single
+ * gen_server does for the tables it mirrors.  Under
+ * TM_ECAP from cap (total > cap) no pick is made and no state moves: the
+ * caller resubmits.  Under TM_ECAP from dcap alone the route outputs and the
+ * picks stand.  TM_EINVAL also for a null out_member with cap > 0.  (The
+ * 32-bit in-place form and the NIF's C half follow separately.) */
+#define TM_SHARE_NONE 0xFFFFFFFFu
+#define TM_SHARE_UNDEF 0xFFFFFFFFu
+enum { TM_SHARE_RANDOM = 0, TM_SHARE_ROUND_ROBIN = 1, TM_SHARE_ROUND_ROBIN_PER_GROUP = 2, TM_SHARE_STICKY = 3,
+       TM_SHARE_LOCAL = 4, TM_SHARE_HASH_CLIENTID = 5, TM_SHARE_HASH_TOPIC = 6 };
+int tm_set_share_slots(tm_index *h, uint64_t n, const uint32_t *values, const uint32_t *slots);
+int tm_set_share_members(tm_index *h, uint64_t n, const uint32_t *slots, const uint64_t *list_offsets,
+                         const uint32_t *members, const uint32_t *n_local, const uint32_t *meta);
+int tm_share_state_set(tm_index *h, uint64_t n, const uint32_t *slots, const uint32_t *states);
+int tm_share_state_get(tm_index *h, uint32_t dev, uint64_t n, const uint32_t *slots, uint32_t *out);
+int tm_share_pick_dev(tm_index *h, uint32_t n_dests, const uint64_t *d_dest_offsets,
+                      const uint32_t *d_topic, const uint32_t *d_value, uint64_t cap,
+                      const uint32_t *d_key_clientid, const uint32_t *d_key_topic, uint64_t n_topics,
+                      uint32_t seed,
+                      const uint32_t *d_slot_of, uint64_t slot_of_len,
+                      const uint32_t *d_slot_rec, uint64_t n_slots,
+                      const uint32_t *d_pool, uint64_t pool_len, uint32_t *d_state,
+                      uint64_t *d_out_head, uint32_t *d_out_member, void *stream);
+int tm_publish_batch(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint64_t *topic_offsets,
+                     uint32_t n_dests, uint32_t local_dest, uint32_t flags,
+                     uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                     uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
+                     uint64_t dcap, const uint32_t *key_clientid, const uint32_t *key_topic, uint32_t seed,
+                     uint32_t *out_member, uint8_t *out_err);
+
 /* Release the batch scratch kept for `stream` (after its batches finish);
  * a caller that retires a stream calls this.  No reference counterpart. */
 int tm_stream_release(tm_index *h, void *stream);

@@ -99,6 +99,22 @@ Outputs are compared before anything is timed (identical); the line says which
 leg finished each call (TM_DEBUG_DISPATCH_ONE / _GRID).  --aggre passes
 TM_ROUTE_AGGRE to every leg.  Under TM_LIB naming a library without
 tm_dispatch_batch32 only the last two legs run (the yardstick of an A/B).
+
+--share: the shared-subscription pick (nothing of the first part runs).  The
+batch is matched as pairs, fanned out over 16 uniform destinations and
+aggregated (filter_of[v] = v); the first four destinations are shared groups,
+their values spread over 1,000 and over 1M slots, every slot round_robin with
+2 to 8 members.  tm_share_pick_dev on the aggregated arrays is timed against
+the torch composition on the same arrays -- a stable sort by slot, a segmented
+arange (cummax of the run heads), the gathers and the scatter back; the
+groups' buckets come first, so their bound is handed over as a host integer;
+it does not advance the state words, one pass less than the kernels -- outputs
+compared first (identical).  One JSON line per slot count.  With --small:
+tm_publish_batch beside tm_dispatch_batch (both with TM_ROUTE_AGGRE), host to
+host as above, per batch size; destinations 1 to 4 are groups, one slot per
+value; the figure is publish_minus_dispatch_ms.  Under TM_LIB naming a library
+without tm_publish_batch only tm_dispatch_batch runs (the yardstick of an A/B);
+--dispatch-leg-only times this library the same way, the other side of that A/B.
 """
 import argparse
 import json
@@ -472,6 +488,145 @@ def dispatch_legs(torch, ix, a, s, n, d_blob, d_offs, d_err, total, most, nvals,
           flush=True)
 
 
+def share_legs(torch, ix, a, s, n, d_blob, d_offs, d_err, total, most, nvals, fs_len, n_dests=16, n_groups=4):
+    """--share: tm_share_pick_dev on the batch's aggregated arrays against the torch composition (a stable
+    argsort by slot, a segmented arange, gathers; its bounds handed over as host integers).  The first
+    n_groups of the n_dests destinations are shared groups, every slot round_robin (the reference's
+    default) with 2-8 members; the composition leaves the state words alone -- one pass less than the kernels."""
+    dev = d_blob.device
+    cap_p = total + 4096 * most
+    d_pairs = torch.zeros(2 * n + 2, dtype=torch.int32, device=dev)
+    d_pv = torch.zeros(cap_p, dtype=torch.int32, device=dev)
+    ix.match_batch_dev_pairs(n, d_blob.data_ptr(), d_offs.data_ptr(), d_pairs.data_ptr(), d_pv.data_ptr(), cap_p,
+                             d_err.data_ptr(), s)
+    rng = np.random.default_rng(7)
+    dest_np = rng.integers(0, n_dests, nvals, dtype=np.int64)
+    dest_of = torch.from_numpy(dest_np.astype(np.int32)).to(dev)
+    fof = torch.arange(nvals, dtype=torch.int32, device=dev)
+    fo, ag = ((torch.zeros(n_dests + 2, dtype=torch.int64, device=dev), torch.zeros(total, dtype=torch.int32, device=dev),
+               torch.zeros(total, dtype=torch.int32, device=dev)) for _ in range(2))
+    ix.fanout_dev_pairs(n, d_pairs.data_ptr(), d_pv.data_ptr(), cap_p, n_dests, fo[0].data_ptr(), fo[1].data_ptr(),
+                        fo[2].data_ptr(), dest_of.data_ptr(), nvals, s)
+    ix.aggre_dev(n_dests, fo[0].data_ptr(), fo[1].data_ptr(), fo[2].data_ptr(), total, ag[0].data_ptr(),
+                 ag[1].data_ptr(), ag[2].data_ptr(), fof.data_ptr(), nvals, s)
+    torch.cuda.synchronize()
+    E, Q = int(ag[0][n_dests + 1]), int(ag[0][n_groups])   # the groups' buckets come first: [0, Q) are the active entries
+    for n_slots in (1000, 1_000_000):
+        slot_np = np.where(dest_np < n_groups, rng.integers(0, n_slots, nvals), -1)
+        slot_of = torch.from_numpy(slot_np.astype(np.int32)).to(dev)
+        cnt = rng.integers(2, 9, n_slots)
+        pos = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+        pool_len = int(cnt.sum())
+        rec = torch.from_numpy(np.stack([pos, cnt, np.zeros(n_slots, np.int64), np.full(n_slots, _native.TM_SHARE_ROUND_ROBIN)],
+                                        axis=1).astype(np.int32).reshape(-1)).to(dev)
+        rec4 = rec.view(n_slots, 4)
+        pool = torch.from_numpy(rng.integers(0, 1 << 31, pool_len, dtype=np.int64).astype(np.int32)).to(dev)
+        state0 = torch.from_numpy(rng.integers(0, 8, n_slots, dtype=np.int64).astype(np.int32)).to(dev)
+        state = state0.clone()
+        head = torch.zeros(2, dtype=torch.int64, device=dev)
+        out = torch.full((E,), -1, dtype=torch.int32, device=dev)
+
+        def hip():
+            ix.share_pick_dev(n_dests, ag[0].data_ptr(), ag[1].data_ptr(), ag[2].data_ptr(), total, head.data_ptr(),
+                              out.data_ptr(), n_topics=n, d_slot_of=slot_of.data_ptr(), slot_of_len=nvals,
+                              d_slot_rec=rec.data_ptr(), n_slots=n_slots, d_pool=pool.data_ptr(), pool_len=pool_len,
+                              d_state=state.data_ptr(), stream=s)
+
+        def tor():
+            sl = slot_of[ag[2][:Q].long()].long()
+            ss, order = torch.sort(sl, stable=True)
+            ar = torch.arange(Q, device=dev)
+            first = torch.ones(Q, dtype=torch.bool, device=dev)
+            first[1:] = ss[1:] != ss[:-1]
+            start = torch.cummax(torch.where(first, ar, torch.zeros_like(ar)), 0).values
+            r = rec4[ss]
+            c = r[:, 1].long()
+            idx = (state0[ss].long() + 1 + (ar - start)) % c
+            res = torch.full((E,), -1, dtype=torch.int32, device=dev)
+            res[order] = pool[r[:, 0].long() + idx]
+            return res
+
+        hip()
+        r = tor()
+        torch.cuda.synchronize()
+        assert head.tolist() == [Q, Q] and torch.equal(out, r), f"n_slots {n_slots}: the two paths differ"
+        del r
+        th, tt = timed_pair(torch, hip, tor, a.warmup, a.reps)
+        h, t = stats(th), stats(tt)
+        print(json.dumps({"tool": "fanout_bench", "kind": "share", "filters": fs_len, "topics": n, "entries": E,
+                          "n_dests": n_dests, "groups": n_groups, "active_entries": Q, "n_slots": n_slots,
+                          "digit_passes": (max(n_slots - 1, 0).bit_length() + 8) // 9, "members": [2, 8],
+                          "strategy": "round_robin", "warmup": a.warmup, "reps": a.reps, "hip": h, "torch": t,
+                          "torch_over_hip": round(t["median_ms"] / h["median_ms"], 2),
+                          "hip_ns_per_active_entry": round(h["median_ms"] * 1e6 / max(Q, 1), 4), "identical": True}),
+              flush=True)
+
+
+def small_share(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=0, n_groups=4):
+    """--small --share: tm_publish_batch host to host beside tm_dispatch_batch (both under TM_ROUTE_AGGRE);
+    destinations 1 .. n_groups are shared groups, one slot per value, round_robin, 2-8 members"""
+    import time
+    P = _native._ptr
+    lib, h = ix._lib, ix._h
+    has = hasattr(lib, "tm_publish_batch") and not a.dispatch_leg_only
+    rng = np.random.default_rng(7)
+    cnt = rng.integers(a.subs[0], a.subs[1] + 1, nvals)
+    loffs = np.zeros(nvals + 1, np.uint64)
+    loffs[1:] = np.cumsum(cnt)
+    subs = rng.integers(0, 1 << 31, int(loffs[-1]), dtype=np.int64).astype(np.uint32)
+    vals = np.arange(nvals, dtype=np.uint32)
+    assert lib.tm_set_subscribers(h, nvals, P(vals), P(loffs), P(subs)) == 0
+    if has:
+        dest = np.random.default_rng(7).integers(0, n_dests, nvals)   # (small_batches' destination table)
+        grp = np.nonzero((dest >= 1) & (dest <= n_groups))[0].astype(np.uint32)
+        ix.set_share_slots(grp, np.arange(len(grp), dtype=np.uint32))
+        mc = rng.integers(2, 9, len(grp))
+        moffs = np.zeros(len(grp) + 1, np.uint64)
+        moffs[1:] = np.cumsum(mc)
+        mem = rng.integers(0, 1 << 31, int(moffs[-1]), dtype=np.int64).astype(np.uint32)
+        zero, meta = np.zeros(len(grp), np.uint32), np.full(len(grp), _native.TM_SHARE_ROUND_ROBIN, np.uint32)
+        assert lib.tm_set_share_members(h, len(grp), P(np.arange(len(grp), dtype=np.uint32)), P(moffs), P(mem), P(zero),
+                                        P(meta)) == 0
+    for n in sizes:
+        tp = wl.topics(3, a.filters, n)
+        blob, offs = np.ascontiguousarray(tp.blob), np.ascontiguousarray(tp.offs, dtype=np.uint64)
+        cap = 16 * n + 1024
+        d64, head, err = np.zeros(n_dests + 2, np.uint64), np.zeros(2, np.uint64), np.zeros(n, np.uint8)
+        rc = lib.tm_dispatch_batch(h, n, P(blob), P(offs), n_dests, local, 1, P(d64), None, None, 0, P(head), None, None,
+                                   None, 0, P(err))
+        assert rc in (0, _native.TM_ECAP)
+        dcap = int(head[1]) + 1024
+        t_, v_, m_ = (np.zeros(cap, np.uint32) for _ in range(3))
+        dd = tuple(np.zeros(dcap, np.uint32) for _ in range(3))
+        kc = rng.integers(0, 1 << 32, n, dtype=np.uint32)
+
+        def leg_d():
+            return lib.tm_dispatch_batch(h, n, P(blob), P(offs), n_dests, local, 1, P(d64), P(t_), P(v_), cap, P(head),
+                                         P(dd[0]), P(dd[1]), P(dd[2]), dcap, P(err))
+
+        def leg_p():
+            return lib.tm_publish_batch(h, n, P(blob), P(offs), n_dests, local, 1, P(d64), P(t_), P(v_), cap, P(head),
+                                        P(dd[0]), P(dd[1]), P(dd[2]), dcap, P(kc), P(kc), 1, P(m_), P(err))
+
+        legs = [("dispatch_batch", leg_d)] + ([("publish_batch", leg_p)] if has else [])
+        ms = {k: [] for k, _ in legs}
+        for r in range(warmup + reps):
+            for k, f in legs:
+                t0 = time.perf_counter_ns()
+                assert f() == 0
+                t1 = time.perf_counter_ns()
+                if r >= warmup:
+                    ms[k].append((t1 - t0) * 1e-6)
+        st = {k: dict(stats(v), p50_ms=round(float(np.median(v)), 4)) for k, v in ms.items()}
+        K = int(d64[n_dests + 1])
+        line = {"tool": "fanout_bench", "kind": "small_share", "filters": fs_len, "topics": n, "kept_entries": K,
+                "n_dests": n_dests, "groups": n_groups, "deliveries": int(head[1]), "warmup": warmup, "reps": reps, **st}
+        if has:
+            line["picks"] = int((m_[:K] != 0xFFFFFFFF).sum())
+            line["publish_minus_dispatch_ms"] = round(st["publish_batch"]["p50_ms"] - st["dispatch_batch"]["p50_ms"], 4)
+        print(json.dumps(line), flush=True)
+
+
 def _np_aggre(doff, t, v, fof, n_dests):
     """include/tmatch.h's numpy definition on a whole fan-out"""
     doff = doff.astype(np.int64)
@@ -496,7 +651,7 @@ def small_batches(a, sizes=(64, 1024, 4096, 16384), n_dests=16, warmup=20, reps=
     nvals = int(fs.vals.max()) + 1
     ix.set_dests(np.arange(nvals, dtype=np.uint32), rng.integers(0, n_dests, nvals).astype(np.uint32))
     fof = None
-    if a.aggre:   # one id per distinct filter, in order of first sight
+    if a.aggre or a.share:   # one id per distinct filter, in order of first sight
         ids: dict = {}
         raw = fs.blob.tobytes()
         fof = np.full(nvals, 0xFFFFFFFF, np.uint32)
@@ -507,6 +662,9 @@ def small_batches(a, sizes=(64, 1024, 4096, 16384), n_dests=16, warmup=20, reps=
     ix.sync(None)
     P = _native._ptr
     lib, h = ix._lib, ix._h
+    if a.share:
+        small_share(a, ix, len(fs), nvals, sizes, n_dests, warmup, reps)
+        return
     if a.dispatch:
         small_dispatch(a, ix, len(fs), nvals, sizes, n_dests, warmup, reps)
         return
@@ -694,6 +852,11 @@ def main():
     p.add_argument("--small", action="store_true", help="the NIF's micro-batches, host to host (see above)")
     p.add_argument("--aggre", action="store_true", help="aggre/1 on the device (see above); with --small: a fourth leg")
     p.add_argument("--dispatch", action="store_true", help="local dispatch on the device (see above)")
+    p.add_argument("--share", action="store_true",
+                   help="the shared-subscription pick: tm_share_pick_dev vs the torch composition; with --small: "
+                        "tm_publish_batch beside tm_dispatch_batch, host to host")
+    p.add_argument("--dispatch-leg-only", action="store_true",
+                   help="--small --share: time tm_dispatch_batch alone, as a library without tm_publish_batch is timed")
     p.add_argument("--sizes", type=int, nargs="+", default=None, help="--small: the batch sizes")
     p.add_argument("--dp1-max", type=int, default=None,
                    help="--small --dispatch: TM_DEBUG_DP1_MAX for the dispatch_batch32 leg (default: the compiled bound)")
@@ -728,6 +891,9 @@ def main():
     nvals = int(fs.vals.max()) + 1
     assert int(d_vals[:total].max()) < nvals and int(d_vals[:total].min()) >= 0
     most = int((d_hit[1:] - d_hit[:-1]).max())
+    if a.share:
+        share_legs(torch, ix, a, s, n, d_blob, d_offs, d_err, total, most, nvals, len(fs))
+        return
     if a.dispatch:
         dispatch_legs(torch, ix, a, s, n, d_blob, d_offs, d_err, total, most, nvals, len(fs))
         return
