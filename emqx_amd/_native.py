@@ -31,7 +31,7 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_fanout_dev_pairs", "tm_route_batch32", "tm_set_route_filters", "tm_aggre_dev", "tm_route_batch_ex",
            "tm_route_batch32_ex", "tm_set_subscribers", "tm_dispatch_dev", "tm_dispatch_batch",
            "tm_dispatch_batch32", "tm_set_share_slots", "tm_set_share_members", "tm_share_state_set",
-           "tm_share_state_get", "tm_share_pick_dev", "tm_publish_batch")
+           "tm_share_state_get", "tm_share_pick_dev", "tm_publish_batch", "tm_publish_batch32")
 TM_ALLOC_VRAM = 1
 TM_ROUTE_AGGRE = 1          # tm_route_batch_ex / tm_route_batch32_ex: aggre/1 applied to the buckets
 NO_FILTER = 0xFFFFFFFF      # tm_set_route_filters: no filter known (equal to nothing)
@@ -59,6 +59,7 @@ TM_DEBUG_SUB_COMPACTIONS = 31   # (get only) rewrites of tm_set_subscribers' poo
 TM_DEBUG_DISPATCH_ONE, TM_DEBUG_DISPATCH_GRID = 32, 33   # (get only) dispatch_batch32 calls per finishing leg
 TM_DEBUG_DP1_MAX = 34   # deliveries the one-launch dispatch kernel expands itself (clamped to DP1_DELIVERIES)
 DP1_DELIVERIES = 32768
+TM_DEBUG_PUBLISH_ONE, TM_DEBUG_PUBLISH_GRID = 35, 36   # (get only) publish_batch32 calls per picking leg
 MAX_DESTS = 65536           # tm_fanout_dev / tm_route_batch: n_dests is 1 .. MAX_DESTS
 
 
@@ -158,6 +159,8 @@ def load_library(path: Path | None = None):
         "tm_share_pick_dev": (i32, [vp, u32, vp, vp, vp, u64, vp, vp, u64, u32, vp, u64, vp, u64, vp, u64, vp, vp, vp, vp]),
         "tm_publish_batch": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u32, vp,
                                    vp]),
+        "tm_publish_batch32": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u32, vp,
+                                     vp]),
         "tm_debug_set": (i32, [vp, u32, u64]),
         "tm_debug_get": (i32, [vp, u32, C.POINTER(u64)]),
     }
@@ -730,6 +733,39 @@ class Index:
                                                                  aggre=True)
             return (doff, topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T]), member[:total]
         raise TmError(TM_ECAP, "publish_batch: the totals kept growing")
+
+    def publish_batch32(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, local_dest: int, out, member,
+                        key_clientid=None, key_topic=None, seed: int = 0, cap: int | None = None,
+                        dcap: int | None = None):
+        """tm_publish_batch32: publish_batch with u32 topic offsets in and u32
+        bucket offsets out, over caller-owned buffers.  out: dispatch_batch32's
+        eight arrays; member u32[>= cap]; key_clientid / key_topic: u32[>= n] or
+        None -> (dispatch_batch32's two tuples under aggre, member[:K]) as
+        views.  In place (no staging, one synchronisation) when every array
+        comes from host_array() and the batch is a micro-batch
+        (include/tmatch.h).  Raises TmError(TM_ECAP) when something does not
+        fit: from cap (dest_offsets[n_dests+1] > cap) no pick was made and no
+        state moved; from dcap alone (head[1] > dcap) the picks stand."""
+        n = len(offs) - 1
+        doff, topic, vals, err, head, dt, dv, ds = out
+        if offs.dtype != np.uint32 or doff.dtype != np.uint32 or err.dtype != np.uint8 or head.dtype != np.uint64 \
+                or any(a.dtype != np.uint32 for a in (topic, vals, dt, dv, ds, member)) or len(doff) < n_dests + 2 \
+                or len(err) < n or len(head) < 2:
+            raise ValueError("publish_batch32: u32 offsets and large enough outputs of the right dtype expected")
+        if any(k is not None and (k.dtype != np.uint32 or len(k) < n) for k in (key_clientid, key_topic)):
+            raise ValueError("publish_batch32: one u32 key word per topic")
+        if cap is None:
+            cap = min(len(topic), len(vals), len(member))
+        if dcap is None:
+            dcap = min(len(dt), len(dv), len(ds))
+        if cap > min(len(topic), len(vals), len(member)) or dcap > min(len(dt), len(dv), len(ds)):
+            raise ValueError("publish_batch32: cap / dcap exceeds the output arrays")
+        self._check(self._lib.tm_publish_batch32(self._h, n, _ptr(blob), _ptr(offs), n_dests, local_dest, TM_ROUTE_AGGRE,
+                                                 _ptr(doff), _ptr(topic), _ptr(vals), cap, _ptr(head), _ptr(dt), _ptr(dv),
+                                                 _ptr(ds), dcap, _ptr(key_clientid), _ptr(key_topic), seed, _ptr(member),
+                                                 _ptr(err)))
+        total, T = int(doff[n_dests + 1]), int(head[1])
+        return (doff[: n_dests + 2], topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T]), member[:total]
 
     def release_stream(self, stream: int | None):
         """Drop the batch scratch the library keeps for `stream`."""

@@ -406,6 +406,27 @@ hipError_t launch_share_pick(const FanoutScratch &fs, uint32_t n_dests, const ui
                              const uint32_t *key_topic, uint64_t n_topics, uint32_t seed, const uint32_t *slot_of,
                              uint64_t slot_of_len, const uint32_t *slot_rec, uint64_t n_slots, const uint32_t *pool,
                              uint64_t pool_len, uint32_t *state, uint64_t *head, uint32_t *out_member, hipStream_t s);
+// A micro-batch's pick in ONE launch of ONE workgroup (k_sh_one;
+// tm_publish_batch32): launch_share_pick's definition over what
+// launch_aggre_one left in device memory (u32 offsets, the K <= FO1_ENTRIES
+// kept entries, its status words), out_member[0 .. K) into a buffer that may be
+// mapped host memory and is never read.  The kernel gates itself, since the
+// run that queued it may be run again: it picks and moves state only if
+// status_in[FO1_ST_STATE] == FO1_DONE, status_in[FO1_ST_TOTAL] <= vcap and <=
+// cap, and *fail (the lane's look-back fail word; may be null) is 0; else it
+// writes status[SH1_ST_STATE] = SH1_SKIPPED and nothing else.  Picked:
+// status[SH1_ST_HEAD ..] = the head as two u64 (launch_share_pick's), then
+// status[SH1_ST_STATE] = SH1_PICKED.  status may be mapped host memory
+// (SH1_ST_WORDS words, SH1_ST_HEAD 8-byte aligned).  slot_rec must be 16-byte
+// aligned.  No scratch: the ranks come from a stable sort inside LDS.
+enum { SH1_ST_STATE = 0, SH1_ST_HEAD = 2, SH1_ST_WORDS = 6 };
+enum : uint32_t { SH1_PICKED = 1, SH1_SKIPPED = 2 };
+hipError_t launch_share_one(const uint32_t *status_in, const uint32_t *fail, const uint32_t *dest_offsets, uint32_t n_dests,
+                            const uint32_t *in_topic, const uint32_t *in_value, uint64_t vcap, uint64_t cap,
+                            const uint32_t *key_clientid, const uint32_t *key_topic, uint64_t n_topics, uint32_t seed,
+                            const uint32_t *slot_of, uint64_t slot_of_len, const uint32_t *slot_rec, uint64_t n_slots,
+                            const uint32_t *pool, uint64_t pool_len, uint32_t *state, uint32_t *out_member, uint32_t *status,
+                            hipStream_t s);
 // delta upload: run i copies runs[i].n u32 words from data + runs[i].src to
 // word (dst & PATCH_OFF) of table (dst >> 48), whose device address on the
 // replica being patched is bases.b[table] (the same runs patch every replica)

@@ -124,7 +124,8 @@ struct Lane {
     uint64_t *d_fo = nullptr; uint64_t d_fo_cap = 0;
     // tm_route_batch32 in place: the match's pairs (its values go to d_vals) and
     // the one-launch kernels' status words (mapped pinned: DP1_ST_WORDS, then
-    // the [M, T] of a tm_dispatch_batch32 the grid kernels finished)
+    // the [M, T] of a tm_dispatch_batch32 the grid kernels finished, then
+    // k_sh_one's SH1_ST_WORDS under tm_publish_batch32)
     uint32_t *d_pr = nullptr; uint64_t d_pr_cap = 0;
     uint32_t *fo1_h = nullptr, *fo1_d = nullptr;
     // TM_ROUTE_AGGRE: the aggregated device results of the grid kernels, and the
@@ -349,6 +350,8 @@ struct tm_index {
     std::atomic<uint64_t> route_one{0}, route_grid{0};
     // tm_dispatch_batch32 calls k_dp_one completed / that the grid kernels or the staged path finished
     std::atomic<uint64_t> dispatch_one{0}, dispatch_grid{0};
+    // tm_publish_batch32 calls k_sh_one picked for / that the grid pick or the staged path finished
+    std::atomic<uint64_t> publish_one{0}, publish_grid{0};
     uint64_t dp1_max = DP1_DELIVERIES;   // TM_DEBUG_DP1_MAX: deliveries k_dp_one expands itself
     // The host-batch combiner (small_combined): small in-place 32-bit batches
     // of concurrent callers queue here; up to cmb_leaders callers at a time
@@ -2159,7 +2162,7 @@ struct HostBatch {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 18u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 19u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 
@@ -4133,14 +4136,28 @@ int tm_match_batch32_pairs(tm_index *ix, uint64_t n, const uint8_t *tb, const ui
 // output.  More than dp1_max deliveries (DP1_TOO_LARGE), or more entries than
 // k_fo_one takes: the grid kernels (launch_dispatch) run on the arrays already
 // on the lane and write the deliveries straight into the caller's buffers.
+// pk (tm_publish_batch32; with dp and aggre): out_member and the key arrays lie
+// in tm_host_alloc memory too, and the same queue lambda -- same lock hold, same
+// stream -- takes the share tables (share_upload) and launches ONE more
+// workgroup, k_sh_one, over k_ag_one's entries on the lane.  The run may be run
+// again (a value scratch that grows, a look-back retry), so k_sh_one gates
+// itself on the device (tm_dev.h launch_share_one) and reports into the lane's
+// status block; on the run that stands the host requires "picked" exactly when
+// total <= cap and the fan-out completed.  DP1_TOO_LARGE: the picks are made,
+// the grid dispatch finishes the deliveries.  More entries than k_fo_one takes:
+// the grid kernels as without pk, then queue_pick once, as route_batch_impl.
 constexpr int ROUTE32_OTHER = 1;   // (not a TM_ code)
 constexpr int DP1_GRID_HEAD = DP1_ST_WORDS;   // status word of the [M, T] a grid dispatch leaves (8-byte aligned)
-constexpr int DP1_HOST_WORDS = DP1_GRID_HEAD + 4;
+constexpr int SH1_HOST = DP1_GRID_HEAD + 4;   // k_sh_one's status words (its head 8-byte aligned)
+constexpr int DP1_HOST_WORDS = SH1_HOST + SH1_ST_WORDS;
 static_assert(DP1_GRID_HEAD % 2 == 0, "the grid dispatch's head is two u64");
+static_assert((SH1_HOST + SH1_ST_HEAD) % 2 == 0, "the pick's head is two u64");
 
 static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint64_t nbytes,
                             uint32_t n_dests, uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
-                            uint64_t cap, uint8_t *out_err, bool aggre, const RouteDispatch *dp = nullptr) {
+                            uint64_t cap, uint8_t *out_err, bool aggre, const RouteDispatch *dp = nullptr,
+                            const RoutePick *pk = nullptr) {
+    if (pk && !(dp && aggre)) return ROUTE32_OTHER;   // (the pick runs over k_ag_one's entries, beside k_dp_one)
     HostBatch hb(ix);
     bool ok = tb || !nbytes;
     uint8_t *db = opt_dev(ix, tb, nbytes, ok);
@@ -4154,6 +4171,9 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     uint32_t *ddt = dp ? reinterpret_cast<uint32_t *>(opt_dev(ix, dp->out_topic, dcap * 4, ok)) : nullptr;
     uint32_t *ddv = dp ? reinterpret_cast<uint32_t *>(opt_dev(ix, dp->out_value, dcap * 4, ok)) : nullptr;
     uint32_t *dds = dp ? reinterpret_cast<uint32_t *>(opt_dev(ix, dp->out_sub, dcap * 4, ok)) : nullptr;
+    uint32_t *dsm = pk ? reinterpret_cast<uint32_t *>(opt_dev(ix, pk->out_member, cap * 4, ok)) : nullptr;
+    const uint32_t *dkc = pk ? reinterpret_cast<const uint32_t *>(opt_dev(ix, pk->key_clientid, n * 4, ok)) : nullptr;
+    const uint32_t *dkt = pk ? reinterpret_cast<const uint32_t *>(opt_dev(ix, pk->key_topic, n * 4, ok)) : nullptr;
     if (!ok || !de || (dp && !dhd)) return ROUTE32_OTHER;
     int rc;
     if ((rc = hb.open(n + (uint64_t)SMALL_SEGS * SM_TOPICS))) return rc;
@@ -4199,6 +4219,7 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
             uint64_t dlen = 0, flen = 0;
             if ((rc = dest_upload(ix, grp, s, dtab, dlen))) return rc;
             st[FO1_ST_STATE] = 0;   // (the lane's stream is idle: nothing else writes the words)
+            st[SH1_HOST + SH1_ST_STATE] = 0;
             uint32_t *fo32 = reinterpret_cast<uint32_t *>(dfo), *t32 = reinterpret_cast<uint32_t *>(dt),
                      *v32 = reinterpret_cast<uint32_t *>(dv);
             if (!aggre && !dp) {
@@ -4227,6 +4248,15 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
             HIPCHK(ix, launch_dispatch_one(st_dev, lfo, ln.d_ft, ln.d_fv, lao, ln.d_at, ln.d_av, n_dests, dp->local_dest,
                                            span, span_len, pool, pool_len, fo32, t32, v32, cap, dhd, ddt, ddv, dds, dcap,
                                            ix->dp1_max, ln.fo1_d, s));
+            if (pk) {   // the share tables of this very run's snapshot; the kernel gates itself (the run may not stand)
+                const uint32_t *slot_of = nullptr, *rec = nullptr, *spool = nullptr;
+                uint64_t slot_len = 0, n_slots = 0, spool_len = 0;
+                uint32_t *state = nullptr;
+                if ((rc = share_upload(ix, grp, s, slot_of, slot_len, rec, n_slots, spool, spool_len, state))) return rc;
+                HIPCHK(ix, launch_share_one(st_dev, n ? ln.w.hint_d + HINT_FAIL : nullptr, lao, n_dests, ln.d_at, ln.d_av,
+                                            vcap, cap, dkc, dkt, n, pk->seed, slot_of, slot_len, rec, n_slots, spool,
+                                            spool_len, state, dsm, ln.fo1_d + SH1_HOST, s));
+            }
             return TM_OK;
         });
         if (rc) return rc;
@@ -4237,6 +4267,14 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
         if ((rc = hb.relock())) return rc;
     }
     const uint32_t state = st[FO1_ST_STATE];
+    if (pk) {
+        // the run stands: k_sh_one picked (and moved the state, once) exactly when the caller gets the entries
+        const uint32_t ps = st[SH1_HOST + SH1_ST_STATE];
+        const bool want = total <= cap && (state == FO1_DONE || state == (uint32_t)DP1_TOO_LARGE);
+        if ((ps != SH1_PICKED && ps != SH1_SKIPPED) || (ps == SH1_PICKED) != want)
+            return fail(ix, TM_EDEVICE, "tm_publish_batch32: the pick kernel and the host disagree on whether the run stands");
+        if (want) ix->publish_one++;
+    }
     if (state == FO1_DONE) {
         if (!dp) {
             ix->route_one++;
@@ -4296,6 +4334,17 @@ static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     hb.g.unlock();
     rc = copy_route_out(ix, ln, n_dests, total, cap, aggre, ag_out, fo.data(), out_dest_offsets, out_topic, out_values);
     if (rc != TM_OK && rc != TM_ECAP) return rc;
+    if (pk && ag_out) {
+        // the route outputs are out and the caller has the kept entries: the grid pick, once (route_batch_impl's rule)
+        if ((rc = hb.relock())) return rc;
+        if ((rc = queue_pick(ix, ln, n, n_dests, vcap, *pk))) return rc;
+        if ((rc = batch_done(ix, ln))) return rc;
+        hb.g.unlock();
+        const uint64_t kept = std::min(fo[n_dests + 1], cap);
+        if (kept) HIPCHK(ix, hipMemcpyAsync(pk->out_member, ln.d_sm, kept * 4, hipMemcpyDefault, s));
+        HIPCHK(ix, hipStreamSynchronize(s));
+    }
+    if (pk) ix->publish_grid++;
     if (dp) return grid_head();
     ix->route_grid++;
     return rc;
@@ -4378,6 +4427,52 @@ int tm_dispatch_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint3
     if (rc != TM_OK && rc != TM_ECAP) return rc;
     for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
     ix->dispatch_grid++;
+    return rc;
+}
+
+// tm_publish_batch with 32-bit offsets (include/tmatch.h): in place under
+// tm_dispatch_batch32's conditions when out_member and the key arrays given lie
+// in tm_host_alloc memory too; every other batch widened, run by
+// tm_publish_batch, and narrowed.
+int tm_publish_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint32_t n_dests,
+                       uint32_t local_dest, uint32_t flags, uint32_t *out_dest_offsets, uint32_t *out_topic,
+                       uint32_t *out_values, uint64_t cap, uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue,
+                       uint32_t *out_dsub, uint64_t dcap, const uint32_t *key_clientid, const uint32_t *key_topic,
+                       uint32_t seed, uint32_t *out_member, uint8_t *out_err) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_publish_batch32: null handle");
+    if (flags & ~(uint32_t)TM_ROUTE_AGGRE) return fail(ix, TM_EINVAL, "tm_publish_batch32: unknown flag");
+    if (!(flags & TM_ROUTE_AGGRE))
+        return fail(ix, TM_EINVAL, "tm_publish_batch32: TM_ROUTE_AGGRE is required (aggre/1 runs before route/2)");
+    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_publish_batch32: n_dests must be 1 .. 65536");
+    if (local_dest >= n_dests) return fail(ix, TM_EINVAL, "tm_publish_batch32: local_dest must be below n_dests");
+    if (!to || !out_dest_offsets || !out_err || (cap && (!out_topic || !out_values || !out_member)) || !out_head ||
+        (dcap && (!out_dtopic || !out_dvalue || !out_dsub)))
+        return fail(ix, TM_EINVAL, "tm_publish_batch32: null buffer");
+    if ((uintptr_t)out_head & 7) return fail(ix, TM_EINVAL, "tm_publish_batch32: out_head must be 8-byte aligned");
+    if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_publish_batch32: batch too large");
+    const uint64_t nbytes = n ? to[n] : 0;   // (before the lock: in TM_ALLOC_VRAM memory a host read is a PCIe round trip)
+    if (n && !tb && nbytes != to[0]) return fail(ix, TM_EINVAL, "tm_publish_batch32: null buffer");
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
+    if (n <= FO1_TOPICS && n_dests <= FO1_MAX_DESTS && ((uintptr_t)tb & 15) == 0) {
+        const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
+        const RoutePick pk{key_clientid, key_topic, seed, out_member};
+        const int rc = route32_in_place(ix, n, tb, to, nbytes, n_dests, out_dest_offsets, out_topic, out_values, cap,
+                                        out_err, true, &dp, &pk);
+        if (rc != ROUTE32_OTHER) return rc;
+    }
+    static thread_local std::vector<uint64_t> o64, fo;
+    try {
+        o64.assign(to, to + n + 1);
+        fo.resize((uint64_t)n_dests + 2);
+    } catch (const std::bad_alloc &) {
+        return fail(ix, TM_ENOMEM, "tm_publish_batch32: out of host memory");
+    }
+    const int rc = tm_publish_batch(ix, n, tb, o64.data(), n_dests, local_dest, flags, fo.data(), out_topic, out_values,
+                                    cap, out_head, out_dtopic, out_dvalue, out_dsub, dcap, key_clientid, key_topic, seed,
+                                    out_member, out_err);
+    if (rc != TM_OK && rc != TM_ECAP) return rc;
+    for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
+    ix->publish_grid++;
     return rc;
 }
 
@@ -4546,6 +4641,8 @@ int tm_debug_get(tm_index *ix, uint32_t key, uint64_t *value) {
     case TM_DEBUG_ROUTE_GRID: *value = ix->route_grid.load(); break;
     case TM_DEBUG_DISPATCH_ONE: *value = ix->dispatch_one.load(); break;
     case TM_DEBUG_DISPATCH_GRID: *value = ix->dispatch_grid.load(); break;
+    case TM_DEBUG_PUBLISH_ONE: *value = ix->publish_one.load(); break;
+    case TM_DEBUG_PUBLISH_GRID: *value = ix->publish_grid.load(); break;
     case TM_DEBUG_DP1_MAX: {
         std::lock_guard<std::mutex> g(ix->mu);
         *value = ix->dp1_max;

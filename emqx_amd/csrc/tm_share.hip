@@ -121,6 +121,55 @@ __device__ __forceinline__ uint32_t sh_stateless(const ShareTabs &T, uint32_t st
     }
 }
 
+// one entry's mark: value -> slot -> record.  An entry that needs no rank gets
+// its member (NONE: no pick); `ranked`: a stateful strategy with cnt >= 2
+__device__ __forceinline__ void sh_mark_entry(const ShareTabs &T, uint32_t v, uint32_t t, uint32_t *state, uint32_t &s,
+                                              uint32_t &member, bool &ranked, bool &picked) {
+    if (v < T.slot_of_len) s = T.slot_of[v];
+    if (s >= T.n_slots) s = SH_NONE;
+    if (s == SH_NONE) return;
+    uint32_t pos, cnt, nl, meta;
+    sh_record(T, s, pos, cnt, nl, meta);
+    const uint32_t strat = meta & 0xFFu;
+    if (!cnt || strat >= SH_STRATEGIES) return;
+    picked = true;
+    if (cnt == 1) {
+        member = T.pool[pos];
+        if (strat == SH_STICKY) state[s] = 0u;   // (every entry of s stores the same word)
+    } else if (strat == SH_ROUND_ROBIN || strat == SH_ROUND_ROBIN_PER_GROUP || strat == SH_STICKY) {
+        ranked = true;
+    } else {
+        member = T.pool[(uint64_t)pos + sh_stateless(T, strat, t, s, cnt, nl)];
+    }
+}
+
+// slot s's whole transition for a call with m = last + 1 ranked entries, in one
+// compare-and-swap loop on the state word: -> the idx of rank 0.  topic0(): the
+// topic of the rank-0 entry (sticky's initial pick; asked for only then)
+template <class Topic0>
+__device__ __forceinline__ uint32_t sh_transition(const ShareTabs &T, uint32_t *state, uint32_t s, uint32_t cnt, uint32_t nl,
+                                                  uint32_t meta, uint64_t last, Topic0 topic0) {
+    const uint32_t strat = meta & 0xFFu;
+    uint32_t b0 = 0;
+    for (;;) {
+        const uint32_t c = __hip_atomic_load(&state[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint32_t nw;
+        if (strat == SH_ROUND_ROBIN) {
+            b0 = c == SH_NONE ? sh_hash(T.seed, SH_NONE, s) % cnt : (uint32_t)(((uint64_t)c + 1) % cnt);
+            nw = (uint32_t)((b0 + last) % cnt);
+        } else if (strat == SH_ROUND_ROBIN_PER_GROUP) {
+            const uint32_t c00 = c == SH_NONE ? 0u : c;
+            b0 = (c00 < cnt ? c00 : cnt) % cnt;
+            nw = (uint32_t)((b0 + last) % cnt) + 1u;
+        } else {   // SH_STICKY
+            b0 = c < cnt ? c : sh_stateless(T, (meta >> 8) & 0xFFu, topic0(), s, cnt, nl);
+            nw = b0;
+        }
+        if (nw == c || atomicCAS(&state[s], c, nw) == c) break;
+    }
+    return b0;
+}
+
 __global__ __launch_bounds__(64) void k_sh_mark(const uint64_t *doff, uint32_t n_dests, uint64_t cap, const uint32_t *in_t,
                                                 const uint32_t *in_v, ShareTabs T, uint32_t *state, uint32_t *out_member,
                                                 uint32_t *key, uint32_t *blk_cnt) {
@@ -134,25 +183,7 @@ __global__ __launch_bounds__(64) void k_sh_mark(const uint64_t *doff, uint32_t n
         uint32_t s = SH_NONE, member = SH_NONE;
         bool ranked = false, picked = false;
         if (ok) {
-            const uint32_t v = in_v[q], t = in_t[q];
-            if (v < T.slot_of_len) s = T.slot_of[v];
-            if (s >= T.n_slots) s = SH_NONE;
-            if (s != SH_NONE) {
-                uint32_t pos, cnt, nl, meta;
-                sh_record(T, s, pos, cnt, nl, meta);
-                const uint32_t strat = meta & 0xFFu;
-                if (cnt && strat < SH_STRATEGIES) {
-                    picked = true;
-                    if (cnt == 1) {
-                        member = T.pool[pos];
-                        if (strat == SH_STICKY) state[s] = 0u;   // (every entry of s stores the same word)
-                    } else if (strat == SH_ROUND_ROBIN || strat == SH_ROUND_ROBIN_PER_GROUP || strat == SH_STICKY) {
-                        ranked = true;
-                    } else {
-                        member = T.pool[(uint64_t)pos + sh_stateless(T, strat, t, s, cnt, nl)];
-                    }
-                }
-            }
+            sh_mark_entry(T, in_v[q], in_t[q], state, s, member, ranked, picked);
             if (!ranked) out_member[q] = member;
             key[q] = ranked ? s : SH_NONE;
         }
@@ -340,31 +371,11 @@ __global__ __launch_bounds__(64) void k_sh_state(const uint32_t *blk_cnt, const 
         uint32_t pos, cnt, nl, meta;
         sh_record(T, s, pos, cnt, nl, meta);
         if (cnt < 2) { base0[st] = 0; continue; }   // (never: k_sh_mark ranked this slot)
-        const uint32_t strat = meta & 0xFFu;
         const uint64_t last = (uint64_t)p - st;   // rank m - 1
-        uint32_t b0 = 0;
-        for (;;) {
-            const uint32_t c = __hip_atomic_load(&state[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            uint32_t nw;
-            if (strat == SH_ROUND_ROBIN) {
-                b0 = c == SH_NONE ? sh_hash(T.seed, SH_NONE, s) % cnt : (uint32_t)(((uint64_t)c + 1) % cnt);
-                nw = (uint32_t)((b0 + last) % cnt);
-            } else if (strat == SH_ROUND_ROBIN_PER_GROUP) {
-                const uint32_t c00 = c == SH_NONE ? 0u : c;
-                b0 = (c00 < cnt ? c00 : cnt) % cnt;
-                nw = (uint32_t)((b0 + last) % cnt) + 1u;
-            } else {   // SH_STICKY
-                if (c < cnt) {
-                    b0 = c;
-                } else {
-                    const uint32_t q0 = Q[st];   // the rank-0 entry
-                    const uint32_t t = q0 < Ein ? in_t[q0] : 0u;
-                    b0 = sh_stateless(T, (meta >> 8) & 0xFFu, t, s, cnt, nl);
-                }
-                nw = b0;
-            }
-            if (nw == c || atomicCAS(&state[s], c, nw) == c) break;
-        }
+        const uint32_t b0 = sh_transition(T, state, s, cnt, nl, meta, last, [&]() -> uint32_t {
+            const uint32_t q0 = Q[st];   // the rank-0 entry
+            return q0 < Ein ? in_t[q0] : 0u;
+        });
         base0[st] = b0;
     }
 }
@@ -391,7 +402,269 @@ __global__ __launch_bounds__(64) void k_sh_pick(const uint32_t *blk_cnt, const u
     }
 }
 
+// ---- a micro-batch (tm_publish_batch32): ONE workgroup of FO1_BLOCK threads
+// picks for the K <= FO1_ENTRIES aggregated entries k_ag_one left on the lane
+// (u32 offsets), launch_share_pick's definition to the letter.
+//   gate   the run that queued this launch may be run again, so the kernel
+//          picks (and moves state) only when that run stands: the fan-out
+//          completed, the value scratch held the batch (total <= vcap), the
+//          caller has room (total <= cap) and the lane's fail word is down;
+//          else it writes SH1_SKIPPED and nothing more;
+//   mark   wave w owns the entries [w * C, (w + 1) * C), C = ceil(K / 16)
+//          rounded up to 64: sh_mark_entry; s_key[q] = the member of an entry
+//          that needs no rank, the slot of one that does (its bit in s_bal);
+//   rank   the ranked entries' q, compacted in q order as 16-bit indices, sorted
+//          by slot: stable digit passes of 8 bits, least significant first, as
+//          many as the largest slot present has digits (k_fo_one's pass: a row
+//          of bins per wave, the scan over waves then bins, the peer-mask
+//          scatter) between two index arrays -- sorted by (slot, q) whatever
+//          the timing; the run heads' running maximum gives every position its
+//          run's first;
+//   pick   the LAST position of a run applies sh_transition and leaves the idx
+//          of rank 0 in s_key at the run's rank-0 entry; every position gathers
+//          its member, and s_key[0 .. K) goes out to out_member (mapped host
+//          memory: consecutive threads, consecutive words, never read).
+// status (mapped host memory): [SH1_ST_STATE], [SH1_ST_HEAD ..] = the head as
+// two u64.  LDS: 64 KiB keys + 2 x 32 KiB indices + 16 KiB bins + 2 KiB bits.
+constexpr uint32_t SH1_WAVES = FO1_BLOCK / 64;
+constexpr uint32_t SH1_STEPS = FO1_ENTRIES / FO1_BLOCK;   // 64-entry steps of a wave, at most
+constexpr uint32_t SH1_BINS = 256;
+constexpr uint32_t SH1_NOF = 0xFFFFu;                     // "no run head in my chunk before me"
+static_assert(FO1_ENTRIES <= SH1_NOF, "k_sh_one: positions are staged as 16 bits");
+static_assert(SH1_BINS <= FO1_BLOCK && SH1_BINS % 64 == 0, "k_sh_one: one thread per bin, whole waves of them");
+
+__device__ __forceinline__ void sh_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the first position of p's run: what the wave's scan left, or the last head of the nearest wave before it that saw one
+__device__ __forceinline__ uint32_t sh1_first(const uint16_t *F, const uint32_t *s_wt, uint32_t p, uint32_t wv) {
+    uint32_t f = F[p];
+    if (f != SH1_NOF) return f;
+    f = 0;   // (position 0 is a head: some wave before this one saw it)
+    for (uint32_t q = wv; q-- > 0;)
+        if (s_wt[q]) { f = s_wt[q] - 1; break; }
+    return f;
+}
+
+__global__ __launch_bounds__(FO1_BLOCK) void k_sh_one(const uint32_t *st_in, const uint32_t *fail, const uint32_t *doff,
+                                                      uint32_t n_dests, const uint32_t *in_t, const uint32_t *in_v,
+                                                      uint64_t vcap, uint64_t cap, ShareTabs T, uint32_t *state,
+                                                      uint32_t *out_member, uint32_t *status) {
+    __shared__ uint32_t s_key[FO1_ENTRIES];
+    __shared__ __attribute__((aligned(4))) uint16_t s_ix[2][FO1_ENTRIES];
+    __shared__ uint32_t s_h[SH1_WAVES * SH1_BINS];
+    __shared__ uint64_t s_bal[FO1_ENTRIES / 64];
+    __shared__ uint32_t s_wt[SH1_WAVES];
+    __shared__ uint32_t s_bw[SH1_BINS / 64];
+    __shared__ uint32_t s_red[3];   // the largest ranked slot, the entries with a slot, with a pick
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t fo_state = st_in[FO1_ST_STATE], total = st_in[FO1_ST_TOTAL];
+    const uint32_t failed = fail ? __hip_atomic_load(fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
+    if (fo_state != FO1_DONE || total > vcap || total > cap || failed || n_dests > FO1_MAX_DESTS) {   // (block-uniform)
+        if (tid == 0) status[SH1_ST_STATE] = SH1_SKIPPED;
+        return;
+    }
+    uint32_t K = doff[n_dests + 1];
+    if (K > FO1_ENTRIES) K = FO1_ENTRIES;   // (never: k_fo_one completed)
+    if (K > cap) K = (uint32_t)cap;         // (never: K <= total <= cap)
+    if (tid < 3) s_red[tid] = 0;
+    __syncthreads();
+    // ---- mark
+    const uint32_t C = ((K + SH1_WAVES - 1) / SH1_WAVES + 63) & ~63u;   // (<= 64 * SH1_STEPS)
+    const uint32_t c0 = wv * C < K ? wv * C : K, c1 = c0 + C < K ? c0 + C : K;
+    uint32_t n_rank = 0, n_slot = 0, n_pick = 0, smax = 0;
+    for (uint32_t q0 = c0; q0 < c1; q0 += 64) {
+        const uint32_t q = q0 + lane;
+        const bool ok = q < c1;
+        uint32_t s = SH_NONE, member = SH_NONE;
+        bool ranked = false, picked = false;
+        if (ok) {
+            sh_mark_entry(T, in_v[q], in_t[q], state, s, member, ranked, picked);
+            s_key[q] = ranked ? s : member;
+        }
+        const uint64_t m = __ballot(ranked);
+        if (lane == 0) s_bal[q0 >> 6] = m;   // (c0 is a multiple of 64 here: c0 < c1)
+        n_rank += (uint32_t)__popcll(m);
+        n_slot += (uint32_t)__popcll(__ballot(ok && s != SH_NONE));
+        n_pick += (uint32_t)__popcll(__ballot(picked));
+        if (ranked && s > smax) smax = s;
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {
+        const uint32_t y = __shfl_xor(smax, d, 64);
+        if (y > smax) smax = y;
+    }
+    if (lane == 0) {
+        s_wt[wv] = n_rank;
+        atomicMax(&s_red[0], smax);
+        atomicAdd(&s_red[1], n_slot);
+        atomicAdd(&s_red[2], n_pick);
+    }
+    __syncthreads();
+    // ---- rank: the ranked entries' q in q order ...
+    uint32_t base = 0, N = 0;
+    for (uint32_t q = 0; q < SH1_WAVES; q++) {
+        if (q < wv) base += s_wt[q];
+        N += s_wt[q];
+    }
+    for (uint32_t q0 = c0; q0 < c1; q0 += 64) {
+        const uint64_t m = s_bal[q0 >> 6];
+        if ((m >> lane) & 1ull) s_ix[0][base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(q0 + lane);
+        base += (uint32_t)__popcll(m);
+    }
+    const uint32_t top = s_red[0];
+    uint32_t passes = N > 1 ? (32u - (uint32_t)__clz(top | 1u) + 7u) / 8u : 0u;   // (one entry is sorted)
+    if (top == 0) passes = 0;                                                     // (so is one slot, 0)
+    __syncthreads();
+    // ... sorted by slot.  Wave w owns the positions [w * D, (w + 1) * D) of [0, N)
+    const uint32_t D = ((N + SH1_WAVES - 1) / SH1_WAVES + 63) & ~63u;
+    const uint32_t d0 = wv * D < N ? wv * D : N, d1 = d0 + D < N ? d0 + D : N;
+    uint32_t *my_h = s_h + wv * SH1_BINS;
+    uint32_t cur = 0;
+    for (uint32_t pass = 0, shift = 0; pass < passes; pass++, shift += 8, cur ^= 1) {   // (block-uniform)
+        const uint16_t *src = s_ix[cur];
+        uint16_t *dst_ix = s_ix[cur ^ 1];
+        for (uint32_t i = tid; i < SH1_WAVES * SH1_BINS; i += FO1_BLOCK) s_h[i] = 0;
+        __syncthreads();
+        for (uint32_t p0 = d0; p0 < d1; p0 += 64) {
+            const uint32_t p = p0 + lane;
+            if (p < d1) atomicAdd(&my_h[(s_key[src[p]] >> shift) & (SH1_BINS - 1)], 1u);
+        }
+        __syncthreads();
+        // bin b: its counts' exclusive scan over the waves, then over the bins
+        uint32_t tot = 0;
+        if (tid < SH1_BINS)
+            for (uint32_t q = 0; q < SH1_WAVES; q++) {
+                const uint32_t x = s_h[q * SH1_BINS + tid];
+                s_h[q * SH1_BINS + tid] = tot;
+                tot += x;
+            }
+        const uint32_t binc = sh_incl_scan(tot, lane);
+        if (tid < SH1_BINS && lane == 63) s_bw[wv] = binc;
+        __syncthreads();
+        if (tid < SH1_BINS) {
+            uint32_t exc = binc - tot;
+            for (uint32_t q = 0; q < wv; q++) exc += s_bw[q];
+            for (uint32_t q = 0; q < SH1_WAVES; q++) s_h[q * SH1_BINS + tid] += exc;
+        }
+        __syncthreads();
+        // the stable scatter: waves, steps and lanes are in position order
+        for (uint32_t p0 = d0; p0 < d1; p0 += 64) {   // (wave-uniform)
+            const uint32_t p = p0 + lane;
+            const bool ok = p < d1;
+            const uint32_t ix = ok ? src[p] : 0u;
+            const uint32_t d = ok ? (s_key[ix] >> shift) & (SH1_BINS - 1) : 0u;
+            uint64_t peers = __ballot(ok);
+#pragma unroll
+            for (uint32_t k = 0; k < 8; k++) {
+                const bool bit = (d >> k) & 1u;
+                const uint64_t m = __ballot(ok && bit);
+                peers &= bit ? m : ~m;
+            }
+            uint32_t dst = 0;
+            if (ok) dst = my_h[d] + (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
+            sh_wave_sync();
+            if (ok && (peers >> lane) == 1ull) my_h[d] += (uint32_t)__popcll(peers);
+            sh_wave_sync();
+            if (ok && dst < N) dst_ix[dst] = (uint16_t)ix;   // (dst < N always: the histogram saw these slots)
+        }
+        __syncthreads();
+    }
+    // ---- pick.  I: the ranked entries by (slot, q); F: every position's run's first
+    const uint16_t *I = s_ix[cur];
+    uint16_t *F = s_ix[cur ^ 1];
+    uint32_t rs[SH1_STEPS];   // the position's slot, then its member
+    uint32_t tails = 0;       // bit k: step k's position is its run's last
+    uint32_t carry = 0;       // the last head at or before the step, + 1 (0: none in my chunk so far)
+#pragma unroll
+    for (uint32_t k = 0; k < SH1_STEPS; k++) {
+        if (k * 64 >= D) break;   // (block-uniform)
+        const uint32_t p = d0 + k * 64 + lane;
+        const bool ok = p < d1;
+        const uint32_t s = ok ? s_key[I[p]] : SH_NONE;
+        rs[k] = s;
+        const bool head = ok && (p == 0 || s_key[I[p - 1]] != s);
+        const bool tail = ok && (p + 1 == N || s_key[I[p + 1]] != s);
+        uint32_t x = sh_incl_max(head ? p + 1 : 0u, lane);
+        if (carry > x) x = carry;
+        carry = __shfl(x, 63, 64);
+        if (ok) F[p] = x ? (uint16_t)(x - 1) : (uint16_t)SH1_NOF;
+        if (tail) tails |= 1u << k;
+    }
+    if (lane == 0) s_wt[wv] = carry;   // (the compaction's reads of s_wt lie behind a barrier)
+    __syncthreads();
+    // one lane per (call, slot): the whole transition; the idx of rank 0 replaces the slot at the rank-0 entry
+#pragma unroll
+    for (uint32_t k = 0; k < SH1_STEPS; k++) {
+        if (k * 64 >= D) break;
+        if (!((tails >> k) & 1u)) continue;   // (no wave operation below)
+        const uint32_t p = d0 + k * 64 + lane, s = rs[k];
+        const uint32_t f = sh1_first(F, s_wt, p, wv);
+        const uint32_t q0 = I[f];   // the rank-0 entry
+        uint32_t pos, cnt, nl, meta;
+        sh_record(T, s, pos, cnt, nl, meta);
+        uint32_t b0 = 0;
+        if (cnt >= 2)   // (always: the mark ranked this slot)
+            b0 = sh_transition(T, state, s, cnt, nl, meta, (uint64_t)(p - f), [&]() -> uint32_t { return in_t[q0]; });
+        s_key[q0] = b0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < SH1_STEPS; k++) {
+        if (k * 64 >= D) break;
+        const uint32_t p = d0 + k * 64 + lane;
+        if (p >= d1) continue;
+        const uint32_t s = rs[k], f = sh1_first(F, s_wt, p, wv), b0 = s_key[I[f]];
+        uint32_t pos, cnt, nl, meta;
+        sh_record(T, s, pos, cnt, nl, meta);
+        uint32_t member = SH_NONE;
+        if (cnt) {
+            const uint64_t idx = (meta & 0xFFu) == SH_STICKY ? b0 % cnt : (b0 + (uint64_t)(p - f)) % cnt;
+            member = T.pool[pos + idx];   // (inside the pool: pos + cnt <= pool_len)
+        }
+        rs[k] = member;
+    }
+    __syncthreads();   // (every b0 is read: the members take the keys' place)
+#pragma unroll
+    for (uint32_t k = 0; k < SH1_STEPS; k++) {
+        if (k * 64 >= D) break;
+        const uint32_t p = d0 + k * 64 + lane;
+        if (p < d1) s_key[I[p]] = rs[k];
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < K; i += FO1_BLOCK) out_member[i] = s_key[i];
+    if (tid == 0) {
+        status[SH1_ST_HEAD] = s_red[1];
+        status[SH1_ST_HEAD + 1] = 0;
+        status[SH1_ST_HEAD + 2] = s_red[2];
+        status[SH1_ST_HEAD + 3] = 0;
+        status[SH1_ST_STATE] = SH1_PICKED;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_share_one(const uint32_t *status_in, const uint32_t *fail, const uint32_t *dest_offsets, uint32_t n_dests,
+                            const uint32_t *in_topic, const uint32_t *in_value, uint64_t vcap, uint64_t cap,
+                            const uint32_t *key_clientid, const uint32_t *key_topic, uint64_t n_topics, uint32_t seed,
+                            const uint32_t *slot_of, uint64_t slot_of_len, const uint32_t *slot_rec, uint64_t n_slots,
+                            const uint32_t *pool, uint64_t pool_len, uint32_t *state, uint32_t *out_member, uint32_t *status,
+                            hipStream_t s) {
+    if (!n_dests || n_dests > FO_MAX_DESTS || ((uintptr_t)slot_rec & 15) || !status_in || !status) return hipErrorInvalidValue;
+    if (cap && !out_member) return hipErrorInvalidValue;
+    if (!slot_of) slot_of_len = 0;
+    if (!slot_rec || !state) n_slots = 0;
+    if (n_slots > 0xFFFFFFFFull) n_slots = 0xFFFFFFFFull;   // (0xFFFFFFFF is "none")
+    if (!pool) pool_len = 0;
+    const ShareTabs T{slot_of, slot_of_len, reinterpret_cast<const uint4 *>(slot_rec), n_slots, pool, pool_len,
+                      key_clientid, key_topic, n_topics, seed};
+    hipLaunchKernelGGL(k_sh_one, dim3(1), dim3(FO1_BLOCK), 0, s, status_in, fail, dest_offsets, n_dests, in_topic, in_value,
+                       vcap, cap, T, state, out_member, status);
+    return hipGetLastError();
+}
 
 uint32_t share_passes(uint64_t n_slots) {
     uint32_t bits = 0;

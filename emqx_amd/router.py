@@ -151,7 +151,8 @@ class Router:
         route_kids32 (tm_route_batch32 on pooled pinned buffers: a micro-batch
         is matched and fanned out in place) instead of route_kids, and
         match_routes_dispatch through dispatch_kids32 (tm_dispatch_batch32)
-        instead of dispatch_kids.
+        instead of dispatch_kids, match_routes_publish through publish_kids32
+        (tm_publish_batch32) instead of publish_kids.
         local_subs: this node's subscribers.LocalSubs; the device list of every
         route key {Filter, node()} then follows it (tm_set_subscribers), for
         match_routes_dispatch.
@@ -369,7 +370,8 @@ class Router:
 
     def match_routes_publish(self, topics, key_clientid=None, key_topic=None, seed: int = 0, errors: str = "raise"):
         """match_routes_dispatch under aggre/1 plus the shared-subscription
-        pick, in one device call (tm_publish_batch) -> (ByDest, deliveries,
+        pick, in one device call (tm_publish_batch; tm_publish_batch32 with
+        route_in_place) -> (ByDest, deliveries,
         picks): picks = {group: [(message index, To, pid or None)]}, ONE member
         per (message, {Group, To}) -- what emqx_shared_sub:dispatch/3 would pick
         by the group's strategy (None: {error, no_subscribers}).  In message
@@ -704,7 +706,8 @@ class Router:
                 if local == UNROUTED:
                     raise ValueError("match_routes_dispatch: this node has no destination id")
                 if publish is not None:
-                    (doff, tidx, kids, err), (dt, dk, ds), member = mirror.publish_kids(topics, n_dests, local, *publish)
+                    pub = mirror.publish_kids32 if self._route_in_place else mirror.publish_kids
+                    (doff, tidx, kids, err), (dt, dk, ds), member = pub(topics, n_dests, local, *publish)
                 else:
                     disp = mirror.dispatch_kids32 if self._route_in_place else mirror.dispatch_kids
                     (doff, tidx, kids, err), (dt, dk, ds) = disp(topics, n_dests, local, aggre=aggre)

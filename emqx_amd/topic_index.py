@@ -440,6 +440,71 @@ class Tab:
         finally:
             self._route_put(s)
 
+    def publish_kids32(self, topics, n_dests: int, local_dest: int, key_clientid=None, key_topic=None, seed: int = 0):
+        """publish_kids through tm_publish_batch32 on pooled pinned buffers: a
+        micro-batch is matched, fanned out, dispatched and picked for in place
+        (one synchronisation, no staging copy).  TM_ECAP from the entries: no
+        pick was made and no state moved, so the call is made once more with
+        larger arrays.  TM_ECAP from the deliveries alone: the picks stand (the
+        state has moved), so only the dispatch is fetched again, through
+        tm_dispatch_batch32.  Returns what publish_kids returns (copies: the
+        buffers go back to the pool)."""
+        self.flush()
+        blob, offs = _native.pack_strings(topics)
+        n, nbytes = len(offs) - 1, int(offs[-1])
+        if nbytes >= 1 << 32:
+            return self._index.publish_batch(blob, offs, n_dests, local_dest, key_clientid=key_clientid,
+                                             key_topic=key_topic, seed=seed)
+        s = self._route_set(n, nbytes, n_dests, max(4 * n, 1024), max(4 * n, 1024))
+        try:
+            want = {"member": len(s["topic"]), "kc": max(n, 1), "kt": max(n, 1)}
+            for name, need in want.items():
+                if name not in s or len(s[name]) < need:
+                    if name in s:
+                        self._index.host_free(s.pop(name))
+                    s[name] = self._index.host_array(need + need // 4, np.uint32)
+            s["blob"][:nbytes] = blob[:nbytes]
+            s["offs"][: n + 1] = offs
+            keys = []
+            for name, k in (("kc", key_clientid), ("kt", key_topic)):
+                if k is None:
+                    keys.append(None)
+                    continue
+                k = np.asarray(k, dtype=np.uint32)
+                if len(k) < n:
+                    raise ValueError("publish_kids32: one key word per topic")
+                s[name][:n] = k[:n]
+                keys.append(s[name][:max(n, 1)])
+            for attempt in (0, 1):
+                out = (s["doff"], s["topic"], s["vals"], s["err"], s["head"], s["dtopic"], s["dvals"], s["dsubs"])
+                try:
+                    (doff, tidx, kids, err), dl, member = self._index.publish_batch32(
+                        s["blob"], s["offs"][: n + 1], n_dests, local_dest, out, s["member"], keys[0], keys[1], seed)
+                    break
+                except _native.TmError as e:
+                    if e.code != _native.TM_ECAP or attempt:
+                        raise
+                    total, T = int(s["doff"][n_dests + 1]), int(s["head"][1])
+                    picked = total <= min(len(s["topic"]), len(s["vals"]), len(s["member"]))
+                    if picked:   # the deliveries alone were short: the route outputs and the picks stand
+                        route = (s["doff"][: n_dests + 2].astype(np.uint64), s["topic"][:total].copy(),
+                                 s["vals"][:total].copy(), s["err"][:n].copy())
+                        member = s["member"][:total].copy()
+                    for names, need in ((("topic", "vals", "member"), total), (("dtopic", "dvals", "dsubs"), T)):
+                        if need <= len(s[names[0]]):
+                            continue
+                        for name in names:   # the offsets hold the full bucket sizes, the head the deliveries
+                            self._index.host_free(s.pop(name))
+                            s[name] = self._index.host_array(need + need // 4, np.uint32)
+                    if picked:
+                        out = (s["doff"], s["topic"], s["vals"], s["err"], s["head"], s["dtopic"], s["dvals"], s["dsubs"])
+                        _, dl = self._index.dispatch_batch32(s["blob"], s["offs"][: n + 1], n_dests, local_dest, out,
+                                                             aggre=True)
+                        return route, tuple(a.copy() for a in dl), member
+            return (doff.astype(np.uint64), tidx.copy(), kids.copy(), err.copy()), tuple(a.copy() for a in dl), member.copy()
+        finally:
+            self._route_put(s)
+
     def read_begin(self) -> int:
         return self._index.read_begin()
 

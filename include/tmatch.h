@@ -816,8 +816,43 @@ int tm_dispatch_batch32(tm_index *h, uint64_t n, const uint8_t *topic_bytes, con
  * gen_server does for the tables it mirrors.  Under
  * TM_ECAP from cap (total > cap) no pick is made and no state moves: the
  * caller resubmits.  Under TM_ECAP from dcap alone the route outputs and the
- * picks stand.  TM_EINVAL also for a null out_member with cap > 0.  (The
- * 32-bit in-place form and the NIF's C half follow separately.) */
+ * picks stand.  TM_EINVAL also for a null out_member with cap > 0.
+ *
+ * tm_publish_batch32 (ABI minor 19): tm_publish_batch with 32-bit offsets in
+ * and out, for a NIF's micro-batches (its C half: c_src/tmatch_nif_share.h).
+ * For the same index state, arguments and start state of the slots the return
+ * code, every route output, the head, the deliveries, out_member[0 .. K) and
+ * the state words afterwards are tm_publish_batch's, out_dest_offsets narrowed
+ * to u32 as in tm_dispatch_batch32.  Nothing is written at or past min(total,
+ * cap), min(T, dcap), or K in out_member.  Under TM_ECAP from cap no pick is
+ * made and no state moves; under TM_ECAP from dcap alone the picks stand; the
+ * state moves exactly once per successful call.  TM_EINVAL: whatever
+ * tm_dispatch_batch32 refuses, a missing TM_ROUTE_AGGRE, a null out_member
+ * with cap > 0.  In place -- one synchronisation, no copy in or out -- under
+ * exactly tm_dispatch_batch32's conditions with out_member, and each key array
+ * that is given, in this index's tm_host_alloc memory as well: behind the
+ * dispatch's workgroup, in the same hold of the index lock and on the same
+ * stream, ONE more workgroup picks for the K <= 16384 kept entries on the lane;
+ * the ranks come from a stable sort by slot inside its LDS (8-bit digits, as
+ * many passes as the largest slot present needs), one lane per (call, slot)
+ * applies the transition with the compare-and-swap loop on the device-resident
+ * word, so concurrent calls compose as tm_share_pick_dev's do.  The pick then
+ * sees the share tables (slots, members, state) of the run's own snapshot:
+ * stricter than tm_publish_batch's "as of the moment it is queued", never
+ * looser.  That run may have to be run again (a value scratch that grows, a
+ * failed batch), so the workgroup gates itself on the device: it picks and
+ * moves state only when the fan-out completed, the value scratch held the
+ * batch, total <= cap and the lane's fail word is down, and reports which into
+ * the lane's status words; the host requires "picked" exactly when the run
+ * that stands gives the caller its entries (TM_EDEVICE otherwise).  A local
+ * bucket with more deliveries than the dispatch's workgroup expands: the picks
+ * are made, the grid kernels finish the deliveries.  A batch with more than
+ * 16384 entries: the grid fan-out and dispatch as under tm_dispatch_batch32,
+ * then, once the route outputs are out and total <= cap, the grid pick once, as
+ * in tm_publish_batch.  Every other batch is widened, run by tm_publish_batch,
+ * and narrowed.  TM_DEBUG_PUBLISH_ONE / TM_DEBUG_PUBLISH_GRID count the calls
+ * the one-launch kernel picked for / the grid pick or the staged path
+ * finished. */
 #define TM_SHARE_NONE 0xFFFFFFFFu
 #define TM_SHARE_UNDEF 0xFFFFFFFFu
 enum { TM_SHARE_RANDOM = 0, TM_SHARE_ROUND_ROBIN = 1, TM_SHARE_ROUND_ROBIN_PER_GROUP = 2, TM_SHARE_STICKY = 3,
@@ -841,6 +876,12 @@ int tm_publish_batch(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const 
                      uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
                      uint64_t dcap, const uint32_t *key_clientid, const uint32_t *key_topic, uint32_t seed,
                      uint32_t *out_member, uint8_t *out_err);
+int tm_publish_batch32(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint32_t *topic_offsets,
+                       uint32_t n_dests, uint32_t local_dest, uint32_t flags,
+                       uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                       uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
+                       uint64_t dcap, const uint32_t *key_clientid, const uint32_t *key_topic, uint32_t seed,
+                       uint32_t *out_member, uint8_t *out_err);
 
 /* Release the batch scratch kept for `stream` (after its batches finish);
  * a caller that retires a stream calls this.  No reference counterpart. */
@@ -947,7 +988,9 @@ int tm_profile_read(tm_index *h, double *walk_ms, double *batch_ms, uint64_t *ba
  * calls the one-launch kernel completed / that the grid kernels or the staged
  * path finished.  TM_DEBUG_DP1_MAX (set / get): the deliveries of the local
  * bucket up to which the one-launch kernel expands them itself, clamped to the
- * compiled bound (32768). */
+ * compiled bound (32768).  TM_DEBUG_PUBLISH_ONE / TM_DEBUG_PUBLISH_GRID (get
+ * only): tm_publish_batch32 calls the one-launch pick kernel picked for / that
+ * the grid pick or the staged path finished. */
 enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES = 3, TM_DEBUG_PHASES = 4,
        TM_DEBUG_FAILED_BATCHES = 5, TM_DEBUG_RETRIED_BATCHES = 6, TM_DEBUG_PATH_PHASES = 7,
        TM_DEBUG_PATH_SMALL = 8, TM_DEBUG_PATH_LANE = 9, TM_DEBUG_SMALL_KERNEL = 10,
@@ -957,7 +1000,7 @@ enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES =
        TM_DEBUG_CMB_SPIN = 23, TM_DEBUG_PATCH_ZC = 24, TM_DEBUG_FANOUT_GRID = 25,
        TM_DEBUG_ROUTE_ONE = 26, TM_DEBUG_ROUTE_GRID = 27, TM_DEBUG_ANNEX0 = 28, TM_DEBUG_ANNEX1 = 29,
        TM_DEBUG_HINT_AUDIT = 30, TM_DEBUG_SUB_COMPACTIONS = 31, TM_DEBUG_DISPATCH_ONE = 32,
-       TM_DEBUG_DISPATCH_GRID = 33, TM_DEBUG_DP1_MAX = 34 };
+       TM_DEBUG_DISPATCH_GRID = 33, TM_DEBUG_DP1_MAX = 34, TM_DEBUG_PUBLISH_ONE = 35, TM_DEBUG_PUBLISH_GRID = 36 };
 int tm_debug_set(tm_index *h, uint32_t key, uint64_t value);
 int tm_debug_get(tm_index *h, uint32_t key, uint64_t *value);
 

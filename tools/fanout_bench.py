@@ -112,7 +112,13 @@ it does not advance the state words, one pass less than the kernels -- outputs
 compared first (identical).  One JSON line per slot count.  With --small:
 tm_publish_batch beside tm_dispatch_batch (both with TM_ROUTE_AGGRE), host to
 host as above, per batch size; destinations 1 to 4 are groups, one slot per
-value; the figure is publish_minus_dispatch_ms.  Under TM_LIB naming a library
+value; the figure is publish_minus_dispatch_ms.  Two more legs, interleaved
+with those two, run the in-place forms on tm_host_alloc buffers:
+tm_publish_batch32 and tm_dispatch_batch32 (publish_batch32, dispatch_batch32,
+publish32_minus_dispatch32_ms: what the pick adds in place;
+publish_over_publish32; picked_by: the one-launch kernel, or the grid pick /
+the staged path); the route outputs, the head and which entries have a pick
+are compared with tm_publish_batch's first.  Under TM_LIB naming a library
 without tm_publish_batch only tm_dispatch_batch runs (the yardstick of an A/B);
 --dispatch-leg-only times this library the same way, the other side of that A/B.
 """
@@ -569,6 +575,7 @@ def small_share(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=0, n_g
     P = _native._ptr
     lib, h = ix._lib, ix._h
     has = hasattr(lib, "tm_publish_batch") and not a.dispatch_leg_only
+    has32 = has and hasattr(lib, "tm_publish_batch32")
     rng = np.random.default_rng(7)
     cnt = rng.integers(a.subs[0], a.subs[1] + 1, nvals)
     loffs = np.zeros(nvals + 1, np.uint64)
@@ -609,6 +616,39 @@ def small_share(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=0, n_g
                                         P(dd[0]), P(dd[1]), P(dd[2]), dcap, P(kc), P(kc), 1, P(m_), P(err))
 
         legs = [("dispatch_batch", leg_d)] + ([("publish_batch", leg_p)] if has else [])
+        pinned, took = [], None
+        if has32:
+            # the in-place forms on tm_host_alloc buffers: tm_publish_batch32 and, to show what the pick adds, tm_dispatch_batch32
+            def pin(k, dt):
+                pinned.append(ix.host_array(k, dt))
+                return pinned[-1]
+            nb = int(offs[-1])
+            b32, o32, e32 = pin(nb + 16, np.uint8), pin(n + 1, np.uint32), pin(n, np.uint8)
+            b32[:nb], o32[:] = blob[:nb], offs.astype(np.uint32)
+            d32, h32 = pin(n_dests + 2, np.uint32), pin(2, np.uint64)
+            t32, v32, m32 = (pin(cap, np.uint32) for _ in range(3))
+            dd32 = tuple(pin(dcap, np.uint32) for _ in range(3))
+            k32 = pin(n, np.uint32)
+            k32[:] = kc
+
+            def leg_p32():
+                return lib.tm_publish_batch32(h, n, P(b32), P(o32), n_dests, local, 1, P(d32), P(t32), P(v32), cap, P(h32),
+                                              P(dd32[0]), P(dd32[1]), P(dd32[2]), dcap, P(k32), P(k32), 1, P(m32), P(e32))
+
+            def leg_d32():
+                return lib.tm_dispatch_batch32(h, n, P(b32), P(o32), n_dests, local, 1, P(d32), P(t32), P(v32), cap,
+                                               P(h32), P(dd32[0]), P(dd32[1]), P(dd32[2]), dcap, P(e32))
+
+            ONE = _native.TM_DEBUG_PUBLISH_ONE
+            c0 = ix.debug_get(ONE)
+            assert leg_p() == 0 and leg_p32() == 0
+            took = "one_launch" if ix.debug_get(ONE) > c0 else "grid_or_staged"
+            K32 = int(d32[n_dests + 1])
+            assert np.array_equal(d64, d32.astype(np.uint64)) and np.array_equal(t_[:K32], t32[:K32]) and \
+                np.array_equal(v_[:K32], v32[:K32]) and h32.tolist() == head.tolist() and \
+                np.array_equal(m_[:K32] == 0xFFFFFFFF, m32[:K32] == 0xFFFFFFFF), \
+                f"n {n}: tm_publish_batch and tm_publish_batch32 differ"
+            legs += [("publish_batch32", leg_p32), ("dispatch_batch32", leg_d32)]
         ms = {k: [] for k, _ in legs}
         for r in range(warmup + reps):
             for k, f in legs:
@@ -624,7 +664,14 @@ def small_share(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=0, n_g
         if has:
             line["picks"] = int((m_[:K] != 0xFFFFFFFF).sum())
             line["publish_minus_dispatch_ms"] = round(st["publish_batch"]["p50_ms"] - st["dispatch_batch"]["p50_ms"], 4)
+        if has32:
+            line["picked_by"] = took
+            line["publish32_minus_dispatch32_ms"] = round(st["publish_batch32"]["p50_ms"] -
+                                                          st["dispatch_batch32"]["p50_ms"], 4)
+            line["publish_over_publish32"] = round(st["publish_batch"]["p50_ms"] / st["publish_batch32"]["p50_ms"], 2)
         print(json.dumps(line), flush=True)
+        for x in pinned:
+            ix.host_free(x)
 
 
 def _np_aggre(doff, t, v, fof, n_dests):
