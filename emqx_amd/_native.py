@@ -476,6 +476,28 @@ class Index:
         self._check(self._lib.tm_aggre_dev(self._h, n_dests, d_dest_offs, d_topic, d_value, cap, d_filter_of, filter_len,
                                            d_out_dest_offs, d_out_topic, d_out_value, stream))
 
+    @staticmethod
+    def _out32(name, offs, n_dests, out, member=None, keys=(), cap=None, dcap=None):
+        """The checks of a 32-bit call's caller-owned buffers, before the library
+        is touched.  out: route_batch32's four arrays or dispatch_batch32's
+        eight; member: publish_batch32's; keys: its key arrays (None: absent).
+        -> (cap, dcap), by default all of the entry / the delivery arrays."""
+        n = len(offs) - 1
+        doff, err, head = out[0], out[3], out[4:5]
+        entries = tuple(out[1:3]) + (() if member is None else (member,))
+        deliveries = tuple(out[5:])
+        if offs.dtype != np.uint32 or doff.dtype != np.uint32 or err.dtype != np.uint8 \
+                or any(h.dtype != np.uint64 or len(h) < 2 for h in head) \
+                or any(a.dtype != np.uint32 for a in entries + deliveries) or len(doff) < n_dests + 2 or len(err) < n:
+            raise ValueError(f"{name}: u32 offsets and large enough outputs of the right dtype expected")
+        if any(k is not None and (k.dtype != np.uint32 or len(k) < n) for k in keys):
+            raise ValueError(f"{name}: one u32 key word per topic")
+        room, droom = min(map(len, entries)), min(map(len, deliveries), default=0)
+        cap, dcap = room if cap is None else cap, droom if dcap is None else dcap
+        if cap > room or dcap > droom:
+            raise ValueError(f"{name}: cap / dcap exceeds the output arrays")
+        return cap, dcap
+
     def route_batch(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, cap: int | None = None,
                     aggre: bool = False):
         """tm_route_batch -> (dest_offsets u64[n_dests+2], topic u32[total],
@@ -495,12 +517,8 @@ class Index:
         while True:
             topic = np.empty(max(cap, 1), dtype=np.uint32)
             vals = np.empty(max(cap, 1), dtype=np.uint32)
-            if aggre:
-                rc = self._lib.tm_route_batch_ex(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff), _ptr(topic),
-                                                 _ptr(vals), cap, _ptr(err), TM_ROUTE_AGGRE)
-            else:
-                rc = self._lib.tm_route_batch(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff), _ptr(topic),
-                                              _ptr(vals), cap, _ptr(err))
+            rc = self._lib.tm_route_batch_ex(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff), _ptr(topic),
+                                             _ptr(vals), cap, _ptr(err), TM_ROUTE_AGGRE if aggre else 0)
             if rc == TM_ECAP and int(doff[-1]) > cap:
                 cap = int(doff[-1])
                 continue
@@ -522,19 +540,9 @@ class Index:
         the entries BEFORE aggregation do not fit (the offsets are those sizes)."""
         n = len(offs) - 1
         doff, topic, vals, err = out
-        if offs.dtype != np.uint32 or doff.dtype != np.uint32 or topic.dtype != np.uint32 or vals.dtype != np.uint32 \
-                or err.dtype != np.uint8 or len(doff) < n_dests + 2 or len(err) < n:
-            raise ValueError("route_batch32: u32 offsets and large enough outputs of the right dtype expected")
-        if cap is None:
-            cap = min(len(topic), len(vals))
-        if cap > min(len(topic), len(vals)):
-            raise ValueError("route_batch32: cap exceeds the output arrays")
-        if aggre:
-            self._check(self._lib.tm_route_batch32_ex(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff),
-                                                      _ptr(topic), _ptr(vals), cap, _ptr(err), TM_ROUTE_AGGRE))
-        else:
-            self._check(self._lib.tm_route_batch32(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff), _ptr(topic),
-                                                   _ptr(vals), cap, _ptr(err)))
+        cap, _ = self._out32("route_batch32", offs, n_dests, out, cap=cap)
+        self._check(self._lib.tm_route_batch32_ex(self._h, n, _ptr(blob), _ptr(offs), n_dests, _ptr(doff), _ptr(topic),
+                                                  _ptr(vals), cap, _ptr(err), TM_ROUTE_AGGRE if aggre else 0))
         total = int(doff[n_dests + 1])
         return doff[: n_dests + 2], topic[:total], vals[:total], err[:n]
 
@@ -574,6 +582,15 @@ class Index:
         deliveries of bucket local_dest with the table of set_subscribers, in
         entry order and list order.  A cap that proves too small is retried,
         sized from what the call returned."""
+        route, deliveries, _ = self._dispatch_loop(blob, offs, n_dests, local_dest, cap, dcap,
+                                                   TM_ROUTE_AGGRE if aggre else 0)
+        return route, deliveries
+
+    def _dispatch_loop(self, blob, offs, n_dests, local_dest, cap, dcap, flags, pick=None):
+        """dispatch_batch's and publish_batch's loop: allocate, call, grow what
+        was short from what the call returned.  pick: (key_clientid, key_topic,
+        seed) -- tm_publish_batch, else tm_dispatch_batch.
+        -> (route tuple, deliveries, member or None)."""
         n = len(offs) - 1
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
@@ -585,20 +602,28 @@ class Index:
         if dcap is None:
             dcap = max(4 * n, 1024)
         for _ in range(4):
-            topic = np.empty(max(cap, 1), dtype=np.uint32)
-            vals = np.empty(max(cap, 1), dtype=np.uint32)
+            topic, vals = (np.empty(max(cap, 1), dtype=np.uint32) for _ in range(2))
+            member = None if pick is None else np.empty(max(cap, 1), dtype=np.uint32)
             dt, dv, ds = (np.empty(max(dcap, 1), dtype=np.uint32) for _ in range(3))
-            rc = self._lib.tm_dispatch_batch(self._h, n, _ptr(blob), _ptr(offs), n_dests, local_dest,
-                                             TM_ROUTE_AGGRE if aggre else 0, _ptr(doff), _ptr(topic), _ptr(vals), cap,
-                                             _ptr(head), _ptr(dt), _ptr(dv), _ptr(ds), dcap, _ptr(err))
-            if rc == TM_ECAP and (int(doff[-1]) > cap or int(head[1]) > dcap):
-                cap = max(cap, int(doff[-1]))
-                dcap = max(dcap, int(head[1]))
-                continue
-            self._check(rc)
+            args = (self._h, n, _ptr(blob), _ptr(offs), n_dests, local_dest, flags, _ptr(doff), _ptr(topic), _ptr(vals),
+                    cap, _ptr(head), _ptr(dt), _ptr(dv), _ptr(ds), dcap)
+            if pick is None:
+                rc = self._lib.tm_dispatch_batch(*args, _ptr(err))
+            else:
+                rc = self._lib.tm_publish_batch(*args, _ptr(pick[0]), _ptr(pick[1]), pick[2], _ptr(member), _ptr(err))
             total, T = int(doff[-1]), int(head[1])
-            return (doff, topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T])
-        raise TmError(TM_ECAP, "dispatch_batch: the totals kept growing")
+            if rc == TM_ECAP and pick is not None and total <= cap:
+                # publish, dcap alone: the picks stand (the state has moved); only the dispatch is fetched again
+                _, (dt, dv, ds), _ = self._dispatch_loop(blob, offs, n_dests, local_dest, cap, T, flags)
+            elif rc == TM_ECAP and (total > cap or T > dcap):
+                # (a publish made no pick: the state has not moved)
+                cap, dcap = max(cap, total), max(dcap, T)
+                continue
+            else:
+                self._check(rc)
+            return (doff, topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T]), \
+                None if member is None else member[:total]
+        raise TmError(TM_ECAP, f"{'dispatch_batch' if pick is None else 'publish_batch'}: the totals kept growing")
 
     def dispatch_batch32(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, local_dest: int, out,
                          cap: int | None = None, dcap: int | None = None, aggre: bool = False):
@@ -615,16 +640,7 @@ class Index:
         under aggre) and head[1] size the retry."""
         n = len(offs) - 1
         doff, topic, vals, err, head, dt, dv, ds = out
-        if offs.dtype != np.uint32 or doff.dtype != np.uint32 or err.dtype != np.uint8 or head.dtype != np.uint64 \
-                or any(a.dtype != np.uint32 for a in (topic, vals, dt, dv, ds)) or len(doff) < n_dests + 2 \
-                or len(err) < n or len(head) < 2:
-            raise ValueError("dispatch_batch32: u32 offsets and large enough outputs of the right dtype expected")
-        if cap is None:
-            cap = min(len(topic), len(vals))
-        if dcap is None:
-            dcap = min(len(dt), len(dv), len(ds))
-        if cap > min(len(topic), len(vals)) or dcap > min(len(dt), len(dv), len(ds)):
-            raise ValueError("dispatch_batch32: cap / dcap exceeds the output arrays")
+        cap, dcap = self._out32("dispatch_batch32", offs, n_dests, out, cap=cap, dcap=dcap)
         self._check(self._lib.tm_dispatch_batch32(self._h, n, _ptr(blob), _ptr(offs), n_dests, local_dest,
                                                   TM_ROUTE_AGGRE if aggre else 0, _ptr(doff), _ptr(topic), _ptr(vals),
                                                   cap, _ptr(head), _ptr(dt), _ptr(dv), _ptr(ds), dcap, _ptr(err)))
@@ -704,35 +720,7 @@ class Index:
         kt = None if key_topic is None else np.ascontiguousarray(key_topic, dtype=np.uint32)
         if any(k is not None and len(k) < n for k in (kc, kt)):
             raise ValueError("publish_batch: one key word per topic")
-        doff = np.zeros(n_dests + 2, dtype=np.uint64)
-        head = np.zeros(2, dtype=np.uint64)
-        err = np.zeros(max(n, 1), dtype=np.uint8)
-        if cap is None:
-            cap = max(4 * n, 1024)
-        if dcap is None:
-            dcap = max(4 * n, 1024)
-        for _ in range(4):
-            topic = np.empty(max(cap, 1), dtype=np.uint32)
-            vals = np.empty(max(cap, 1), dtype=np.uint32)
-            member = np.empty(max(cap, 1), dtype=np.uint32)
-            dt, dv, ds = (np.empty(max(dcap, 1), dtype=np.uint32) for _ in range(3))
-            rc = self._lib.tm_publish_batch(self._h, n, _ptr(blob), _ptr(offs), n_dests, local_dest, TM_ROUTE_AGGRE,
-                                            _ptr(doff), _ptr(topic), _ptr(vals), cap, _ptr(head), _ptr(dt), _ptr(dv),
-                                            _ptr(ds), dcap, _ptr(kc), _ptr(kt), seed, _ptr(member), _ptr(err))
-            if rc == TM_ECAP and int(doff[-1]) > cap:
-                # (no pick was made: the state has not moved)
-                cap = max(cap, int(doff[-1]))
-                dcap = max(dcap, int(head[1]))
-                continue
-            if rc != TM_ECAP:
-                self._check(rc)
-            total, T = int(doff[-1]), int(head[1])
-            if rc == TM_ECAP:
-                # dcap alone: the picks stand; only the dispatch is fetched again
-                (_, _, _, _), (dt, dv, ds) = self.dispatch_batch(blob, offs, n_dests, local_dest, cap=cap, dcap=T,
-                                                                 aggre=True)
-            return (doff, topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T]), member[:total]
-        raise TmError(TM_ECAP, "publish_batch: the totals kept growing")
+        return self._dispatch_loop(blob, offs, n_dests, local_dest, cap, dcap, TM_ROUTE_AGGRE, pick=(kc, kt, seed))
 
     def publish_batch32(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, local_dest: int, out, member,
                         key_clientid=None, key_topic=None, seed: int = 0, cap: int | None = None,
@@ -748,18 +736,7 @@ class Index:
         state moved; from dcap alone (head[1] > dcap) the picks stand."""
         n = len(offs) - 1
         doff, topic, vals, err, head, dt, dv, ds = out
-        if offs.dtype != np.uint32 or doff.dtype != np.uint32 or err.dtype != np.uint8 or head.dtype != np.uint64 \
-                or any(a.dtype != np.uint32 for a in (topic, vals, dt, dv, ds, member)) or len(doff) < n_dests + 2 \
-                or len(err) < n or len(head) < 2:
-            raise ValueError("publish_batch32: u32 offsets and large enough outputs of the right dtype expected")
-        if any(k is not None and (k.dtype != np.uint32 or len(k) < n) for k in (key_clientid, key_topic)):
-            raise ValueError("publish_batch32: one u32 key word per topic")
-        if cap is None:
-            cap = min(len(topic), len(vals), len(member))
-        if dcap is None:
-            dcap = min(len(dt), len(dv), len(ds))
-        if cap > min(len(topic), len(vals), len(member)) or dcap > min(len(dt), len(dv), len(ds)):
-            raise ValueError("publish_batch32: cap / dcap exceeds the output arrays")
+        cap, dcap = self._out32("publish_batch32", offs, n_dests, out, member, (key_clientid, key_topic), cap, dcap)
         self._check(self._lib.tm_publish_batch32(self._h, n, _ptr(blob), _ptr(offs), n_dests, local_dest, TM_ROUTE_AGGRE,
                                                  _ptr(doff), _ptr(topic), _ptr(vals), cap, _ptr(head), _ptr(dt), _ptr(dv),
                                                  _ptr(ds), dcap, _ptr(key_clientid), _ptr(key_topic), seed, _ptr(member),

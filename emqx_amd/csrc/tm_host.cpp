@@ -2102,7 +2102,8 @@ struct HostBatch {
     uint64_t ws_topics = 0;
     int tries = 0;
     uint64_t t_queued = 0, t_synced = 0;   // (TM_HOST_TIMING) the last attempt: lock dropped, GPU wait over
-    explicit HostBatch(tm_index *ix) : ix(ix), g(ix->mu) {}
+    const char *who;   // the entry point, for the messages
+    explicit HostBatch(tm_index *ix, const char *who = "tm_match_batch") : ix(ix), g(ix->mu), who(who) {}
     ~HostBatch() {
         if (!ln) return;
         if (!g.owns_lock()) g.lock();
@@ -2148,8 +2149,8 @@ struct HostBatch {
             if (g_cmb_timing) t_synced = ns_now();
             if (!batch_failed(ix, *ln)) return TM_OK;
             if (tries++ >= 1)
-                return fail(ix, TM_EDEVICE, "tm_match_batch: the batch failed on the device twice (look-back wait "
-                                            "expired, err 4); not matched");
+                return fail(ix, TM_EDEVICE, std::string(who) + ": the batch failed on the device twice (look-back wait "
+                                                               "expired, err 4); not matched");
             ix->retried_batches++;
             if ((rc = relock())) return rc;
         }
@@ -3843,28 +3844,88 @@ static int copy_route_out(tm_index *ix, Lane &ln, uint32_t n_dests, uint64_t tot
     return total > cap ? TM_ECAP : TM_OK;
 }
 
-// The product path of a batched broker: match into device scratch (CSR,
-// traversal order), fan out with the index's own destination table, copy the
-// destination-major arrays back.  The lane's value scratch always holds the
-// whole batch (it grows and the batch runs again), so the bucket offsets are
-// complete whatever `cap` is; cap only bounds what is copied out.
+// One request of the route family (tm_route_batch, tm_dispatch_batch,
+// tm_publish_batch and their 32-bit forms): everything the six entry points
+// share.  dp / pk: the dispatch and the pick, null when the call has none.
+// who: the entry point the caller called -- every refusal and failure names
+// it.  Only the topic offsets and out_dest_offsets differ in width; they travel
+// beside the request.
+struct RouteReq {
+    const char *who;
+    uint64_t n;
+    const uint8_t *tb;
+    uint32_t n_dests, flags;
+    uint32_t *out_topic, *out_values;
+    uint64_t cap;
+    uint8_t *out_err;
+    const RouteDispatch *dp;
+    const RoutePick *pk;
+    bool aggre() const { return flags & TM_ROUTE_AGGRE; }
+};
+
+static int route_fail(tm_index *ix, const RouteReq &rq, int code, const char *what) {
+    return fail(ix, code, std::string(rq.who) + ": " + what);
+}
+
+// The family's argument checks, once per call, before anything is locked or
+// queued.  offsets: the topic offsets and out_dest_offsets are both there.
+// narrow: a 32-bit call, which may run in place -- out_err is required (the
+// device writes the flags there) and so is an out_head the device can write
+// as two u64.
+static int route_check(tm_index *ix, const RouteReq &rq, bool offsets, bool narrow) {
+    const RouteDispatch *dp = rq.dp;
+    if (!ix) return route_fail(nullptr, rq, TM_EINVAL, "null handle");
+    if (rq.flags & ~(uint32_t)TM_ROUTE_AGGRE) return route_fail(ix, rq, TM_EINVAL, "unknown flag");
+    if (rq.pk && !rq.aggre())
+        return route_fail(ix, rq, TM_EINVAL, "TM_ROUTE_AGGRE is required (aggre/1 runs before route/2)");
+    if (!rq.n_dests || rq.n_dests > FO_MAX_DESTS) return route_fail(ix, rq, TM_EINVAL, "n_dests must be 1 .. 65536");
+    if (dp && dp->local_dest >= rq.n_dests) return route_fail(ix, rq, TM_EINVAL, "local_dest must be below n_dests");
+    if (!offsets || (narrow && !rq.out_err) ||
+        (rq.cap && (!rq.out_topic || !rq.out_values || (rq.pk && !rq.pk->out_member))) ||
+        (dp && (!dp->out_head || (dp->dcap && (!dp->out_topic || !dp->out_value || !dp->out_sub)))))
+        return route_fail(ix, rq, TM_EINVAL, "null buffer");
+    if (narrow && dp && ((uintptr_t)dp->out_head & 7)) return route_fail(ix, rq, TM_EINVAL, "out_head must be 8-byte aligned");
+    if (rq.n >= 0xFFFFFFFFull) return route_fail(ix, rq, TM_EINVAL, "batch too large");
+    return TM_OK;
+}
+
+// The pick of a call whose run stands (no scratch grows, no retry is left) and
+// whose caller has the `kept` entries: queued now, ONCE, over the arrays still
+// in the lane -- the state words move once, and only for entries the caller
+// gets.  Only the copy of its own output can fail after it.
+static int pick_after_run(tm_index *ix, HostBatch &hb, const RouteReq &rq, uint64_t vcap, uint64_t kept) {
+    int rc;
+    Lane &ln = *hb.ln;
+    if ((rc = hb.relock())) return rc;
+    if ((rc = queue_pick(ix, ln, rq.n, rq.n_dests, vcap, *rq.pk))) return rc;
+    if ((rc = batch_done(ix, ln))) return rc;
+    hb.g.unlock();
+    // (the copy may wait for the stream: never under the lock.  out_member is
+    // pageable memory or, after a 32-bit call, a tm_host_alloc buffer)
+    if (kept) HIPCHK(ix, hipMemcpyAsync(rq.pk->out_member, ln.d_sm, kept * 4, hipMemcpyDefault, ln.s));
+    HIPCHK(ix, hipStreamSynchronize(ln.s));
+    return TM_OK;
+}
+
+// The product path of a batched broker (the request already checked): match
+// into device scratch (CSR, traversal order), fan out with the index's own
+// destination table, copy the destination-major arrays back.  The lane's value
+// scratch always holds the whole batch (it grows and the batch runs again), so
+// the bucket offsets are complete whatever `cap` is; cap only bounds what is
+// copied out.
 // TM_ROUTE_AGGRE: the aggre pass runs on the fan-out's results in the lane's
 // scratch, and only the kept entries are copied back.
 // dp (tm_dispatch_batch): in the same run, on the same lane, the dispatch of
 // bucket dp->local_dest over the results; the lane's delivery scratch grows
 // from the T that comes back with the results, and then only the dispatch
 // kernels are queued again.
-static int route_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
-                            uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
-                            uint8_t *out_err, uint32_t flags, const RouteDispatch *dp, const RoutePick *pk = nullptr) {
-    if (!ix) return fail(nullptr, TM_EINVAL, "tm_route_batch: null handle");
-    if (flags & ~(uint32_t)TM_ROUTE_AGGRE) return fail(ix, TM_EINVAL, "tm_route_batch: unknown flag");
-    const bool aggre = flags & TM_ROUTE_AGGRE;
-    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_route_batch: n_dests must be 1 .. 65536");
-    if (!to || !out_dest_offsets || (n && !tb && to[n] != to[0]) || (cap && (!out_topic || !out_values)))
-        return fail(ix, TM_EINVAL, "tm_route_batch: null buffer");
-    if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch: batch too large");
-    HostBatch hb(ix);
+// pk (tm_publish_batch): pick_after_run, when the kept entries fit.
+static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to, uint64_t *out_dest_offsets) {
+    const uint64_t n = rq.n, cap = rq.cap;
+    const uint32_t n_dests = rq.n_dests;
+    const bool aggre = rq.aggre();
+    const RouteDispatch *dp = rq.dp;
+    HostBatch hb(ix, rq.who);
     int rc;
     if ((rc = hb.open(n))) return rc;
     Lane &ln = *hb.ln;
@@ -3872,7 +3933,7 @@ static int route_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     ix->rep[ln.r].batches++;
     const uint8_t *dbytes;
     const uint64_t *doffs;
-    if ((rc = stage_in(ix, ln, n, tb, to, nullptr, dbytes, doffs))) return rc;
+    if ((rc = stage_in(ix, ln, n, rq.tb, to, nullptr, dbytes, doffs))) return rc;
     // hit offsets, then the err flags; with a dispatch its two head words after them
     const uint64_t hoff = ((n + 1) * 8 + n + 7) & ~7ull;
     const uint64_t rbytes = dp ? hoff + 16 : (n + 1) * 8 + n;
@@ -3885,7 +3946,7 @@ static int route_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     uint64_t total = 0, vcap = std::max<uint64_t>({ln.d_vals_cap, 4 * n, 1 << 16});
     uint64_t dwant = dp ? std::max<uint64_t>(ln.d_ds_cap, 1 << 16) : 0;   // deliveries the lane has room for
     for (int attempt = 0;; attempt++) {
-        if (vcap > 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch: more than 2^32 - 1 hits in one batch");
+        if (vcap > 0xFFFFFFFFull) return route_fail(ix, rq, TM_EINVAL, "more than 2^32 - 1 hits in one batch");
         if ((rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, vcap))) return rc;
         if ((rc = route_scratch(ix, ln, n_dests, vcap, aggre, false, 0))) return rc;
         if (dp && (rc = dispatch_scratch(ix, ln, vcap, dwant))) return rc;
@@ -3904,7 +3965,7 @@ static int route_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const u
         if (rc) return rc;
         std::memcpy(&total, ln.pin_out + n * 8, 8);
         if (total <= vcap) break;
-        if (attempt >= 2) return fail(ix, TM_EDEVICE, "tm_route_batch: hit total kept growing past the value scratch");
+        if (attempt >= 2) return route_fail(ix, rq, TM_EDEVICE, "hit total kept growing past the value scratch");
         vcap = total + total / 4;
         if ((rc = hb.relock())) return rc;
     }
@@ -3914,7 +3975,7 @@ static int route_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const u
         for (int attempt = 0; std::min(head[1], dcap) > dwant; attempt++) {
             // more deliveries than the lane had room for: the scratch grows and the
             // dispatch alone runs again on the results still in the lane (no walk)
-            if (attempt >= 2) return fail(ix, TM_EDEVICE, "tm_dispatch_batch: the delivery total kept growing past the scratch");
+            if (attempt >= 2) return route_fail(ix, rq, TM_EDEVICE, "the delivery total kept growing past the scratch");
             dwant = std::min(head[1] + head[1] / 4, dcap);
             if ((rc = hb.relock())) return rc;
             if ((rc = dispatch_scratch(ix, ln, vcap, dwant))) return rc;
@@ -3926,24 +3987,12 @@ static int route_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const u
             std::memcpy(head, ln.pin_out + hoff, 16);
         }
     }
-    rc = copy_route_out(ix, ln, n_dests, total, cap, aggre, aggre && total <= cap, out_dest_offsets, nullptr, out_topic,
-                        out_values);
+    rc = copy_route_out(ix, ln, n_dests, total, cap, aggre, aggre && total <= cap, out_dest_offsets, nullptr, rq.out_topic,
+                        rq.out_values);
     if (rc != TM_OK && rc != TM_ECAP) return rc;
-    if (out_err && n) std::memcpy(out_err, ln.pin_out + (n + 1) * 8, n);
-    if (pk && aggre && total <= cap) {
-        // the run stands (no scratch grows, no retry is left) and the caller has
-        // the kept entries: the pick is queued now, once, over the arrays still
-        // in the lane; only the copy of its own output can fail after it
-        int prc;
-        if ((prc = hb.relock())) return prc;
-        if ((prc = queue_pick(ix, ln, n, n_dests, vcap, *pk))) return prc;
-        if ((prc = batch_done(ix, ln))) return prc;
-        hb.g.unlock();
-        // (the copy into the caller's pageable buffer may wait for the stream: never under the lock)
-        const uint64_t kept = std::min(out_dest_offsets[n_dests + 1], cap);
-        if (kept) HIPCHK(ix, hipMemcpyAsync(pk->out_member, ln.d_sm, kept * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(ix, hipStreamSynchronize(s));
-    }
+    if (rq.out_err && n) std::memcpy(rq.out_err, ln.pin_out + (n + 1) * 8, n);
+    if (rq.pk && aggre && total <= cap)
+        if (int prc = pick_after_run(ix, hb, rq, vcap, std::min(out_dest_offsets[n_dests + 1], cap))) return prc;
     if (dp) {
         dp->out_head[0] = head[0];
         dp->out_head[1] = head[1];
@@ -3959,22 +4008,34 @@ static int route_batch_impl(tm_index *ix, uint64_t n, const uint8_t *tb, const u
     return rc;
 }
 
+// the 64-bit entry points: checked, then route_batch_impl
+static int route_batch64(tm_index *ix, const RouteReq &rq, const uint64_t *to, uint64_t *out_dest_offsets) {
+    if (int rc = route_check(ix, rq, to && out_dest_offsets, false)) return rc;
+    if (rq.n && !rq.tb && to[rq.n] != to[0]) return route_fail(ix, rq, TM_EINVAL, "null buffer");
+    return route_batch_impl(ix, rq, to, out_dest_offsets);
+}
+
 int tm_route_batch_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
                       uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
                       uint8_t *out_err, uint32_t flags) {
-    return route_batch_impl(ix, n, tb, to, n_dests, out_dest_offsets, out_topic, out_values, cap, out_err, flags, nullptr);
+    const RouteReq rq{"tm_route_batch_ex", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, nullptr, nullptr};
+    return route_batch64(ix, rq, to, out_dest_offsets);
+}
+
+int tm_route_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
+                   uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                   uint8_t *out_err) {
+    const RouteReq rq{"tm_route_batch", n, tb, n_dests, 0, out_topic, out_values, cap, out_err, nullptr, nullptr};
+    return route_batch64(ix, rq, to, out_dest_offsets);
 }
 
 int tm_dispatch_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
                       uint32_t local_dest, uint32_t flags, uint64_t *out_dest_offsets, uint32_t *out_topic,
                       uint32_t *out_values, uint64_t cap, uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue,
                       uint32_t *out_dsub, uint64_t dcap, uint8_t *out_err) {
-    if (!ix) return fail(nullptr, TM_EINVAL, "tm_dispatch_batch: null handle");
-    if (n_dests && local_dest >= n_dests) return fail(ix, TM_EINVAL, "tm_dispatch_batch: local_dest must be below n_dests");
-    if (!out_head || (dcap && (!out_dtopic || !out_dvalue || !out_dsub)))
-        return fail(ix, TM_EINVAL, "tm_dispatch_batch: null buffer");
     const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
-    return route_batch_impl(ix, n, tb, to, n_dests, out_dest_offsets, out_topic, out_values, cap, out_err, flags, &dp);
+    const RouteReq rq{"tm_dispatch_batch", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, &dp, nullptr};
+    return route_batch64(ix, rq, to, out_dest_offsets);
 }
 
 int tm_publish_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
@@ -3982,21 +4043,10 @@ int tm_publish_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t
                      uint32_t *out_values, uint64_t cap, uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue,
                      uint32_t *out_dsub, uint64_t dcap, const uint32_t *key_clientid, const uint32_t *key_topic,
                      uint32_t seed, uint32_t *out_member, uint8_t *out_err) {
-    if (!ix) return fail(nullptr, TM_EINVAL, "tm_publish_batch: null handle");
-    if (!(flags & TM_ROUTE_AGGRE))
-        return fail(ix, TM_EINVAL, "tm_publish_batch: TM_ROUTE_AGGRE is required (aggre/1 runs before route/2)");
-    if (n_dests && local_dest >= n_dests) return fail(ix, TM_EINVAL, "tm_publish_batch: local_dest must be below n_dests");
-    if (!out_head || (dcap && (!out_dtopic || !out_dvalue || !out_dsub)) || (cap && !out_member))
-        return fail(ix, TM_EINVAL, "tm_publish_batch: null buffer");
     const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
     const RoutePick pk{key_clientid, key_topic, seed, out_member};
-    return route_batch_impl(ix, n, tb, to, n_dests, out_dest_offsets, out_topic, out_values, cap, out_err, flags, &dp, &pk);
-}
-
-int tm_route_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
-                   uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
-                   uint8_t *out_err) {
-    return tm_route_batch_ex(ix, n, tb, to, n_dests, out_dest_offsets, out_topic, out_values, cap, out_err, 0);
+    const RouteReq rq{"tm_publish_batch", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, &dp, &pk};
+    return route_batch64(ix, rq, to, out_dest_offsets);
 }
 
 // 32-bit offsets (include/tmatch.h).  An in-place batch the one-launch small
@@ -4122,30 +4172,12 @@ int tm_match_batch32_pairs(tm_index *ix, uint64_t n, const uint8_t *tb, const ui
     return rc;
 }
 
-// tm_route_batch32 in place (include/tmatch.h): the batch matched as ONE
-// pairs segment of the one-launch kernel (launch_small_segs, no combiner) into
-// the lane's HBM scratch, the flags into the caller's out_err, then k_fo_one
-// fans out into the caller's mapped outputs -- two launches, one
-// synchronisation, no copy.  ROUTE32_OTHER: the batch is not eligible (the
-// caller takes tm_route_batch).  A batch k_fo_one reports as too large is
-// finished here by launch_fanout_pairs on the pairs already matched.
-// dp (tm_dispatch_batch32): k_fo_one's results stay on the lane, as under
-// aggre, k_ag_one's too, and ONE more launch of one workgroup (k_dp_one) writes
-// the route outputs, the head and the deliveries into the caller's buffers --
-// still one synchronisation and no copy; the device never reads a caller's
-// output.  More than dp1_max deliveries (DP1_TOO_LARGE), or more entries than
-// k_fo_one takes: the grid kernels (launch_dispatch) run on the arrays already
-// on the lane and write the deliveries straight into the caller's buffers.
-// pk (tm_publish_batch32; with dp and aggre): out_member and the key arrays lie
-// in tm_host_alloc memory too, and the same queue lambda -- same lock hold, same
-// stream -- takes the share tables (share_upload) and launches ONE more
-// workgroup, k_sh_one, over k_ag_one's entries on the lane.  The run may be run
-// again (a value scratch that grows, a look-back retry), so k_sh_one gates
-// itself on the device (tm_dev.h launch_share_one) and reports into the lane's
-// status block; on the run that stands the host requires "picked" exactly when
-// total <= cap and the fan-out completed.  DP1_TOO_LARGE: the picks are made,
-// the grid dispatch finishes the deliveries.  More entries than k_fo_one takes:
-// the grid kernels as without pk, then queue_pick once, as route_batch_impl.
+// ---- the route family in place (include/tmatch.h): a 32-bit micro-batch whose
+// buffers all lie in tm_host_alloc memory is matched as ONE pairs segment of
+// the one-launch kernel (launch_small_segs, no combiner) into the lane's HBM
+// scratch, and one-workgroup kernels write the caller's mapped outputs -- one
+// synchronisation, no copy; the device never reads a caller's output.
+// ROUTE32_OTHER: the batch is not eligible (the caller takes route_batch_impl).
 constexpr int ROUTE32_OTHER = 1;   // (not a TM_ code)
 constexpr int DP1_GRID_HEAD = DP1_ST_WORDS;   // status word of the [M, T] a grid dispatch leaves (8-byte aligned)
 constexpr int SH1_HOST = DP1_GRID_HEAD + 4;   // k_sh_one's status words (its head 8-byte aligned)
@@ -4153,327 +4185,334 @@ constexpr int DP1_HOST_WORDS = SH1_HOST + SH1_ST_WORDS;
 static_assert(DP1_GRID_HEAD % 2 == 0, "the grid dispatch's head is two u64");
 static_assert((SH1_HOST + SH1_ST_HEAD) % 2 == 0, "the pick's head is two u64");
 
-static int route32_in_place(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint64_t nbytes,
-                            uint32_t n_dests, uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values,
-                            uint64_t cap, uint8_t *out_err, bool aggre, const RouteDispatch *dp = nullptr,
-                            const RoutePick *pk = nullptr) {
-    if (pk && !(dp && aggre)) return ROUTE32_OTHER;   // (the pick runs over k_ag_one's entries, beside k_dp_one)
-    HostBatch hb(ix);
-    bool ok = tb || !nbytes;
-    uint8_t *db = opt_dev(ix, tb, nbytes, ok);
-    uint8_t *dof = opt_dev(ix, to, (n + 1) * 4, ok);
-    uint8_t *dfo = opt_dev(ix, out_dest_offsets, ((uint64_t)n_dests + 2) * 4, ok);
-    uint8_t *dt = opt_dev(ix, out_topic, cap * 4, ok);
-    uint8_t *dv = opt_dev(ix, out_values, cap * 4, ok);
-    uint8_t *de = pinned_dev(ix, out_err, n);   // (required even for no topics)
-    const uint64_t dcap = dp ? std::min<uint64_t>(dp->dcap, 0xFFFFFFFFull) : 0;
-    uint64_t *dhd = dp ? reinterpret_cast<uint64_t *>(pinned_dev(ix, dp->out_head, 16)) : nullptr;
-    uint32_t *ddt = dp ? reinterpret_cast<uint32_t *>(opt_dev(ix, dp->out_topic, dcap * 4, ok)) : nullptr;
-    uint32_t *ddv = dp ? reinterpret_cast<uint32_t *>(opt_dev(ix, dp->out_value, dcap * 4, ok)) : nullptr;
-    uint32_t *dds = dp ? reinterpret_cast<uint32_t *>(opt_dev(ix, dp->out_sub, dcap * 4, ok)) : nullptr;
-    uint32_t *dsm = pk ? reinterpret_cast<uint32_t *>(opt_dev(ix, pk->out_member, cap * 4, ok)) : nullptr;
-    const uint32_t *dkc = pk ? reinterpret_cast<const uint32_t *>(opt_dev(ix, pk->key_clientid, n * 4, ok)) : nullptr;
-    const uint32_t *dkt = pk ? reinterpret_cast<const uint32_t *>(opt_dev(ix, pk->key_topic, n * 4, ok)) : nullptr;
-    if (!ok || !de || (dp && !dhd)) return ROUTE32_OTHER;
+// The device addresses of one request's buffers.  An absent or empty optional
+// buffer is null (opt_dev); the delivery arrays, the head, out_member and the
+// key arrays are looked at only when the request has a dispatch / a pick.
+struct Route32Dev {
+    const uint8_t *bytes, *offs;
+    uint32_t *fo, *topic, *value;
+    uint8_t *err;
+    uint64_t dcap;
+    uint64_t *head;
+    uint32_t *dtopic, *dvalue, *dsub;
+    uint32_t *member;
+    const uint32_t *kc, *kt;
+};
+
+// fills `v` (caller holds ix->mu: the list of tm_host_alloc buffers);
+// false: a buffer lies elsewhere, the batch is staged
+static bool route32_resolve(tm_index *ix, const RouteReq &rq, const uint32_t *to, uint64_t nbytes,
+                            uint32_t *out_dest_offsets, Route32Dev &v) {
+    const RouteDispatch *dp = rq.dp;
+    const RoutePick *pk = rq.pk;
+    bool ok = rq.tb || !nbytes;
+    const auto words = [&](const void *p, uint64_t k) { return reinterpret_cast<uint32_t *>(opt_dev(ix, p, k * 4, ok)); };
+    v.bytes = opt_dev(ix, rq.tb, nbytes, ok);
+    v.offs = opt_dev(ix, to, (rq.n + 1) * 4, ok);
+    v.fo = words(out_dest_offsets, (uint64_t)rq.n_dests + 2);
+    v.topic = words(rq.out_topic, rq.cap);
+    v.value = words(rq.out_values, rq.cap);
+    v.err = pinned_dev(ix, rq.out_err, rq.n);   // (required even for no topics)
+    v.dcap = dp ? std::min<uint64_t>(dp->dcap, 0xFFFFFFFFull) : 0;
+    v.head = dp ? reinterpret_cast<uint64_t *>(pinned_dev(ix, dp->out_head, 16)) : nullptr;
+    v.dtopic = dp ? words(dp->out_topic, v.dcap) : nullptr;
+    v.dvalue = dp ? words(dp->out_value, v.dcap) : nullptr;
+    v.dsub = dp ? words(dp->out_sub, v.dcap) : nullptr;
+    v.member = pk ? words(pk->out_member, rq.cap) : nullptr;
+    v.kc = pk ? words(pk->key_clientid, rq.n) : nullptr;
+    v.kt = pk ? words(pk->key_topic, rq.n) : nullptr;
+    return ok && v.err && (!dp || v.head);
+}
+
+// room on the lane for one attempt with vcap values: the match's pairs and
+// values; under aggre or dp k_fo_one's results, which then stay on the device
+// (k_ag_one / k_dp_one writes the caller's buffers); under both k_ag_one's too
+static int route32_scratch(tm_index *ix, Lane &ln, const RouteReq &rq, uint64_t vcap) {
     int rc;
-    if ((rc = hb.open(n + (uint64_t)SMALL_SEGS * SM_TOPICS))) return rc;
+    const hipStream_t s = ln.s;
+    const uint64_t nfo = (uint64_t)rq.n_dests + 2;
+    if ((rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, vcap))) return rc;
+    if ((rc = grow_dev(ix, s, ln.d_pr, ln.d_pr_cap, 2 * rq.n + 2))) return rc;
+    if (rq.aggre() || rq.dp) {
+        if ((rc = grow_dev(ix, s, ln.d_ft, ln.d_ft_cap, FO1_ENTRIES))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_fv, ln.d_fv_cap, FO1_ENTRIES))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_fo, ln.d_fo_cap, nfo))) return rc;
+    }
+    if (rq.aggre() && rq.dp) {
+        if ((rc = grow_dev(ix, s, ln.d_at, ln.d_at_cap, FO1_ENTRIES))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_av, ln.d_av_cap, FO1_ENTRIES))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_ao, ln.d_ao_cap, nfo))) return rc;
+    }
+    return TM_OK;
+}
+
+// Queues one attempt on the lane's stream (caller holds ix->mu): the segment
+// walk, the flags into the caller's out_err, then k_fo_one.  A plain route:
+// k_fo_one fans out into the caller's outputs -- two launches.  aggre alone:
+// k_fo_one's results stay on the lane and k_ag_one writes the outputs.  dp:
+// k_ag_one's (if any) stay there too, and ONE more launch of one workgroup,
+// k_dp_one, writes the route outputs, the head and the deliveries.  pk: in the
+// same lock hold, on the same stream, the share tables of this very run's
+// snapshot and ONE more workgroup, k_sh_one, over k_ag_one's entries.  The run
+// may be run again (a value scratch that grows, a look-back retry), so
+// k_sh_one gates itself on the device (tm_dev.h launch_share_one) and reports
+// into the lane's status block.
+static int route32_queue(tm_index *ix, Lane &ln, const RouteReq &rq, const Route32Dev &v, const DevIndex &d,
+                         uint32_t tag, uint64_t vcap) {
+    int rc;
+    const hipStream_t s = ln.s;
+    const uint64_t n = rq.n, cap = rq.cap;
+    const uint32_t n_dests = rq.n_dests;
+    const bool aggre = rq.aggre();
+    const RouteDispatch *dp = rq.dp;
+    volatile uint32_t *st = ln.fo1_h;
+    if (n) {
+        SmallSegs sg{};
+        sg.count = 1;
+        sg.pairs = 1;
+        sg.s[0] = SmallSeg{v.bytes ? v.bytes : v.offs, v.offs, ln.d_pr, v.err, ln.d_vals, vcap, (uint32_t)n, 0};
+        int path = PATH_SMALL;
+        HIPCHK(ix, launch_small_segs(d, ln.w, sg, true, tag, next_lb(ix), ix->small_kind, s, &path));
+        ix->path_batches[path]++;
+    }
+    const int grp = ix->rep[ln.r].group;
+    const uint32_t *dtab = nullptr, *ftab = nullptr;
+    uint64_t dlen = 0, flen = 0;
+    if ((rc = dest_upload(ix, grp, s, dtab, dlen))) return rc;
+    st[FO1_ST_STATE] = 0;   // (the lane's stream is idle: nothing else writes the words)
+    st[SH1_HOST + SH1_ST_STATE] = 0;
+    if (!aggre && !dp) {
+        HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, v.fo, v.topic, v.value, cap,
+                                     ln.fo1_d, s));
+        return TM_OK;
+    }
+    if (aggre && (rc = filter_upload(ix, grp, s, ftab, flen))) return rc;
+    uint32_t *lfo = reinterpret_cast<uint32_t *>(ln.d_fo);
+    HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, lfo, ln.d_ft, ln.d_fv, FO1_ENTRIES,
+                                 ln.fo1_s, s));
+    if (!dp) {
+        HIPCHK(ix, launch_aggre_one(ln.fo1_s, lfo, n_dests, ln.d_ft, ln.d_fv, ftab, flen, v.fo, v.topic, v.value, cap,
+                                    ln.fo1_d, s));
+        return TM_OK;
+    }
+    uint32_t *lao = nullptr, *st_dev = ln.fo1_s;
+    if (aggre) {   // (room for every entry k_fo_one completes: the pass always compacts)
+        lao = reinterpret_cast<uint32_t *>(ln.d_ao);
+        st_dev = ln.fo1_s + FO1_ST_WORDS;
+        HIPCHK(ix, launch_aggre_one(ln.fo1_s, lfo, n_dests, ln.d_ft, ln.d_fv, ftab, flen, lao, ln.d_at, ln.d_av,
+                                    FO1_ENTRIES, st_dev, s));
+    }
+    const uint32_t *span = nullptr, *pool = nullptr;
+    uint64_t span_len = 0, pool_len = 0;
+    if ((rc = subs_upload(ix, grp, s, span, span_len, pool, pool_len))) return rc;
+    HIPCHK(ix, launch_dispatch_one(st_dev, lfo, ln.d_ft, ln.d_fv, lao, ln.d_at, ln.d_av, n_dests, dp->local_dest, span,
+                                   span_len, pool, pool_len, v.fo, v.topic, v.value, cap, v.head, v.dtopic, v.dvalue,
+                                   v.dsub, v.dcap, ix->dp1_max, ln.fo1_d, s));
+    if (!rq.pk) return TM_OK;
+    const uint32_t *slot_of = nullptr, *rec = nullptr, *spool = nullptr;
+    uint64_t slot_len = 0, n_slots = 0, spool_len = 0;
+    uint32_t *state = nullptr;
+    if ((rc = share_upload(ix, grp, s, slot_of, slot_len, rec, n_slots, spool, spool_len, state))) return rc;
+    HIPCHK(ix, launch_share_one(st_dev, n ? ln.w.hint_d + HINT_FAIL : nullptr, lao, n_dests, ln.d_at, ln.d_av, vcap, cap,
+                                v.kc, v.kt, n, rq.pk->seed, slot_of, slot_len, rec, n_slots, spool, spool_len, state,
+                                v.member, ln.fo1_d + SH1_HOST, s));
+    return TM_OK;
+}
+
+// k_sh_one's status against the host's view of the run that stands: it picked
+// (and moved the state, once) exactly when the caller gets the entries --
+// total <= cap and the fan-out completed
+static int route32_pick_status(tm_index *ix, Lane &ln, const RouteReq &rq, uint64_t total, uint32_t state) {
+    const uint32_t ps = ln.fo1_h[SH1_HOST + SH1_ST_STATE];
+    const bool want = total <= rq.cap && (state == FO1_DONE || state == (uint32_t)DP1_TOO_LARGE);
+    if ((ps != SH1_PICKED && ps != SH1_SKIPPED) || (ps == SH1_PICKED) != want)
+        return route_fail(ix, rq, TM_EDEVICE, "the pick kernel and the host disagree on whether the run stands");
+    if (want) ix->publish_one++;
+    return TM_OK;
+}
+
+// ending 1, FO1_DONE: everything is in the caller's buffers
+static int route32_end_in_place(tm_index *ix, Lane &ln, const RouteReq &rq, uint64_t total) {
+    if (!rq.dp) {
+        ix->route_one++;
+        return total > rq.cap ? TM_ECAP : TM_OK;
+    }
+    ix->dispatch_one++;
+    const volatile uint32_t *st = ln.fo1_h;
+    const uint64_t T = (uint64_t)st[DP1_ST_T_HI] << 32 | st[DP1_ST_T_LO];
+    return total > rq.cap || T > rq.dp->dcap ? TM_ECAP : TM_OK;
+}
+
+// the [M, T] a grid dispatch left with the lane's status words, to the caller
+static int route32_grid_head(tm_index *ix, Lane &ln, const RouteReq &rq, uint64_t total) {
+    const volatile uint64_t *gh = reinterpret_cast<const volatile uint64_t *>(ln.fo1_h + DP1_GRID_HEAD);
+    rq.dp->out_head[0] = gh[0];
+    rq.dp->out_head[1] = gh[1];
+    ix->dispatch_grid++;
+    return total > rq.cap || gh[1] > rq.dp->dcap ? TM_ECAP : TM_OK;
+}
+
+// ending 2, DP1_TOO_LARGE: more deliveries than one workgroup should write
+// (dp1_max).  The route outputs are in place (and under pk the picks are
+// made); the grid kernels (launch_dispatch) expand the bucket of the arrays on
+// the lane (their u32 offsets widened beside them) straight into the caller's
+// buffers
+static int route32_end_grid_dispatch(tm_index *ix, HostBatch &hb, const RouteReq &rq, const Route32Dev &v, uint64_t total) {
+    int rc;
     Lane &ln = *hb.ln;
     const hipStream_t s = ln.s;
+    const bool aggre = rq.aggre();
+    const uint64_t nfo = (uint64_t)rq.n_dests + 2;
+    if ((rc = hb.relock())) return rc;
+    if ((rc = ensure_dispatch(ix, ln, FO1_ENTRIES, true))) return rc;
+    if ((rc = grow_dev(ix, s, ln.d_o64, ln.d_o64_cap, nfo))) return rc;
+    HIPCHK(ix, launch_offs_widen(reinterpret_cast<const uint32_t *>(aggre ? ln.d_ao : ln.d_fo), ln.d_o64, nfo, s));
+    if ((rc = queue_dispatch_to(ix, ln, rq.n_dests, rq.dp->local_dest, ln.d_o64, aggre, FO1_ENTRIES, v.dcap,
+                                reinterpret_cast<uint64_t *>(ln.fo1_d + DP1_GRID_HEAD), v.dtopic, v.dvalue, v.dsub)))
+        return rc;
+    if ((rc = batch_done(ix, ln))) return rc;
+    hb.g.unlock();
+    HIPCHK(ix, hipStreamSynchronize(s));
+    return route32_grid_head(ix, ln, rq, total);
+}
+
+// ending 3, FO1_TOO_LARGE: more entries than k_fo_one takes.  The grid kernels
+// run on the same pairs (no second walk) into the lane's scratch, copied out
+// and narrowed; a dispatch writes the deliveries straight into the caller's
+// buffers; a pick follows as in route_batch_impl (pick_after_run).
+// (under aggre with total > cap: TM_ECAP, the un-aggregated sizes, no entries;
+// a dispatch reads the aggregated arrays all the same)
+static int route32_end_grid(tm_index *ix, HostBatch &hb, const RouteReq &rq, const Route32Dev &v,
+                            uint32_t *out_dest_offsets, uint64_t total, uint64_t vcap) {
+    int rc;
+    Lane &ln = *hb.ln;
+    const uint32_t n_dests = rq.n_dests;
+    const RouteDispatch *dp = rq.dp;
+    const bool ag_out = rq.aggre() && total <= rq.cap, ag = rq.aggre() && (dp || ag_out);
+    std::vector<uint64_t> fo;
+    try {
+        fo.resize((uint64_t)n_dests + 2);
+    } catch (const std::bad_alloc &) {
+        return route_fail(ix, rq, TM_ENOMEM, "out of host memory");
+    }
+    if ((rc = hb.relock())) return rc;
+    if ((rc = route_scratch(ix, ln, n_dests, vcap, ag, true, rq.n))) return rc;
+    if (dp && (rc = ensure_dispatch(ix, ln, vcap, true))) return rc;
+    if ((rc = queue_grid_fanout(ix, ln, rq.n, nullptr, ln.d_pr, vcap, n_dests, ag))) return rc;
+    if (dp && (rc = queue_dispatch_to(ix, ln, n_dests, dp->local_dest, ag ? ln.d_ao : ln.d_fo, ag, vcap, v.dcap,
+                                      reinterpret_cast<uint64_t *>(ln.fo1_d + DP1_GRID_HEAD), v.dtopic, v.dvalue, v.dsub)))
+        return rc;
+    if ((rc = batch_done(ix, ln))) return rc;
+    hb.g.unlock();
+    rc = copy_route_out(ix, ln, n_dests, total, rq.cap, rq.aggre(), ag_out, fo.data(), out_dest_offsets, rq.out_topic,
+                        rq.out_values);
+    if (rc != TM_OK && rc != TM_ECAP) return rc;
+    if (rq.pk && ag_out)
+        if (int prc = pick_after_run(ix, hb, rq, vcap, std::min(fo[n_dests + 1], rq.cap))) return prc;
+    if (rq.pk) ix->publish_grid++;
+    if (dp) return route32_grid_head(ix, ln, rq, total);
+    ix->route_grid++;
+    return rc;
+}
+
+// the in-place attempt of route_batch32: the stages above, in order
+static int route32_in_place(tm_index *ix, const RouteReq &rq, const uint32_t *to, uint64_t nbytes,
+                            uint32_t *out_dest_offsets) {
+    HostBatch hb(ix, rq.who);
+    Route32Dev v;
+    if (!route32_resolve(ix, rq, to, nbytes, out_dest_offsets, v)) return ROUTE32_OTHER;
+    int rc;
+    const uint64_t n = rq.n;
+    if ((rc = hb.open(n + (uint64_t)SMALL_SEGS * SM_TOPICS))) return rc;
+    Lane &ln = *hb.ln;
     if (n && !small_path_ok(dev_view(ix, ln.r), n)) return ROUTE32_OTHER;
     ix->rep[ln.r].batches++;
     if (!ln.fo1_h) {
         HIPCHK(ix, hipHostMalloc(&ln.fo1_h, DP1_HOST_WORDS * 4, hipHostMallocMapped));
         HIPCHK(ix, hipHostGetDevicePointer(reinterpret_cast<void **>(&ln.fo1_d), ln.fo1_h, 0));
     }
-    if ((aggre || dp) && !ln.fo1_s) HIPCHK(ix, hipMalloc(&ln.fo1_s, 2 * FO1_ST_WORDS * 4));
+    if ((rq.aggre() || rq.dp) && !ln.fo1_s) HIPCHK(ix, hipMalloc(&ln.fo1_s, 2 * FO1_ST_WORDS * 4));
     volatile uint32_t *st = ln.fo1_h;
-    uint64_t *ghead = reinterpret_cast<uint64_t *>(ln.fo1_d + DP1_GRID_HEAD);
     uint64_t total = 0, vcap = std::max<uint64_t>({ln.d_vals_cap, 4 * n, 1 << 16});
     for (int attempt = 0;; attempt++) {
-        if (vcap > 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch32: more than 2^32 - 1 hits in one batch");
-        if ((rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, vcap))) return rc;
-        if ((rc = grow_dev(ix, s, ln.d_pr, ln.d_pr_cap, 2 * n + 2))) return rc;
-        if (aggre || dp) {   // k_fo_one's results stay on the device: k_ag_one / k_dp_one writes the caller's buffers
-            if ((rc = grow_dev(ix, s, ln.d_ft, ln.d_ft_cap, FO1_ENTRIES))) return rc;
-            if ((rc = grow_dev(ix, s, ln.d_fv, ln.d_fv_cap, FO1_ENTRIES))) return rc;
-            if ((rc = grow_dev(ix, s, ln.d_fo, ln.d_fo_cap, (uint64_t)n_dests + 2))) return rc;
-        }
-        if (aggre && dp) {   // and k_ag_one's
-            if ((rc = grow_dev(ix, s, ln.d_at, ln.d_at_cap, FO1_ENTRIES))) return rc;
-            if ((rc = grow_dev(ix, s, ln.d_av, ln.d_av_cap, FO1_ENTRIES))) return rc;
-            if ((rc = grow_dev(ix, s, ln.d_ao, ln.d_ao_cap, (uint64_t)n_dests + 2))) return rc;
-        }
-        rc = hb.run([&](const DevIndex &d, uint32_t tag) -> int {
-            int rc;
-            if (n) {
-                SmallSegs sg{};
-                sg.count = 1;
-                sg.pairs = 1;
-                sg.s[0] = SmallSeg{db ? db : dof, dof, ln.d_pr, de, ln.d_vals, vcap, (uint32_t)n, 0};
-                int path = PATH_SMALL;
-                HIPCHK(ix, launch_small_segs(d, ln.w, sg, true, tag, next_lb(ix), ix->small_kind, s, &path));
-                ix->path_batches[path]++;
-            }
-            const int grp = ix->rep[ln.r].group;
-            const uint32_t *dtab = nullptr, *ftab = nullptr;
-            uint64_t dlen = 0, flen = 0;
-            if ((rc = dest_upload(ix, grp, s, dtab, dlen))) return rc;
-            st[FO1_ST_STATE] = 0;   // (the lane's stream is idle: nothing else writes the words)
-            st[SH1_HOST + SH1_ST_STATE] = 0;
-            uint32_t *fo32 = reinterpret_cast<uint32_t *>(dfo), *t32 = reinterpret_cast<uint32_t *>(dt),
-                     *v32 = reinterpret_cast<uint32_t *>(dv);
-            if (!aggre && !dp) {
-                HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, fo32, t32, v32, cap, ln.fo1_d, s));
-                return TM_OK;
-            }
-            if (aggre && (rc = filter_upload(ix, grp, s, ftab, flen))) return rc;
-            uint32_t *lfo = reinterpret_cast<uint32_t *>(ln.d_fo);
-            HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, lfo, ln.d_ft, ln.d_fv,
-                                         FO1_ENTRIES, ln.fo1_s, s));
-            if (!dp) {
-                HIPCHK(ix, launch_aggre_one(ln.fo1_s, lfo, n_dests, ln.d_ft, ln.d_fv, ftab, flen, fo32, t32, v32, cap,
-                                            ln.fo1_d, s));
-                return TM_OK;
-            }
-            uint32_t *lao = nullptr, *st_dev = ln.fo1_s;
-            if (aggre) {   // (room for every entry k_fo_one completes: the pass always compacts)
-                lao = reinterpret_cast<uint32_t *>(ln.d_ao);
-                st_dev = ln.fo1_s + FO1_ST_WORDS;
-                HIPCHK(ix, launch_aggre_one(ln.fo1_s, lfo, n_dests, ln.d_ft, ln.d_fv, ftab, flen, lao, ln.d_at, ln.d_av,
-                                            FO1_ENTRIES, st_dev, s));
-            }
-            const uint32_t *span = nullptr, *pool = nullptr;
-            uint64_t span_len = 0, pool_len = 0;
-            if ((rc = subs_upload(ix, grp, s, span, span_len, pool, pool_len))) return rc;
-            HIPCHK(ix, launch_dispatch_one(st_dev, lfo, ln.d_ft, ln.d_fv, lao, ln.d_at, ln.d_av, n_dests, dp->local_dest,
-                                           span, span_len, pool, pool_len, fo32, t32, v32, cap, dhd, ddt, ddv, dds, dcap,
-                                           ix->dp1_max, ln.fo1_d, s));
-            if (pk) {   // the share tables of this very run's snapshot; the kernel gates itself (the run may not stand)
-                const uint32_t *slot_of = nullptr, *rec = nullptr, *spool = nullptr;
-                uint64_t slot_len = 0, n_slots = 0, spool_len = 0;
-                uint32_t *state = nullptr;
-                if ((rc = share_upload(ix, grp, s, slot_of, slot_len, rec, n_slots, spool, spool_len, state))) return rc;
-                HIPCHK(ix, launch_share_one(st_dev, n ? ln.w.hint_d + HINT_FAIL : nullptr, lao, n_dests, ln.d_at, ln.d_av,
-                                            vcap, cap, dkc, dkt, n, pk->seed, slot_of, slot_len, rec, n_slots, spool,
-                                            spool_len, state, dsm, ln.fo1_d + SH1_HOST, s));
-            }
-            return TM_OK;
-        });
+        if (vcap > 0xFFFFFFFFull) return route_fail(ix, rq, TM_EINVAL, "more than 2^32 - 1 hits in one batch");
+        if ((rc = route32_scratch(ix, ln, rq, vcap))) return rc;
+        rc = hb.run([&](const DevIndex &d, uint32_t tag) { return route32_queue(ix, ln, rq, v, d, tag, vcap); });
         if (rc) return rc;
         total = st[FO1_ST_TOTAL];
         if (total <= vcap) break;
-        if (attempt >= 2) return fail(ix, TM_EDEVICE, "tm_route_batch32: hit total kept growing past the value scratch");
+        if (attempt >= 2) return route_fail(ix, rq, TM_EDEVICE, "hit total kept growing past the value scratch");
         vcap = total + total / 4;
         if ((rc = hb.relock())) return rc;
     }
     const uint32_t state = st[FO1_ST_STATE];
-    if (pk) {
-        // the run stands: k_sh_one picked (and moved the state, once) exactly when the caller gets the entries
-        const uint32_t ps = st[SH1_HOST + SH1_ST_STATE];
-        const bool want = total <= cap && (state == FO1_DONE || state == (uint32_t)DP1_TOO_LARGE);
-        if ((ps != SH1_PICKED && ps != SH1_SKIPPED) || (ps == SH1_PICKED) != want)
-            return fail(ix, TM_EDEVICE, "tm_publish_batch32: the pick kernel and the host disagree on whether the run stands");
-        if (want) ix->publish_one++;
+    if (rq.pk && (rc = route32_pick_status(ix, ln, rq, total, state))) return rc;
+    if (state == FO1_DONE) return route32_end_in_place(ix, ln, rq, total);
+    if (rq.dp && state == DP1_TOO_LARGE) return route32_end_grid_dispatch(ix, hb, rq, v, total);
+    if (state != FO1_TOO_LARGE) return route_fail(ix, rq, TM_EDEVICE, "the fan-out kernel left no status");
+    return route32_end_grid(ix, hb, rq, v, out_dest_offsets, total, vcap);
+}
+
+// The three 32-bit calls (include/tmatch.h): in place when the batch is a
+// micro-batch whose buffers lie in tm_host_alloc memory; every other batch
+// widened, run by route_batch_impl, and narrowed.
+static int route_batch32(tm_index *ix, RouteReq rq, const uint32_t *to, uint32_t *out_dest_offsets) {
+    if (int rc = route_check(ix, rq, to && out_dest_offsets, true)) return rc;
+    const uint64_t n = rq.n;
+    const uint64_t nbytes = n ? to[n] : 0;   // (before the lock: in TM_ALLOC_VRAM memory a host read is a PCIe round trip)
+    if (n && !rq.tb && nbytes != to[0]) return route_fail(ix, rq, TM_EINVAL, "null buffer");
+    if (rq.cap > 0xFFFFFFFFull) rq.cap = 0xFFFFFFFFull;   // (32-bit positions)
+    if (n <= FO1_TOPICS && rq.n_dests <= FO1_MAX_DESTS && ((uintptr_t)rq.tb & 15) == 0) {
+        const int rc = route32_in_place(ix, rq, to, nbytes, out_dest_offsets);
+        if (rc != ROUTE32_OTHER) return rc;
     }
-    if (state == FO1_DONE) {
-        if (!dp) {
-            ix->route_one++;
-            return total > cap ? TM_ECAP : TM_OK;
-        }
-        ix->dispatch_one++;
-        const uint64_t T = (uint64_t)st[DP1_ST_T_HI] << 32 | st[DP1_ST_T_LO];
-        return total > cap || T > dp->dcap ? TM_ECAP : TM_OK;
-    }
-    // the [M, T] a grid dispatch left with the lane's status words, to the caller
-    const auto grid_head = [&]() -> int {
-        const volatile uint64_t *gh = reinterpret_cast<const volatile uint64_t *>(ln.fo1_h + DP1_GRID_HEAD);
-        dp->out_head[0] = gh[0];
-        dp->out_head[1] = gh[1];
-        ix->dispatch_grid++;
-        return total > cap || gh[1] > dp->dcap ? TM_ECAP : TM_OK;
-    };
-    if (dp && state == DP1_TOO_LARGE) {
-        // more deliveries than one workgroup should write: the route outputs are
-        // in place; the grid kernels expand the bucket of the arrays on the lane
-        // (their u32 offsets widened beside them) into the caller's buffers
-        if ((rc = hb.relock())) return rc;
-        if ((rc = ensure_dispatch(ix, ln, FO1_ENTRIES, true))) return rc;
-        if ((rc = grow_dev(ix, s, ln.d_o64, ln.d_o64_cap, (uint64_t)n_dests + 2))) return rc;
-        HIPCHK(ix, launch_offs_widen(reinterpret_cast<const uint32_t *>(aggre ? ln.d_ao : ln.d_fo), ln.d_o64,
-                                     (uint64_t)n_dests + 2, s));
-        if ((rc = queue_dispatch_to(ix, ln, n_dests, dp->local_dest, ln.d_o64, aggre, FO1_ENTRIES, dcap, ghead, ddt, ddv,
-                                    dds)))
-            return rc;
-        if ((rc = batch_done(ix, ln))) return rc;
-        hb.g.unlock();
-        HIPCHK(ix, hipStreamSynchronize(s));
-        return grid_head();
-    }
-    if (state != FO1_TOO_LARGE) return fail(ix, TM_EDEVICE, "tm_route_batch32: the fan-out kernel left no status");
-    // more entries than k_fo_one takes: the grid kernels on the same pairs (no
-    // second walk), into the lane's scratch, copied out and narrowed
-    // (under aggre with total > cap: TM_ECAP, the un-aggregated sizes, no
-    // entries; a dispatch reads the aggregated arrays all the same)
-    const bool ag_out = aggre && total <= cap, ag = aggre && (dp || ag_out);
-    std::vector<uint64_t> fo;
+    // (the buffers kept per thread: a fresh 128 KB vector per call is an mmap and its page faults)
+    static thread_local std::vector<uint64_t> o64, fo;
     try {
-        fo.resize((uint64_t)n_dests + 2);
+        o64.assign(to, to + n + 1);
+        fo.resize((uint64_t)rq.n_dests + 2);
     } catch (const std::bad_alloc &) {
-        return fail(ix, TM_ENOMEM, "tm_route_batch32: out of host memory");
+        return route_fail(ix, rq, TM_ENOMEM, "out of host memory");
     }
-    if ((rc = hb.relock())) return rc;
-    if ((rc = route_scratch(ix, ln, n_dests, vcap, ag, true, n))) return rc;
-    if (dp && (rc = ensure_dispatch(ix, ln, vcap, true))) return rc;
-    if ((rc = queue_grid_fanout(ix, ln, n, nullptr, ln.d_pr, vcap, n_dests, ag))) return rc;
-    if (dp) {
-        if ((rc = queue_dispatch_to(ix, ln, n_dests, dp->local_dest, ag ? ln.d_ao : ln.d_fo, ag, vcap, dcap, ghead, ddt,
-                                    ddv, dds)))
-            return rc;
-    }
-    if ((rc = batch_done(ix, ln))) return rc;
-    hb.g.unlock();
-    rc = copy_route_out(ix, ln, n_dests, total, cap, aggre, ag_out, fo.data(), out_dest_offsets, out_topic, out_values);
+    const int rc = route_batch_impl(ix, rq, o64.data(), fo.data());
     if (rc != TM_OK && rc != TM_ECAP) return rc;
-    if (pk && ag_out) {
-        // the route outputs are out and the caller has the kept entries: the grid pick, once (route_batch_impl's rule)
-        if ((rc = hb.relock())) return rc;
-        if ((rc = queue_pick(ix, ln, n, n_dests, vcap, *pk))) return rc;
-        if ((rc = batch_done(ix, ln))) return rc;
-        hb.g.unlock();
-        const uint64_t kept = std::min(fo[n_dests + 1], cap);
-        if (kept) HIPCHK(ix, hipMemcpyAsync(pk->out_member, ln.d_sm, kept * 4, hipMemcpyDefault, s));
-        HIPCHK(ix, hipStreamSynchronize(s));
-    }
-    if (pk) ix->publish_grid++;
-    if (dp) return grid_head();
-    ix->route_grid++;
+    for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
+    (rq.pk ? ix->publish_grid : rq.dp ? ix->dispatch_grid : ix->route_grid)++;
     return rc;
 }
 
 int tm_route_batch32_ex(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint32_t n_dests,
                         uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
                         uint8_t *out_err, uint32_t flags) {
-    if (!ix) return fail(nullptr, TM_EINVAL, "tm_route_batch32: null handle");
-    if (flags & ~(uint32_t)TM_ROUTE_AGGRE) return fail(ix, TM_EINVAL, "tm_route_batch32: unknown flag");
-    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_route_batch32: n_dests must be 1 .. 65536");
-    if (!to || !out_dest_offsets || !out_err || (cap && (!out_topic || !out_values)))
-        return fail(ix, TM_EINVAL, "tm_route_batch32: null buffer");
-    if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_route_batch32: batch too large");
-    const uint64_t nbytes = n ? to[n] : 0;   // (before the lock: in TM_ALLOC_VRAM memory a host read is a PCIe round trip)
-    if (n && !tb && nbytes != to[0]) return fail(ix, TM_EINVAL, "tm_route_batch32: null buffer");
-    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
-    if (n <= FO1_TOPICS && n_dests <= FO1_MAX_DESTS && ((uintptr_t)tb & 15) == 0) {
-        const int rc = route32_in_place(ix, n, tb, to, nbytes, n_dests, out_dest_offsets, out_topic, out_values, cap,
-                                        out_err, flags & TM_ROUTE_AGGRE);
-        if (rc != ROUTE32_OTHER) return rc;
-    }
-    // every other batch: widened, tm_route_batch, narrowed (the buffers kept per
-    // thread: a fresh 128 KB vector per call is an mmap and its page faults)
-    static thread_local std::vector<uint64_t> o64, fo;
-    try {
-        o64.assign(to, to + n + 1);
-        fo.resize((uint64_t)n_dests + 2);
-    } catch (const std::bad_alloc &) {
-        return fail(ix, TM_ENOMEM, "tm_route_batch32: out of host memory");
-    }
-    const int rc = tm_route_batch_ex(ix, n, tb, o64.data(), n_dests, fo.data(), out_topic, out_values, cap, out_err, flags);
-    if (rc != TM_OK && rc != TM_ECAP) return rc;
-    for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
-    ix->route_grid++;
-    return rc;
+    return route_batch32(ix, {"tm_route_batch32_ex", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, nullptr, nullptr},
+                         to, out_dest_offsets);
 }
 
 int tm_route_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint32_t n_dests,
                      uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
                      uint8_t *out_err) {
-    return tm_route_batch32_ex(ix, n, tb, to, n_dests, out_dest_offsets, out_topic, out_values, cap, out_err, 0);
+    return route_batch32(ix, {"tm_route_batch32", n, tb, n_dests, 0, out_topic, out_values, cap, out_err, nullptr, nullptr}, to,
+                         out_dest_offsets);
 }
 
-// tm_dispatch_batch with 32-bit offsets (include/tmatch.h): in place under
-// tm_route_batch32's conditions when the head and the delivery arrays lie in
-// tm_host_alloc memory too; every other batch widened, run by
-// tm_dispatch_batch, and narrowed.
 int tm_dispatch_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint32_t n_dests,
                         uint32_t local_dest, uint32_t flags, uint32_t *out_dest_offsets, uint32_t *out_topic,
                         uint32_t *out_values, uint64_t cap, uint64_t *out_head, uint32_t *out_dtopic,
                         uint32_t *out_dvalue, uint32_t *out_dsub, uint64_t dcap, uint8_t *out_err) {
-    if (!ix) return fail(nullptr, TM_EINVAL, "tm_dispatch_batch32: null handle");
-    if (flags & ~(uint32_t)TM_ROUTE_AGGRE) return fail(ix, TM_EINVAL, "tm_dispatch_batch32: unknown flag");
-    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_dispatch_batch32: n_dests must be 1 .. 65536");
-    if (local_dest >= n_dests) return fail(ix, TM_EINVAL, "tm_dispatch_batch32: local_dest must be below n_dests");
-    if (!to || !out_dest_offsets || !out_err || (cap && (!out_topic || !out_values)) || !out_head ||
-        (dcap && (!out_dtopic || !out_dvalue || !out_dsub)))
-        return fail(ix, TM_EINVAL, "tm_dispatch_batch32: null buffer");
-    if ((uintptr_t)out_head & 7) return fail(ix, TM_EINVAL, "tm_dispatch_batch32: out_head must be 8-byte aligned");
-    if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_dispatch_batch32: batch too large");
-    const uint64_t nbytes = n ? to[n] : 0;   // (before the lock: in TM_ALLOC_VRAM memory a host read is a PCIe round trip)
-    if (n && !tb && nbytes != to[0]) return fail(ix, TM_EINVAL, "tm_dispatch_batch32: null buffer");
-    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
-    if (n <= FO1_TOPICS && n_dests <= FO1_MAX_DESTS && ((uintptr_t)tb & 15) == 0) {
-        const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
-        const int rc = route32_in_place(ix, n, tb, to, nbytes, n_dests, out_dest_offsets, out_topic, out_values, cap,
-                                        out_err, flags & TM_ROUTE_AGGRE, &dp);
-        if (rc != ROUTE32_OTHER) return rc;
-    }
-    static thread_local std::vector<uint64_t> o64, fo;
-    try {
-        o64.assign(to, to + n + 1);
-        fo.resize((uint64_t)n_dests + 2);
-    } catch (const std::bad_alloc &) {
-        return fail(ix, TM_ENOMEM, "tm_dispatch_batch32: out of host memory");
-    }
-    const int rc = tm_dispatch_batch(ix, n, tb, o64.data(), n_dests, local_dest, flags, fo.data(), out_topic, out_values,
-                                     cap, out_head, out_dtopic, out_dvalue, out_dsub, dcap, out_err);
-    if (rc != TM_OK && rc != TM_ECAP) return rc;
-    for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
-    ix->dispatch_grid++;
-    return rc;
+    const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
+    return route_batch32(ix, {"tm_dispatch_batch32", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, &dp, nullptr},
+                         to, out_dest_offsets);
 }
 
-// tm_publish_batch with 32-bit offsets (include/tmatch.h): in place under
-// tm_dispatch_batch32's conditions when out_member and the key arrays given lie
-// in tm_host_alloc memory too; every other batch widened, run by
-// tm_publish_batch, and narrowed.
 int tm_publish_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint32_t n_dests,
                        uint32_t local_dest, uint32_t flags, uint32_t *out_dest_offsets, uint32_t *out_topic,
                        uint32_t *out_values, uint64_t cap, uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue,
                        uint32_t *out_dsub, uint64_t dcap, const uint32_t *key_clientid, const uint32_t *key_topic,
                        uint32_t seed, uint32_t *out_member, uint8_t *out_err) {
-    if (!ix) return fail(nullptr, TM_EINVAL, "tm_publish_batch32: null handle");
-    if (flags & ~(uint32_t)TM_ROUTE_AGGRE) return fail(ix, TM_EINVAL, "tm_publish_batch32: unknown flag");
-    if (!(flags & TM_ROUTE_AGGRE))
-        return fail(ix, TM_EINVAL, "tm_publish_batch32: TM_ROUTE_AGGRE is required (aggre/1 runs before route/2)");
-    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_publish_batch32: n_dests must be 1 .. 65536");
-    if (local_dest >= n_dests) return fail(ix, TM_EINVAL, "tm_publish_batch32: local_dest must be below n_dests");
-    if (!to || !out_dest_offsets || !out_err || (cap && (!out_topic || !out_values || !out_member)) || !out_head ||
-        (dcap && (!out_dtopic || !out_dvalue || !out_dsub)))
-        return fail(ix, TM_EINVAL, "tm_publish_batch32: null buffer");
-    if ((uintptr_t)out_head & 7) return fail(ix, TM_EINVAL, "tm_publish_batch32: out_head must be 8-byte aligned");
-    if (n >= 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_publish_batch32: batch too large");
-    const uint64_t nbytes = n ? to[n] : 0;   // (before the lock: in TM_ALLOC_VRAM memory a host read is a PCIe round trip)
-    if (n && !tb && nbytes != to[0]) return fail(ix, TM_EINVAL, "tm_publish_batch32: null buffer");
-    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
-    if (n <= FO1_TOPICS && n_dests <= FO1_MAX_DESTS && ((uintptr_t)tb & 15) == 0) {
-        const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
-        const RoutePick pk{key_clientid, key_topic, seed, out_member};
-        const int rc = route32_in_place(ix, n, tb, to, nbytes, n_dests, out_dest_offsets, out_topic, out_values, cap,
-                                        out_err, true, &dp, &pk);
-        if (rc != ROUTE32_OTHER) return rc;
-    }
-    static thread_local std::vector<uint64_t> o64, fo;
-    try {
-        o64.assign(to, to + n + 1);
-        fo.resize((uint64_t)n_dests + 2);
-    } catch (const std::bad_alloc &) {
-        return fail(ix, TM_ENOMEM, "tm_publish_batch32: out of host memory");
-    }
-    const int rc = tm_publish_batch(ix, n, tb, o64.data(), n_dests, local_dest, flags, fo.data(), out_topic, out_values,
-                                    cap, out_head, out_dtopic, out_dvalue, out_dsub, dcap, key_clientid, key_topic, seed,
-                                    out_member, out_err);
-    if (rc != TM_OK && rc != TM_ECAP) return rc;
-    for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
-    ix->publish_grid++;
-    return rc;
+    const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
+    const RoutePick pk{key_clientid, key_topic, seed, out_member};
+    return route_batch32(ix, {"tm_publish_batch32", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, &dp, &pk}, to,
+                         out_dest_offsets);
 }
 
 int tm_match_batch32_dev(tm_index *ix, uint64_t n, const uint8_t *bytes, const uint32_t *offs, uint32_t *hit_offs,

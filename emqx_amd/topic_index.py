@@ -345,12 +345,13 @@ class Tab:
         blob, offs = _native.pack_strings(topics)
         return self._index.dispatch_batch(blob, offs, n_dests, local_dest, aggre=aggre)
 
-    def _route_set(self, n: int, nbytes: int, n_dests: int, cap: int, dcap: int | None = None) -> dict:
+    def _route_set(self, n: int, nbytes: int, n_dests: int, cap: int, dcap: int | None = None, pick: bool = False) -> dict:
         """A set of pinned buffers (host_array) large enough for the batch, from
         the pool or new -- what a NIF keeps per scheduler.  Arrays too small are
         replaced; the set goes back with _route_put.  dcap: the head and the
         three delivery arrays of dispatch_kids32 as well (a set that never
-        dispatched has none)."""
+        dispatched has none); pick: publish_kids32's member array -- a pick per
+        entry the set has room for -- and its two key arrays."""
         with self._lock:
             s = self._route_pool.pop() if self._route_pool else {}
         want = {"blob": (nbytes + 16, np.uint8), "offs": (n + 1, np.uint32), "doff": (n_dests + 2, np.uint32),
@@ -358,12 +359,19 @@ class Tab:
         if dcap is not None:
             want.update({"head": (2, np.uint64), "dtopic": (dcap, np.uint32), "dvals": (dcap, np.uint32),
                          "dsubs": (dcap, np.uint32)})
+        if pick:
+            want.update({"member": (max(cap, len(s.get("topic", ()))), np.uint32), "kc": (max(n, 1), np.uint32),
+                         "kt": (max(n, 1), np.uint32)})
         for name, (need, dt) in want.items():
             if name not in s or len(s[name]) < need:
-                if name in s:
-                    self._index.host_free(s.pop(name))
-                s[name] = self._index.host_array(need + need // 4, dt)
+                self._route_grow(s, name, need, dt)
         return s
+
+    def _route_grow(self, s: dict, name: str, need: int, dt=np.uint32):
+        """array `name` of the set replaced by one with room for `need` and a quarter"""
+        if name in s:
+            self._index.host_free(s.pop(name))
+        s[name] = self._index.host_array(need + need // 4, dt)
 
     def _route_put(self, s: dict):
         with self._lock:
@@ -373,37 +381,86 @@ class Tab:
         for a in s.values():
             self._index.host_free(a)
 
+    def _kids32(self, topics, n_dests: int, local_dest: int | None = None, aggre: bool = False, pick=None):
+        """The pooled, in-place call behind route_kids32 (local_dest None),
+        dispatch_kids32 and publish_kids32 (pick: (key_clientid, key_topic,
+        seed); always with aggre) -> (route outputs, deliveries or (), members
+        or None), copies: the buffers go back to the pool.  One retry on TM_ECAP."""
+        self.flush()
+        ix = self._index
+        blob, offs = _native.pack_strings(topics)
+        n, nbytes = len(offs) - 1, int(offs[-1])
+        if nbytes >= 1 << 32:   # no 32-bit offsets for them: the staged calls
+            if local_dest is None:
+                return ix.route_batch(blob, offs, n_dests, aggre=aggre), (), None
+            if pick is None:
+                return ix.dispatch_batch(blob, offs, n_dests, local_dest, aggre=aggre) + (None,)
+            return ix.publish_batch(blob, offs, n_dests, local_dest, key_clientid=pick[0], key_topic=pick[1], seed=pick[2])
+        first = max(4 * n, 1024)
+        s = self._route_set(n, nbytes, n_dests, first, None if local_dest is None else first, pick is not None)
+
+        def copied(doff, tidx, kids, err):
+            return doff.astype(np.uint64), tidx.copy(), kids.copy(), err.copy()
+        try:
+            s["blob"][:nbytes] = blob[:nbytes]
+            s["offs"][: n + 1] = offs
+            keys = []
+            for name, k in (("kc", pick[0]), ("kt", pick[1])) if pick is not None else ():
+                if k is None:
+                    keys.append(None)
+                    continue
+                k = np.asarray(k, dtype=np.uint32)
+                if len(k) < n:
+                    raise ValueError("publish_kids32: one key word per topic")
+                s[name][:n] = k[:n]
+                keys.append(s[name][:max(n, 1)])
+            entries = ("topic", "vals") if pick is None else ("topic", "vals", "member")
+            kept = None   # a publish whose picks stand: its route outputs and members
+            for attempt in (0, 1):
+                b, o = s["blob"], s["offs"][: n + 1]
+                out = (s["doff"], s["topic"], s["vals"], s["err"])
+                if local_dest is not None:
+                    out += (s["head"], s["dtopic"], s["dvals"], s["dsubs"])
+                try:
+                    if local_dest is None:
+                        res = ix.route_batch32(b, o, n_dests, out, aggre=aggre), (), None
+                    elif pick is None or kept is not None:
+                        res = ix.dispatch_batch32(b, o, n_dests, local_dest, out, aggre=aggre) + (None,)
+                    else:
+                        res = ix.publish_batch32(b, o, n_dests, local_dest, out, s["member"], keys[0], keys[1], pick[2])
+                    break
+                except _native.TmError as e:
+                    if e.code != _native.TM_ECAP or attempt:
+                        raise
+                total = int(s["doff"][n_dests + 1])
+                if pick is not None and total <= min(len(s[name]) for name in entries):
+                    # a publish whose deliveries alone were short made its picks (the state has moved): its
+                    # route outputs and members are kept, and only the dispatch is fetched again
+                    kept = copied(s["doff"][: n_dests + 2], s["topic"][:total], s["vals"][:total], s["err"][:n]), \
+                        s["member"][:total].copy()
+                # the entry arrays grow from the bucket offsets (the full sizes) ...
+                short = [(entries, total)]
+                if local_dest is not None:   # ... and the delivery arrays from the head
+                    short.append((("dtopic", "dvals", "dsubs"), int(s["head"][1])))
+                for names, need in short:
+                    if need > len(s[names[0]]):
+                        for name in names:
+                            self._route_grow(s, name, need)
+            route, deliveries, member = res
+            deliveries = tuple(a.copy() for a in deliveries)
+            if kept is not None:
+                return kept[0], deliveries, kept[1]
+            return copied(*route), deliveries, None if member is None else member.copy()
+        finally:
+            self._route_put(s)
+
     def route_kids32(self, topics, n_dests: int, aggre: bool = False):
         """route_kids through tm_route_batch32 on pooled pinned buffers: a
         micro-batch is matched and fanned out in place (two launches, no
         staging copy).  One retry on TM_ECAP, sized from the bucket offsets.
         Returns what route_kids returns (copies: the buffers go back to the
         pool)."""
-        self.flush()
-        blob, offs = _native.pack_strings(topics)
-        n, nbytes = len(offs) - 1, int(offs[-1])
-        if nbytes >= 1 << 32:
-            return self._index.route_batch(blob, offs, n_dests, aggre=aggre)
-        s = self._route_set(n, nbytes, n_dests, max(4 * n, 1024))
-        try:
-            s["blob"][:nbytes] = blob[:nbytes]
-            s["offs"][: n + 1] = offs
-            for attempt in (0, 1):
-                out = (s["doff"], s["topic"], s["vals"], s["err"])
-                try:
-                    doff, tidx, kids, err = self._index.route_batch32(s["blob"], s["offs"][: n + 1], n_dests, out,
-                                                                      aggre=aggre)
-                    break
-                except _native.TmError as e:
-                    if e.code != _native.TM_ECAP or attempt:
-                        raise
-                    total = int(s["doff"][n_dests + 1])
-                    for name in ("topic", "vals"):   # the offsets hold the full bucket sizes
-                        self._index.host_free(s.pop(name))
-                        s[name] = self._index.host_array(total + total // 4, np.uint32)
-            return doff.astype(np.uint64), tidx.copy(), kids.copy(), err.copy()
-        finally:
-            self._route_put(s)
+        return self._kids32(topics, n_dests, aggre=aggre)[0]
 
     def dispatch_kids32(self, topics, n_dests: int, local_dest: int, aggre: bool = False):
         """dispatch_kids through tm_dispatch_batch32 on pooled pinned buffers: a
@@ -411,34 +468,7 @@ class Tab:
         synchronisation, no staging copy).  One retry on TM_ECAP, sized from the
         bucket offsets and the head.  Returns what dispatch_kids returns
         (copies: the buffers go back to the pool)."""
-        self.flush()
-        blob, offs = _native.pack_strings(topics)
-        n, nbytes = len(offs) - 1, int(offs[-1])
-        if nbytes >= 1 << 32:
-            return self._index.dispatch_batch(blob, offs, n_dests, local_dest, aggre=aggre)
-        s = self._route_set(n, nbytes, n_dests, max(4 * n, 1024), max(4 * n, 1024))
-        try:
-            s["blob"][:nbytes] = blob[:nbytes]
-            s["offs"][: n + 1] = offs
-            for attempt in (0, 1):
-                out = (s["doff"], s["topic"], s["vals"], s["err"], s["head"], s["dtopic"], s["dvals"], s["dsubs"])
-                try:
-                    (doff, tidx, kids, err), dl = self._index.dispatch_batch32(s["blob"], s["offs"][: n + 1], n_dests,
-                                                                               local_dest, out, aggre=aggre)
-                    break
-                except _native.TmError as e:
-                    if e.code != _native.TM_ECAP or attempt:
-                        raise
-                    total, T = int(s["doff"][n_dests + 1]), int(s["head"][1])
-                    for names, need in ((("topic", "vals"), total), (("dtopic", "dvals", "dsubs"), T)):
-                        if need <= len(s[names[0]]):
-                            continue
-                        for name in names:   # the offsets hold the full bucket sizes, the head the deliveries
-                            self._index.host_free(s.pop(name))
-                            s[name] = self._index.host_array(need + need // 4, np.uint32)
-            return (doff.astype(np.uint64), tidx.copy(), kids.copy(), err.copy()), tuple(a.copy() for a in dl)
-        finally:
-            self._route_put(s)
+        return self._kids32(topics, n_dests, local_dest, aggre)[:2]
 
     def publish_kids32(self, topics, n_dests: int, local_dest: int, key_clientid=None, key_topic=None, seed: int = 0):
         """publish_kids through tm_publish_batch32 on pooled pinned buffers: a
@@ -449,61 +479,7 @@ class Tab:
         state has moved), so only the dispatch is fetched again, through
         tm_dispatch_batch32.  Returns what publish_kids returns (copies: the
         buffers go back to the pool)."""
-        self.flush()
-        blob, offs = _native.pack_strings(topics)
-        n, nbytes = len(offs) - 1, int(offs[-1])
-        if nbytes >= 1 << 32:
-            return self._index.publish_batch(blob, offs, n_dests, local_dest, key_clientid=key_clientid,
-                                             key_topic=key_topic, seed=seed)
-        s = self._route_set(n, nbytes, n_dests, max(4 * n, 1024), max(4 * n, 1024))
-        try:
-            want = {"member": len(s["topic"]), "kc": max(n, 1), "kt": max(n, 1)}
-            for name, need in want.items():
-                if name not in s or len(s[name]) < need:
-                    if name in s:
-                        self._index.host_free(s.pop(name))
-                    s[name] = self._index.host_array(need + need // 4, np.uint32)
-            s["blob"][:nbytes] = blob[:nbytes]
-            s["offs"][: n + 1] = offs
-            keys = []
-            for name, k in (("kc", key_clientid), ("kt", key_topic)):
-                if k is None:
-                    keys.append(None)
-                    continue
-                k = np.asarray(k, dtype=np.uint32)
-                if len(k) < n:
-                    raise ValueError("publish_kids32: one key word per topic")
-                s[name][:n] = k[:n]
-                keys.append(s[name][:max(n, 1)])
-            for attempt in (0, 1):
-                out = (s["doff"], s["topic"], s["vals"], s["err"], s["head"], s["dtopic"], s["dvals"], s["dsubs"])
-                try:
-                    (doff, tidx, kids, err), dl, member = self._index.publish_batch32(
-                        s["blob"], s["offs"][: n + 1], n_dests, local_dest, out, s["member"], keys[0], keys[1], seed)
-                    break
-                except _native.TmError as e:
-                    if e.code != _native.TM_ECAP or attempt:
-                        raise
-                    total, T = int(s["doff"][n_dests + 1]), int(s["head"][1])
-                    picked = total <= min(len(s["topic"]), len(s["vals"]), len(s["member"]))
-                    if picked:   # the deliveries alone were short: the route outputs and the picks stand
-                        route = (s["doff"][: n_dests + 2].astype(np.uint64), s["topic"][:total].copy(),
-                                 s["vals"][:total].copy(), s["err"][:n].copy())
-                        member = s["member"][:total].copy()
-                    for names, need in ((("topic", "vals", "member"), total), (("dtopic", "dvals", "dsubs"), T)):
-                        if need <= len(s[names[0]]):
-                            continue
-                        for name in names:   # the offsets hold the full bucket sizes, the head the deliveries
-                            self._index.host_free(s.pop(name))
-                            s[name] = self._index.host_array(need + need // 4, np.uint32)
-                    if picked:
-                        out = (s["doff"], s["topic"], s["vals"], s["err"], s["head"], s["dtopic"], s["dvals"], s["dsubs"])
-                        _, dl = self._index.dispatch_batch32(s["blob"], s["offs"][: n + 1], n_dests, local_dest, out,
-                                                             aggre=True)
-                        return route, tuple(a.copy() for a in dl), member
-            return (doff.astype(np.uint64), tidx.copy(), kids.copy(), err.copy()), tuple(a.copy() for a in dl), member.copy()
-        finally:
-            self._route_put(s)
+        return self._kids32(topics, n_dests, local_dest, True, (key_clientid, key_topic, seed))
 
     def read_begin(self) -> int:
         return self._index.read_begin()

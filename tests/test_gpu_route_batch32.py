@@ -11,6 +11,11 @@ FO1_ENTRIES entries, 256 buckets) or the grid kernels / the staged path.
 k_fo_one gives each of its 16 waves a chunk of ceil(E / 16) entries rounded up
 to 64, so E = 1024 fills every wave's first step exactly and 1025 takes a
 second; E = FO1_ENTRIES fills all 16 steps of all waves.
+
+Last, one table of refusals over the six entry points of the route family
+(tm_route_batch_ex, tm_dispatch_batch, tm_publish_batch and their 32-bit
+forms): TM_EINVAL, no output written, no leg counted, no state word moved, and
+tm_last_error names the entry point that was called.
 """
 import ctypes as C
 import subprocess
@@ -565,3 +570,91 @@ def test_nif_core_routes_on_the_real_library(routed, nif, in_flags):
         assert tv[b.value:e.value] == vals[int(hit[i]):int(hit[i + 1])].tolist()
     nif.tmn_give(pool, s)
     nif.shim_pool_free(pool)
+
+
+# ---- 11. refusals: the six entry points of the route family, one table
+
+R_N, R_DESTS, R_CAP, R_STATE = 1, 2, 8, 5
+R_COUNTERS = (ONE, GRID, _native.TM_DEBUG_DISPATCH_ONE, _native.TM_DEBUG_DISPATCH_GRID,
+              _native.TM_DEBUG_PUBLISH_ONE, _native.TM_DEBUG_PUBLISH_GRID)
+R_ENTRIES = ("tm_route_batch_ex", "tm_route_batch32_ex", "tm_dispatch_batch", "tm_dispatch_batch32",
+             "tm_publish_batch", "tm_publish_batch32")
+ALL, WIDE32, DISPATCHING = R_ENTRIES, R_ENTRIES[1::2], R_ENTRIES[2:]
+# row -> (the argument it spoils, its value, the entry points that have it)
+R_ROWS = {
+    "unknown-flag": ("flags", 0x80 | _native.TM_ROUTE_AGGRE, ALL),
+    "n_dests-0": ("n_dests", 0, ALL),
+    "n_dests-65537": ("n_dests", 65537, ALL),
+    "local_dest-n_dests": ("local", R_DESTS, DISPATCHING),
+    "null-dest_offsets": ("doff", None, ALL),
+    "null-err": ("err", None, WIDE32),
+    "null-topic": ("topic", None, ALL),
+    "null-head": ("head", None, DISPATCHING),
+    "null-dtopic": ("dt", None, DISPATCHING),
+    "null-dvalue": ("dv", None, DISPATCHING),
+    "null-dsub": ("ds", None, DISPATCHING),
+    "misaligned-head": ("head", "+4", WIDE32[1:]),
+    "no-aggre": ("flags", 0, R_ENTRIES[4:]),
+    "null-member": ("member", None, R_ENTRIES[4:]),
+}
+R_CASES = [(entry, row) for entry in R_ENTRIES for row in R_ROWS if entry in R_ROWS[row][2]]
+HEAD_CANARY = 0xABCDEF0123456789
+
+
+@pytest.fixture(scope="module")
+def refusing(gpu):
+    """one filter, routed, with a subscriber and a shared slot whose state word is R_STATE; every
+    buffer of every call pinned (an eligible in-place batch, were it not refused)"""
+    ix = _native.Index()
+    ix.set_route_filters([0], [0])
+    ix.set_subscribers([0], [[7, 8]])
+    ix.set_share_members([0], [[3, 4]], [0], [_native.TM_SHARE_ROUND_ROBIN])
+    ix.share_state_set([0], [R_STATE])
+    ix.set_share_slots([0], [0])
+    _insert(ix, [b"a/b"], [0], [0])
+    u32, u64 = np.uint32, np.uint64
+    a = {"blob": ix.host_array(64, np.uint8), "offs32": ix.host_array(R_N + 1, u32), "offs64": ix.host_array(R_N + 1, u64),
+         "doff32": ix.host_array(R_DESTS + 2 + TAIL, u32), "doff64": ix.host_array(R_DESTS + 2 + TAIL, u64),
+         "err": ix.host_array(R_N + TAIL, np.uint8), "head": ix.host_array(3, u64),
+         "kc": ix.host_array(R_N, u32), "kt": ix.host_array(R_N, u32)}
+    for name in ("topic", "vals", "member", "dt", "dv", "ds"):
+        a[name] = ix.host_array(R_CAP + TAIL, u32)
+    a["blob"][:3] = np.frombuffer(b"a/b", np.uint8)
+    a["offs32"][:], a["offs64"][:] = (0, 3), (0, 3)
+    yield ix, a
+    ix.close()
+
+
+@pytest.mark.parametrize("entry,row", R_CASES, ids=[f"{e}-{r}" for e, r in R_CASES])
+def test_refusals(refusing, entry, row):
+    """a refused call returns TM_EINVAL, writes no output, counts on no leg, moves no state word,
+    and says in tm_last_error which entry point was called"""
+    ix, a = refusing
+    w = "32" if "32" in entry else "64"
+    outs = [a["doff" + w], a["err"], a["head"]] + [a[k] for k in ("topic", "vals", "member", "dt", "dv", "ds")]
+    for o in outs:
+        o[:] = HEAD_CANARY if o.dtype == np.uint64 else ERRC if o.dtype == np.uint8 else CANARY
+    arg = {k: P(a[k]) for k in ("blob", "err", "head", "topic", "vals", "member", "dt", "dv", "ds", "kc", "kt")}
+    arg.update(offs=P(a["offs" + w]), doff=P(a["doff" + w]), n_dests=R_DESTS, local=0, flags=_native.TM_ROUTE_AGGRE)
+    what, value, _ = R_ROWS[row]
+    arg[what] = C.c_void_p(a["head"].ctypes.data + 4) if value == "+4" else value
+    head = [arg["n_dests"]]
+    tail = [arg["doff"], arg["topic"], arg["vals"], R_CAP]
+    if "route" in entry:
+        args = head + tail + [arg["err"], arg["flags"]]
+    else:
+        args = head + [arg["local"], arg["flags"]] + tail + [arg["head"], arg["dt"], arg["dv"], arg["ds"], R_CAP]
+        if "publish" in entry:
+            args += [arg["kc"], arg["kt"], 1, arg["member"]]
+        args.append(arg["err"])
+    before = [ix.debug_get(k) for k in R_COUNTERS]
+    rc = getattr(ix._lib, entry)(ix._h, R_N, arg["blob"], arg["offs"], *args)
+    said = ix._lib.tm_last_error(ix._h)
+    assert rc == _native.TM_EINVAL
+    for o in outs:
+        assert (o == (HEAD_CANARY if o.dtype == np.uint64 else ERRC if o.dtype == np.uint8 else CANARY)).all(), \
+            "a refused call wrote an output"
+    assert [ix.debug_get(k) for k in R_COUNTERS] == before, "a refused call counted on a leg"
+    if "publish" in entry:
+        assert ix.share_state_get([0]).tolist() == [R_STATE], "a refused call moved the state word"
+    assert entry.encode() in said, f"tm_last_error names another function: {said!r}"
