@@ -31,7 +31,8 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_fanout_dev_pairs", "tm_route_batch32", "tm_set_route_filters", "tm_aggre_dev", "tm_route_batch_ex",
            "tm_route_batch32_ex", "tm_set_subscribers", "tm_dispatch_dev", "tm_dispatch_batch",
            "tm_dispatch_batch32", "tm_set_share_slots", "tm_set_share_members", "tm_share_state_set",
-           "tm_share_state_get", "tm_share_pick_dev", "tm_publish_batch", "tm_publish_batch32")
+           "tm_share_state_get", "tm_share_pick_dev", "tm_publish_batch", "tm_publish_batch32",
+           "tm_group_subs_dev", "tm_deliver_batch")
 TM_ALLOC_VRAM = 1
 TM_ROUTE_AGGRE = 1          # tm_route_batch_ex / tm_route_batch32_ex: aggre/1 applied to the buckets
 NO_FILTER = 0xFFFFFFFF      # tm_set_route_filters: no filter known (equal to nothing)
@@ -60,6 +61,9 @@ TM_DEBUG_DISPATCH_ONE, TM_DEBUG_DISPATCH_GRID = 32, 33   # (get only) dispatch_b
 TM_DEBUG_DP1_MAX = 34   # deliveries the one-launch dispatch kernel expands itself (clamped to DP1_DELIVERIES)
 DP1_DELIVERIES = 32768
 TM_DEBUG_PUBLISH_ONE, TM_DEBUG_PUBLISH_GRID = 35, 36   # (get only) publish_batch32 calls per picking leg
+# (get only) keys a block of group_subs_dev ranks per pass at a time; the digit passes its calls ran / skipped
+TM_DEBUG_GROUP_TILE, TM_DEBUG_GROUP_PASSES_RUN, TM_DEBUG_GROUP_PASSES_SKIPPED = 37, 38, 39
+TM_DEBUG_GROUP_GRID = 40    # (get only) the blocks of group_subs_dev's fixed grid
 MAX_DESTS = 65536           # tm_fanout_dev / tm_route_batch: n_dests is 1 .. MAX_DESTS
 
 
@@ -161,6 +165,9 @@ def load_library(path: Path | None = None):
                                    vp]),
         "tm_publish_batch32": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u32, vp,
                                      vp]),
+        "tm_group_subs_dev": (i32, [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+        "tm_deliver_batch": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, u64,
+                                   vp]),
         "tm_debug_set": (i32, [vp, u32, u64]),
         "tm_debug_get": (i32, [vp, u32, C.POINTER(u64)]),
     }
@@ -586,6 +593,29 @@ class Index:
                                                    TM_ROUTE_AGGRE if aggre else 0)
         return route, deliveries
 
+    def group_subs_dev(self, d_head: int, d_topic: int, d_value: int, d_sub: int, cap: int, d_out_ghead: int,
+                       d_out_gsub: int, d_out_goff: int, gcap: int, d_out_topic: int, d_out_value: int, d_out_sub: int,
+                       d_out_perm: int | None = None, stream: int | None = None):
+        """tm_group_subs_dev on device pointers: the first min(d_head[1], cap)
+        deliveries a dispatch wrote, stably sorted by subscriber into d_out_topic
+        / d_out_value / d_out_sub (d_out_perm: the input positions); d_out_ghead
+        u64[2] = (groups G, deliveries W), the first min(G, gcap) subscribers in
+        d_out_gsub, their offsets and the last one's end in d_out_goff
+        u64[gcap + 1]."""
+        self._check(self._lib.tm_group_subs_dev(self._h, d_head, d_topic, d_value, d_sub, cap, d_out_ghead, d_out_gsub,
+                                                d_out_goff, gcap, d_out_topic, d_out_value, d_out_sub, d_out_perm,
+                                                stream))
+
+    def deliver_batch(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, local_dest: int, cap: int | None = None,
+                      dcap: int | None = None, gcap: int | None = None, aggre: bool = False):
+        """tm_deliver_batch -> (route_batch's tuple, (dtopic, dvalue, dsub) u32[T]
+        GROUPED by subscriber -- ascending ids, each subscriber's deliveries in
+        dispatch_batch's order -- and (gsub u32[G], goff u64[G + 1]): subscriber
+        gsub[g] owns the deliveries [goff[g], goff[g + 1]).  A cap that proves
+        too small is retried, sized from what the call returned."""
+        return self._deliver_loop(blob, offs, n_dests, local_dest, cap, dcap, TM_ROUTE_AGGRE if aggre else 0,
+                                  1024 if gcap is None else gcap)
+
     def _dispatch_loop(self, blob, offs, n_dests, local_dest, cap, dcap, flags, pick=None):
         """dispatch_batch's and publish_batch's loop: allocate, call, grow what
         was short from what the call returned.  pick: (key_clientid, key_topic,
@@ -624,6 +654,35 @@ class Index:
             return (doff, topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T]), \
                 None if member is None else member[:total]
         raise TmError(TM_ECAP, f"{'dispatch_batch' if pick is None else 'publish_batch'}: the totals kept growing")
+
+    def _deliver_loop(self, blob, offs, n_dests, local_dest, cap, dcap, flags, gcap):
+        """_dispatch_loop's shape for tm_deliver_batch, with gcap as a third size
+        -> (route tuple, grouped deliveries, (gsub, goff))."""
+        n = len(offs) - 1
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        doff = np.zeros(n_dests + 2, dtype=np.uint64)
+        head, ghead = np.zeros(2, dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+        err = np.zeros(max(n, 1), dtype=np.uint8)
+        if cap is None:
+            cap = max(4 * n, 1024)
+        if dcap is None:
+            dcap = max(4 * n, 1024)
+        for _ in range(4):
+            topic, vals = (np.empty(max(cap, 1), dtype=np.uint32) for _ in range(2))
+            dt, dv, ds = (np.empty(max(dcap, 1), dtype=np.uint32) for _ in range(3))
+            gsub, goff = np.empty(max(gcap, 1), dtype=np.uint32), np.zeros(gcap + 1, dtype=np.uint64)
+            rc = self._lib.tm_deliver_batch(self._h, n, _ptr(blob), _ptr(offs), n_dests, local_dest, flags, _ptr(doff),
+                                            _ptr(topic), _ptr(vals), cap, _ptr(head), _ptr(dt), _ptr(dv), _ptr(ds), dcap,
+                                            _ptr(ghead), _ptr(gsub), _ptr(goff), gcap, _ptr(err))
+            total, T, G = int(doff[-1]), int(head[1]), int(ghead[0])
+            if rc == TM_ECAP and (total > cap or T > dcap or G > gcap):
+                # (G counts the groups of the deliveries that fitted: at most T of them in the end)
+                cap, dcap, gcap = max(cap, total), max(dcap, T), max(gcap, G if T <= dcap else min(T, max(4 * G, 1024)))
+                continue
+            self._check(rc)
+            return (doff, topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T]), (gsub[:G], goff[:G + 1])
+        raise TmError(TM_ECAP, "deliver_batch: the totals kept growing")
 
     def dispatch_batch32(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, local_dest: int, out,
                          cap: int | None = None, dcap: int | None = None, aggre: bool = False):

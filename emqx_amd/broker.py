@@ -60,7 +60,8 @@ class Broker:
     def __init__(self, router, node=None, dispatch=None, forward=None, share_dispatch=None,
                  max_batch: int = 4096, max_wait_ms: float = 0.2, start: bool = False,
                  aggre_on_device: bool = False, dispatch_on_device: bool = False, deliver=None,
-                 share_on_device: bool = False, share_send=None, share_keys=None, share_seed: int = 0):
+                 share_on_device: bool = False, share_send=None, share_keys=None, share_seed: int = 0,
+                 deliver_grouped: bool = False, deliver_batch=None):
         """aggre_on_device: publish_batch_by_dest asks the router for buckets
         the device has already applied aggre/1 to (TM_ROUTE_AGGRE).
         dispatch_on_device: publish_batch_by_dest asks the router for the local
@@ -73,7 +74,16 @@ class Broker:
         To, pid)], each handed to share_send(pid, To, message) -> "ok" or an
         error reason, and share_dispatch is not called.  share_keys(message) ->
         (phash2(ClientId), phash2(Topic)) for the two hash strategies (default:
-        zeros); share_seed: the seed of the batch's random picks."""
+        zeros); share_seed: the seed of the batch's random picks.
+        deliver_grouped: publish_batch_by_dest asks the router for the local
+        node's deliveries grouped by subscriber as well
+        (Router.match_routes_deliver) and calls deliver_batch(SubPid, [(To,
+        message)]) once per subscriber per batch, the list in publish order --
+        what the connection process gathers from its mailbox
+        (emqx_connection.erl:611-612) -- in place of one deliver per delivery.
+        What publish_batch_by_dest returns is unchanged."""
+        self.deliver_grouped = deliver_grouped
+        self.deliver_batch = deliver_batch or (lambda sub, items: None)
         self.share_on_device = share_on_device
         self.share_send = share_send or (lambda pid, to, msg: "ok")
         self.share_keys = share_keys or (lambda msg: (0, 0))
@@ -152,12 +162,15 @@ class Broker:
         if not msgs:
             return {}, {}
         on_dev = self.aggre_on_device
-        deliveries = picks = keys = None
+        deliveries = picks = keys = by_sub = None
         if self.share_on_device:
             keys = [self.share_keys(m) for m in msgs]
             by_dest, deliveries, picks = self.router.match_routes_publish(
                 [m.topic for m in msgs], [k[0] for k in keys], [k[1] for k in keys], seed=self.share_seed, errors="return")
             on_dev = True
+        elif self.deliver_grouped:
+            by_dest, deliveries, by_sub = self.router.match_routes_deliver([m.topic for m in msgs], errors="return",
+                                                                           aggre=on_dev)
         elif self.dispatch_on_device:
             by_dest, deliveries = self.router.match_routes_dispatch([m.topic for m in msgs], errors="return",
                                                                     aggre=on_dev)
@@ -190,8 +203,12 @@ class Broker:
             plan.sort(key=lambda e: e[0])   # several classes in one plan (every ("external", X)): message order again
             out[dest] = [(i, to) + (self._route2((to, dest), msgs[i])[2],) for i, to in plan]
         if deliveries:
-            for i, to, sub in deliveries:
-                self.deliver(sub, to, msgs[i])
+            if by_sub is not None:
+                for sub, items in by_sub.items():
+                    self.deliver_batch(sub, [(to, msgs[i]) for i, to in items])
+            else:
+                for i, to, sub in deliveries:
+                    self.deliver(sub, to, msgs[i])
             out[self.node] = list(deliveries)
         for group, rows in (picks or {}).items():
             out[group] = [(i, to, self._share_deliver(group, to, i, pid, msgs[i], keys[i])) for i, to, pid in rows]

@@ -30,6 +30,7 @@ FANOUT_SOURCE = "tm_fanout.hip"   # the route fan-out's kernels (not among the m
 AGGRE_SOURCE = "tm_aggre.hip"     # aggre/1 on the fan-out's output (likewise)
 DISPATCH_SOURCE = "tm_dispatch.hip"   # local dispatch: route hits expanded to subscribers (likewise)
 SHARE_SOURCE = "tm_share.hip"         # shared-subscription pick: one member per (message, group) (likewise)
+GROUP_SOURCE = "tm_group.hip"         # deliveries grouped by subscriber: a stable radix sort (likewise)
 
 
 def source_hash() -> str:
@@ -60,7 +61,7 @@ def _run(cmd, cwd=None):
 
 def build_tmatch(force: bool = False) -> Path:
     srcs = [CSRC / "tm_host.cpp", CSRC / "tm_kernels.hip", CSRC / FANOUT_SOURCE, CSRC / AGGRE_SOURCE,
-            CSRC / DISPATCH_SOURCE, CSRC / SHARE_SOURCE]
+            CSRC / DISPATCH_SOURCE, CSRC / SHARE_SOURCE, CSRC / GROUP_SOURCE]
     deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", CSRC / "tm_subs.h", ROOT / "include" / "tmatch.h"]
     if force or _stale(LIB_TMATCH, deps):
         tmp = LIB_TMATCH.with_suffix(".so.tmp")
@@ -81,7 +82,7 @@ def build_variant(name: str, kernel_src: str | None = None, force: bool = False,
     out.parent.mkdir(exist_ok=True)
     kern = Path(kernel_src) if kernel_src else CSRC / "tm_kernels.hip"
     srcs = [Path(host_src) if host_src else CSRC / "tm_host.cpp", kern, CSRC / FANOUT_SOURCE, CSRC / AGGRE_SOURCE,
-            CSRC / DISPATCH_SOURCE, CSRC / SHARE_SOURCE]
+            CSRC / DISPATCH_SOURCE, CSRC / SHARE_SOURCE, CSRC / GROUP_SOURCE]
     deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", CSRC / "tm_subs.h", ROOT / "include" / "tmatch.h"]
     if force or _stale(out, deps):
         _run(["hipcc", "-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-shared", "-Wall",

@@ -231,6 +231,11 @@ struct FanoutScratch {
     // FO_GRID ranked / with-slot / picked block counts (3 * FO_GRID + 1 words)
     uint32_t *sh_key, *sh_s[2], *sh_q[2], *sh_cnt;
     uint64_t sh_cap;
+    // grouping by subscriber (launch_group_subs): the fixed words (GS_FIX_WORDS: the counters, the plan,
+    // the histograms) and, per delivery below gs_cap, the two (key, position) pair arrays of the passes'
+    // ping-pong (gs_k[b], gs_p[b]: 16 bytes in all)
+    uint32_t *gs_fix, *gs_k[2], *gs_p[2];
+    uint64_t gs_cap;
 };
 constexpr uint32_t FP_TILES = 1024;
 #if defined(__HIPCC__)
@@ -427,6 +432,33 @@ hipError_t launch_share_one(const uint32_t *status_in, const uint32_t *fail, con
                             const uint32_t *slot_of, uint64_t slot_of_len, const uint32_t *slot_rec, uint64_t n_slots,
                             const uint32_t *pool, uint64_t pool_len, uint32_t *state, uint32_t *out_member, uint32_t *status,
                             hipStream_t s);
+// Deliveries grouped by subscriber (tm_group.hip; include/tmatch.h
+// tm_group_subs_dev has the definition): the first W = min(head[1], cap)
+// deliveries (topic, value, sub) a dispatch wrote, stably sorted by sub into
+// out_topic / out_value / out_sub (out_perm, when given: the input positions),
+// the G distinct subscribers and their G + 1 offsets -- the first min(G, gcap)
+// of them -- into out_gsub / out_goff, ghead = [G, W].  head, ghead and
+// out_goff must be 8-byte aligned.  Needs fs.gs_fix and fs.gs_cap >= min(cap,
+// 2^32 - 1).  A fixed grid of GS_GRID blocks of GS_BLOCK threads, a block
+// ranking GS_TILE keys at a time.
+constexpr uint32_t GS_GRID = 1024;
+constexpr uint32_t GS_BLOCK = 256;
+constexpr uint32_t GS_TILE = 1024;
+constexpr uint32_t GS_BINS = 256;                       // 8-bit digits, four passes at most
+constexpr uint32_t GS_PASSES = 4;
+// fs.gs_fix, in u32 words: the passes run / skipped so far (two u64, zero when allocated), the plan of
+// the call in flight (GS_SKIP + p: pass p is the identity; GS_SRC + p: where pass p reads, GS_SRC + 4:
+// where the sorted pairs are -- GS_IN the caller's array with positions 0, 1, .., else pair array 0 / 1),
+// the head counts of the GS_GRID * 4 waves, the four digits' bin totals (zero between calls), the
+// bins' first positions per digit, and the (bin, block) histogram of a pass
+enum { GS_STAT = 0, GS_SKIP = 4, GS_SRC = 8, GS_GCNT = 16, GS_TOT = GS_GCNT + GS_GRID * 4,
+       GS_BASE = GS_TOT + GS_PASSES * GS_BINS, GS_TAB = GS_BASE + GS_PASSES * GS_BINS,
+       GS_FIX_WORDS = GS_TAB + GS_BINS * GS_GRID, GS_ZERO_WORDS = GS_BASE /* zero when allocated */ };
+enum : uint32_t { GS_IN = 2 };
+hipError_t launch_group_subs(const FanoutScratch &fs, const uint64_t *head, const uint32_t *in_topic,
+                             const uint32_t *in_value, const uint32_t *in_sub, uint64_t cap, uint64_t *ghead,
+                             uint32_t *out_gsub, uint64_t *out_goff, uint64_t gcap, uint32_t *out_topic,
+                             uint32_t *out_value, uint32_t *out_sub, uint32_t *out_perm, hipStream_t s);
 // delta upload: run i copies runs[i].n u32 words from data + runs[i].src to
 // word (dst & PATCH_OFF) of table (dst >> 48), whose device address on the
 // replica being patched is bases.b[table] (the same runs patch every replica)

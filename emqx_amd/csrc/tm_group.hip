@@ -1,0 +1,412 @@
+// tm_group.hip -- a batch's local deliveries regrouped by subscriber, for gfx950.
+//
+// do_dispatch2/3 sends SubPid ! {deliver, To, Msg} once per delivery
+// (apps/emqx/src/emqx_broker.erl:745-752), and the first thing a connection
+// process does is gather its mailbox's delivers back into one list
+// (emqx_connection.erl:611-612: [Deliver | emqx_utils:drain_deliver(ActiveN)]).
+// A micro-batched broker hands a subscriber its list at once: the W deliveries
+// (topic, value, subscriber) a dispatch wrote in message order, stably sorted
+// by subscriber, with the G distinct subscribers and their offsets.
+//
+// The key is an interned pid, any u32, so the fan-out's buckets do not carry
+// over: a stable LSD radix sort of (key, position) pairs, 8-bit digits, over a
+// fixed grid of GS_GRID blocks of GS_BLOCK threads; block k owns the positions
+// [k * chunk, (k + 1) * chunk) of [0, W), chunk = ceil(W / GS_GRID) rounded up
+// to GS_TILE.  W = min(head[1], cap) is read on the device by every kernel.
+// No block waits for another: every step is a launch of its own.
+//   k_gs_pre      the block's histogram of all four digits (LDS, one add per
+//                 run of equal digits in a wave), its non-zero counts added
+//                 to the digits' bin totals tot[digit][bin] (device atomics:
+//                 integer sums, the same whatever the order; dense ids touch
+//                 few bins);
+//   k_gs_plan     one block: reads the totals and zeroes them for the next
+//                 call.  A digit whose W keys all fall in one bin is the
+//                 identity: skip[p]; src[p] = where pass p reads (the caller's
+//                 array with the positions 0, 1, .. at first, then the two
+//                 pair arrays in turn), src[4] = where the sorted pairs end
+//                 up; base[p][bin] = the exclusive scan of digit p's totals
+//                 (a permutation does not change them: known before any pass
+//                 runs).  A dense pid space below 2^16 costs two passes.
+//   per pass p that is not skipped (the three kernels of a skipped pass read
+//   skip[p] and return; a block whose chunk is empty returns at once):
+//   k_gs_hist     the block's histogram of digit p -> tab[bin][block];
+//   k_gs_scan     block b: the exclusive scan of bin b's row over the blocks
+//                 that own keys, from base[p][b];
+//   k_gs_scatter  per tile of GS_TILE keys: a wave finds each key's lanes with
+//                 the same digit by 8 ballots (rank inside the wave = the set
+//                 lanes below it), the run's first lane stores the run length
+//                 in cnt[64-key row][bin]; thread b scans bin b down the 16
+//                 rows and carries the block's running offset of its bin;
+//                 every key goes to tab[bin][block] + keys of the bin in
+//                 earlier tiles + in earlier rows + its rank: stable.
+//   k_gs_heads    wave w of block k counts the group heads (a key that
+//                 differs from its predecessor) of its quarter of the chunk;
+//   k_gs_gscan    one block: the exclusive scan of the GS_GRID * 4 counts;
+//                 ghead = [G, W], out_goff[G] = W when G <= gcap;
+//   k_gs_emit     the same wave numbers its heads from its base (ballot,
+//                 popcount) and writes out_gsub / out_goff below gcap, and
+//                 gathers (topic, value) through the position: the payload.
+// Bytes per delivery: 4 read (pre), per pass run 4 read (hist) + 8 read + 8
+// written (scatter), 8 read (heads: the key and its predecessor), 8 read + 8
+// gathered + 12 (16 with out_perm) written (emit).  Scratch: 16 bytes per
+// delivery below cap and GS_FIX_WORDS words (1.03 MiB).
+#include <hip/hip_runtime.h>
+
+#include "tm_dev.h"
+
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "tm_group.hip: wave64 ballots and the LDS budget are written for gfx950 only"
+#endif
+
+namespace tmx {
+
+namespace {
+
+constexpr uint32_t GS_WAVES = GS_BLOCK / 64;
+constexpr uint32_t GS_ROWS = GS_TILE / 64;        // 64-key rows of a tile
+constexpr uint32_t GS_PER = GS_ROWS / GS_WAVES;   // rows (keys) a wave (a thread) takes per tile
+static_assert(GS_BLOCK == GS_BINS, "thread b of a block owns bin b");
+static_assert(GS_TILE % GS_BLOCK == 0 && GS_ROWS % GS_WAVES == 0, "a tile is whole rows per wave");
+static_assert(GS_GRID == 1024 && GS_WAVES == 4 && GS_PASSES * GS_BINS == 1024, "k_gs_gscan, k_gs_plan: 1024 threads");
+static_assert(GS_GRID == GS_BLOCK * 4 && GS_TAB % 4 == 0, "k_gs_scan: one aligned quad of a row per thread");
+
+struct GsBufs {
+    uint32_t *fix, *k[2], *p[2];
+};
+
+__device__ __forceinline__ uint64_t gs_w(const uint64_t *head, uint64_t cap) {
+    const uint64_t T = head[1];
+    return T < cap ? T : cap;
+}
+
+// the positions block `blk` owns: [c0, c1) of [0, W); q: a wave's quarter of the chunk
+__device__ __forceinline__ void gs_chunk(uint64_t W, uint32_t blk, uint64_t &c0, uint64_t &c1, uint64_t &q) {
+    const uint64_t chunk = ((W + GS_GRID - 1) / GS_GRID + GS_TILE - 1) / GS_TILE * GS_TILE;
+    q = chunk / GS_WAVES;
+    c0 = (uint64_t)blk * chunk;
+    if (c0 > W) c0 = W;
+    c1 = c0 + chunk < W ? c0 + chunk : W;
+}
+
+// the keys and positions pass-source `src` names (positions null: 0, 1, ..)
+__device__ __forceinline__ void gs_source(const GsBufs &b, const uint32_t *in_sub, uint32_t src, const uint32_t *&k,
+                                          const uint32_t *&p) {
+    k = src == GS_IN ? in_sub : b.k[src & 1];
+    p = src == GS_IN ? nullptr : b.p[src & 1];
+}
+
+// the lanes of the wave (among those with ok) whose 8-bit digit equals this lane's
+__device__ __forceinline__ uint64_t gs_match(uint32_t d, bool ok) {
+    uint64_t m = __ballot(ok);
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+        const bool bit = (d >> b) & 1u;
+        const uint64_t bal = __ballot(bit);
+        m &= bit ? bal : ~bal;
+    }
+    return m;
+}
+
+__device__ __forceinline__ uint32_t gs_below(uint64_t m, uint32_t lane) {
+    return (uint32_t)__popcll(m & ((1ull << lane) - 1));
+}
+
+__device__ __forceinline__ uint32_t gs_incl_scan32(uint32_t x, uint32_t lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d, 64);
+        if (lane >= (uint32_t)d) x += y;
+    }
+    return x;
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void k_gs_pre(const uint64_t *head, uint64_t cap, const uint32_t *in_sub,
+                                                     uint32_t *fix) {
+    __shared__ uint32_t s_h[GS_PASSES * GS_BINS];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint64_t c0, c1, q;
+    gs_chunk(gs_w(head, cap), blockIdx.x, c0, c1, q);
+    if (c0 >= c1) return;   // (block-uniform)
+#pragma unroll
+    for (uint32_t p = 0; p < GS_PASSES; p++) s_h[p * GS_BINS + tid] = 0;
+    __syncthreads();
+    for (uint64_t i0 = c0 + wv * 64; i0 < c1; i0 += GS_BLOCK) {   // (wave-uniform)
+        const uint64_t i = i0 + lane;
+        const bool ok = i < c1;
+        const uint32_t key = ok ? in_sub[i] : 0u;
+#pragma unroll
+        for (uint32_t p = 0; p < GS_PASSES; p++) {
+            const uint32_t d = (key >> (8 * p)) & 255u;
+            const uint64_t m = gs_match(d, ok);
+            if (ok && gs_below(m, lane) == 0) atomicAdd(&s_h[p * GS_BINS + d], (uint32_t)__popcll(m));
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t p = 0; p < GS_PASSES; p++) {
+        const uint32_t c = s_h[p * GS_BINS + tid];
+        if (c) atomicAdd(&fix[GS_TOT + p * GS_BINS + tid], c);
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_gs_plan(const uint64_t *head, uint64_t cap, uint32_t *fix) {
+    __shared__ uint32_t s_one[GS_PASSES];
+    __shared__ uint32_t s_w[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t W = gs_w(head, cap);
+    if (tid < GS_PASSES) s_one[tid] = 0;
+    __syncthreads();
+    const uint32_t tot = fix[GS_TOT + tid];   // (digit tid / 256, bin tid % 256: four waves a digit)
+    fix[GS_TOT + tid] = 0;                    // (the next call on this stream adds to zeroes)
+    if (tot == W) s_one[tid / GS_BINS] = 1;   // (W == 0: every bin)
+    const uint32_t inc = gs_incl_scan32(tot, lane);
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    uint32_t base = inc - tot;
+    for (uint32_t w = wv & ~3u; w < wv; w++) base += s_w[w];
+    fix[GS_BASE + tid] = base;
+    if (tid == 0) {
+        uint32_t src = GS_IN, run = 0;
+        for (uint32_t p = 0; p < GS_PASSES; p++) {
+            const uint32_t skip = s_one[p];
+            fix[GS_SKIP + p] = skip;
+            fix[GS_SRC + p] = src;
+            if (!skip) {
+                src = src == 0 ? 1u : 0u;   // (GS_IN or pair array 1 -> 0; 0 -> 1)
+                run++;
+            }
+        }
+        fix[GS_SRC + GS_PASSES] = src;
+        uint64_t *stat = reinterpret_cast<uint64_t *>(fix + GS_STAT);
+        stat[0] += run;
+        stat[1] += GS_PASSES - run;
+    }
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void k_gs_hist(const uint64_t *head, uint64_t cap, const uint32_t *in_sub,
+                                                      GsBufs bufs, uint32_t pass) {
+    __shared__ uint32_t s_h[GS_BINS];
+    if (bufs.fix[GS_SKIP + pass]) return;   // (uniform over the grid)
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint64_t c0, c1, q;
+    gs_chunk(gs_w(head, cap), blockIdx.x, c0, c1, q);
+    if (c0 >= c1) return;   // (block-uniform; k_gs_scan reads the columns of blocks that own keys only)
+    const uint32_t *kin, *pin;
+    gs_source(bufs, in_sub, bufs.fix[GS_SRC + pass], kin, pin);
+    s_h[tid] = 0;
+    __syncthreads();
+    for (uint64_t i0 = c0 + wv * 64; i0 < c1; i0 += GS_BLOCK) {
+        const uint64_t i = i0 + lane;
+        const bool ok = i < c1;
+        const uint32_t d = ((ok ? kin[i] : 0u) >> (8 * pass)) & 255u;
+        const uint64_t m = gs_match(d, ok);
+        if (ok && gs_below(m, lane) == 0) atomicAdd(&s_h[d], (uint32_t)__popcll(m));
+    }
+    __syncthreads();
+    bufs.fix[GS_TAB + tid * GS_GRID + blockIdx.x] = s_h[tid];   // (every word, every pass run: nothing stale)
+}
+
+// block b: bin b's row tab[b][0 .. nb) -> its exclusive scan in place from base[pass][b], nb = the
+// blocks that own keys (the sums stay below 2^32: W does)
+__global__ __launch_bounds__(GS_BLOCK) void k_gs_scan(const uint64_t *head, uint64_t cap, uint32_t *fix, uint32_t pass) {
+    __shared__ uint32_t s_w[GS_WAVES];
+    if (fix[GS_SKIP + pass]) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, bin = blockIdx.x;
+    const uint64_t W = gs_w(head, cap);
+    const uint64_t chunk = ((W + GS_GRID - 1) / GS_GRID + GS_TILE - 1) / GS_TILE * GS_TILE;   // (gs_chunk's)
+    const uint32_t nb = chunk ? (uint32_t)((W + chunk - 1) / chunk) : 0u;                     // (<= GS_GRID)
+    uint4 *quad = reinterpret_cast<uint4 *>(fix + GS_TAB + (uint64_t)bin * GS_GRID) + tid;
+    uint4 x = *quad;
+    const uint32_t col = 4 * tid;   // (a column at or past nb holds what an older call left: counted as 0)
+    if (col + 0 >= nb) x.x = 0;
+    if (col + 1 >= nb) x.y = 0;
+    if (col + 2 >= nb) x.z = 0;
+    if (col + 3 >= nb) x.w = 0;
+    const uint32_t sum = x.x + x.y + x.z + x.w;
+    const uint32_t inc = gs_incl_scan32(sum, lane);
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    uint32_t run = fix[GS_BASE + pass * GS_BINS + bin] + inc - sum;
+    for (uint32_t w = 0; w < wv; w++) run += s_w[w];
+    uint4 y;
+    y.x = run;
+    y.y = y.x + x.x;
+    y.z = y.y + x.y;
+    y.w = y.z + x.z;
+    *quad = y;
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void k_gs_scatter(const uint64_t *head, uint64_t cap, const uint32_t *in_sub,
+                                                         GsBufs bufs, uint32_t pass) {
+    __shared__ uint32_t s_cnt[GS_ROWS][GS_BINS];
+    __shared__ uint32_t s_base[GS_BINS];
+    if (bufs.fix[GS_SKIP + pass]) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t W = gs_w(head, cap);
+    uint64_t c0, c1, q;
+    gs_chunk(W, blockIdx.x, c0, c1, q);
+    const uint32_t src = bufs.fix[GS_SRC + pass], dst = src == 0 ? 1u : 0u;
+    const uint32_t *kin, *pin;
+    gs_source(bufs, in_sub, src, kin, pin);
+    uint32_t *kout = bufs.k[dst], *pout = bufs.p[dst];
+    uint32_t base = bufs.fix[GS_TAB + tid * GS_GRID + blockIdx.x];   // where the block's next key of bin tid goes
+    for (uint64_t t0 = c0; t0 < c1; t0 += GS_TILE) {
+#pragma unroll
+        for (uint32_t r = 0; r < GS_ROWS; r++) s_cnt[r][tid] = 0;
+        __syncthreads();
+        uint32_t key[GS_PER], pos[GS_PER], rk[GS_PER];
+#pragma unroll
+        for (uint32_t r = 0; r < GS_PER; r++) {
+            const uint32_t row = r * GS_WAVES + wv;
+            const uint64_t i = t0 + row * 64 + lane;
+            const bool ok = i < c1;
+            key[r] = ok ? kin[i] : 0u;
+            pos[r] = !ok ? 0u : pin ? pin[i] : (uint32_t)i;
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < GS_PER; r++) {
+            const uint32_t row = r * GS_WAVES + wv;
+            const bool ok = t0 + row * 64 + lane < c1;
+            const uint32_t d = (key[r] >> (8 * pass)) & 255u;
+            const uint64_t m = gs_match(d, ok);
+            rk[r] = gs_below(m, lane);
+            if (ok && rk[r] == 0) s_cnt[row][d] = (uint32_t)__popcll(m);
+        }
+        __syncthreads();
+        uint32_t run = 0;
+#pragma unroll
+        for (uint32_t r = 0; r < GS_ROWS; r++) {
+            const uint32_t c = s_cnt[r][tid];
+            s_cnt[r][tid] = run;
+            run += c;
+        }
+        s_base[tid] = base;
+        base += run;
+        __syncthreads();
+#pragma unroll
+        for (uint32_t r = 0; r < GS_PER; r++) {
+            const uint32_t row = r * GS_WAVES + wv;
+            const bool ok = t0 + row * 64 + lane < c1;
+            const uint32_t d = (key[r] >> (8 * pass)) & 255u;
+            const uint32_t at = s_base[d] + s_cnt[row][d] + rk[r];
+            if (ok && at < W) {   // (at < W always: the bins' counts sum to W)
+                kout[at] = key[r];
+                pout[at] = pos[r];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// is position i (< W) the first of its group
+__device__ __forceinline__ bool gs_is_head(const uint32_t *k, uint64_t i, uint32_t key) {
+    return i == 0 || k[i - 1] != key;
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void k_gs_heads(const uint64_t *head, uint64_t cap, const uint32_t *in_sub,
+                                                       GsBufs bufs) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint64_t c0, c1, q;
+    gs_chunk(gs_w(head, cap), blockIdx.x, c0, c1, q);
+    const uint32_t *k, *p;
+    gs_source(bufs, in_sub, bufs.fix[GS_SRC + GS_PASSES], k, p);
+    const uint64_t w0 = c0 + wv * q < c1 ? c0 + wv * q : c1, w1 = w0 + q < c1 ? w0 + q : c1;
+    uint32_t n = 0;
+    for (uint64_t i0 = w0; i0 < w1; i0 += 64) {
+        const uint64_t i = i0 + lane;
+        const bool h = i < w1 && gs_is_head(k, i, k[i]);
+        n += (uint32_t)__popcll(__ballot(h));
+    }
+    if (lane == 0) bufs.fix[GS_GCNT + blockIdx.x * GS_WAVES + wv] = n;
+}
+
+__global__ __launch_bounds__(1024) void k_gs_gscan(const uint64_t *head, uint64_t cap, uint32_t *fix, uint64_t *ghead,
+                                                   uint64_t *out_goff, uint64_t gcap) {
+    __shared__ uint32_t s_w[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint4 *quad = reinterpret_cast<uint4 *>(fix + GS_GCNT) + tid;   // block tid's four waves
+    const uint4 x = *quad;
+    const uint32_t c = x.x + x.y + x.z + x.w;
+    const uint32_t inc = gs_incl_scan32(c, lane);
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    uint32_t base = inc - c;
+    for (uint32_t w = 0; w < wv; w++) base += s_w[w];
+    uint4 y;
+    y.x = base;
+    y.y = y.x + x.x;
+    y.z = y.y + x.y;
+    y.w = y.z + x.z;
+    *quad = y;
+    if (tid == 1023) {
+        const uint64_t G = (uint64_t)base + c, W = gs_w(head, cap);
+        ghead[0] = G;
+        ghead[1] = W;
+        if (G <= gcap) out_goff[G] = W;
+    }
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void k_gs_emit(const uint64_t *head, uint64_t cap, const uint32_t *in_topic,
+                                                      const uint32_t *in_value, const uint32_t *in_sub, GsBufs bufs,
+                                                      uint32_t *out_gsub, uint64_t *out_goff, uint64_t gcap,
+                                                      uint32_t *out_topic, uint32_t *out_value, uint32_t *out_sub,
+                                                      uint32_t *out_perm) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t W = gs_w(head, cap);
+    uint64_t c0, c1, q;
+    gs_chunk(W, blockIdx.x, c0, c1, q);
+    const uint32_t *k, *p;
+    gs_source(bufs, in_sub, bufs.fix[GS_SRC + GS_PASSES], k, p);
+    const uint64_t w0 = c0 + wv * q < c1 ? c0 + wv * q : c1, w1 = w0 + q < c1 ? w0 + q : c1;
+    uint64_t g0 = bufs.fix[GS_GCNT + blockIdx.x * GS_WAVES + wv];   // groups that start before w0
+    for (uint64_t i0 = w0; i0 < w1; i0 += 64) {
+        const uint64_t i = i0 + lane;
+        const bool ok = i < w1;
+        const uint32_t key = ok ? k[i] : 0u;
+        const uint32_t pos = !ok ? 0u : p ? p[i] : (uint32_t)i;
+        const bool h = ok && gs_is_head(k, i, key);
+        const uint64_t hm = __ballot(h);
+        if (h) {
+            const uint64_t g = g0 + gs_below(hm, lane);
+            if (g < gcap) out_gsub[g] = key;
+            if (g <= gcap) out_goff[g] = i;   // (g == gcap < G: where the first group left out starts)
+        }
+        g0 += (uint32_t)__popcll(hm);
+        if (ok && pos < W) {   // (pos < W always)
+            out_topic[i] = in_topic[pos];
+            out_value[i] = in_value[pos];
+            out_sub[i] = key;
+            if (out_perm) out_perm[i] = pos;
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_group_subs(const FanoutScratch &fs, const uint64_t *head, const uint32_t *in_topic,
+                             const uint32_t *in_value, const uint32_t *in_sub, uint64_t cap, uint64_t *ghead,
+                             uint32_t *out_gsub, uint64_t *out_goff, uint64_t gcap, uint32_t *out_topic,
+                             uint32_t *out_value, uint32_t *out_sub, uint32_t *out_perm, hipStream_t s) {
+    if (!head || !ghead || !out_goff || (((uintptr_t)head | (uintptr_t)ghead | (uintptr_t)out_goff) & 7))
+        return hipErrorInvalidValue;
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;
+    if (!fs.gs_fix || cap > fs.gs_cap || (cap && (!fs.gs_k[0] || !in_topic || !in_value || !in_sub || !out_topic ||
+                                                   !out_value || !out_sub)) || (gcap && !out_gsub))
+        return hipErrorInvalidValue;
+    const GsBufs b{fs.gs_fix, {fs.gs_k[0], fs.gs_k[1]}, {fs.gs_p[0], fs.gs_p[1]}};
+    const dim3 g(GS_GRID), t(GS_BLOCK), one(1), wide(1024);
+    hipLaunchKernelGGL(k_gs_pre, g, t, 0, s, head, cap, in_sub, b.fix);
+    hipLaunchKernelGGL(k_gs_plan, one, wide, 0, s, head, cap, b.fix);
+    for (uint32_t p = 0; p < GS_PASSES; p++) {
+        hipLaunchKernelGGL(k_gs_hist, g, t, 0, s, head, cap, in_sub, b, p);
+        hipLaunchKernelGGL(k_gs_scan, dim3(GS_BINS), t, 0, s, head, cap, b.fix, p);
+        hipLaunchKernelGGL(k_gs_scatter, g, t, 0, s, head, cap, in_sub, b, p);
+    }
+    hipLaunchKernelGGL(k_gs_heads, g, t, 0, s, head, cap, in_sub, b);
+    hipLaunchKernelGGL(k_gs_gscan, one, wide, 0, s, head, cap, b.fix, ghead, out_goff, gcap);
+    hipLaunchKernelGGL(k_gs_emit, g, t, 0, s, head, cap, in_topic, in_value, in_sub, b, out_gsub, out_goff, gcap,
+                       out_topic, out_value, out_sub, out_perm);
+    return hipGetLastError();
+}
+
+}  // namespace tmx

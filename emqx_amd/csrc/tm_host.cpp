@@ -139,6 +139,10 @@ struct Lane {
     // tm_publish_batch: the picked member of every kept entry, then the pick's two head words
     uint32_t *d_sm = nullptr; uint64_t d_sm_cap = 0;
     uint32_t *d_sk = nullptr; uint64_t d_sk_cap = 0;   // its two key words per topic
+    // tm_deliver_batch: the deliveries grouped by subscriber, the groups' subscribers and offsets
+    uint32_t *d_gt = nullptr, *d_gv = nullptr, *d_gs = nullptr; uint64_t d_gt_cap = 0, d_gv_cap = 0, d_gs_cap = 0;
+    uint32_t *d_gsub = nullptr; uint64_t d_gsub_cap = 0;
+    uint64_t *d_goff = nullptr; uint64_t d_goff_cap = 0;
 };
 
 // Patch log: a ring of the last PATCH_RING patches (numbered 1, 2, ... in the
@@ -1818,7 +1822,8 @@ void free_lane(Lane &l) {
     free_workspace(l.w);
     void *dv[] = {l.d_in, l.d_res, l.d_vals, l.d_o64, l.d_h64, l.f.tab, l.f.tot, l.f.t, l.f.v, l.f.b, l.f.voff, l.f.sums, l.f.b2,
                   l.d_ft, l.d_fv, l.d_fo, l.d_pr, l.f.ag_bits, l.f.ag_pre, l.f.ag_cnt, l.d_at, l.d_av, l.d_ao, l.fo1_s,
-                  l.f.dp_cnt, l.f.dp_off, l.f.dp_tot, l.d_dt, l.d_dv, l.d_ds, l.f.sh_key, l.f.sh_cnt, l.d_sm, l.d_sk};
+                  l.f.dp_cnt, l.f.dp_off, l.f.dp_tot, l.d_dt, l.d_dv, l.d_ds, l.f.sh_key, l.f.sh_cnt, l.d_sm, l.d_sk,
+                  l.f.gs_fix, l.f.gs_k[0], l.d_gt, l.d_gv, l.d_gs, l.d_gsub, l.d_goff};
     for (void *p : dv) if (p) (void)hipFree(p);
     void *pins[] = {l.pin_in, l.pin_out, l.pin_vals, l.fo1_h};
     for (void *p : pins) if (p) (void)hipHostFree(p);
@@ -2163,7 +2168,7 @@ struct HostBatch {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 19u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 20u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 
@@ -2751,6 +2756,54 @@ int ensure_share(tm_index *ix, Lane &ln, uint64_t cap) {
     return TM_OK;
 }
 
+// the grouping's scratch on a lane (grow-only; freed with the lane): the fixed
+// words (its counters zero) and the two (key, position) pair arrays below cap;
+// who: the entry point called, for the messages
+int ensure_group(tm_index *ix, Lane &ln, uint64_t cap, const char *who) {
+    FanoutScratch &f = ln.f;
+    if (!f.gs_fix) {
+        if (hipMalloc(&f.gs_fix, (uint64_t)GS_FIX_WORDS * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            f.gs_fix = nullptr;
+            return fail(ix, TM_ENOMEM, std::string(who) + ": no device memory for the grouping's histograms (1.1 MiB)");
+        }
+        HIPCHK(ix, hipMemsetAsync(f.gs_fix, 0, (uint64_t)GS_ZERO_WORDS * 4, ln.s));   // the pass counters, the bin totals
+    }
+    if (cap <= f.gs_cap && f.gs_k[0]) return TM_OK;
+    HIPCHK(ix, hipStreamSynchronize(ln.s));   // only this lane's stream uses them
+    if (f.gs_k[0]) (void)hipFree(f.gs_k[0]);
+    f.gs_k[0] = nullptr;
+    f.gs_cap = 0;
+    const uint64_t c = std::max<uint64_t>(std::min<uint64_t>(cap + cap / 4, 0xFFFFFFFFull), 4096);
+    if (hipMalloc(&f.gs_k[0], c * 16) != hipSuccess) {
+        (void)hipGetLastError();
+        f.gs_k[0] = nullptr;
+        return fail(ix, TM_ENOMEM, std::string(who) + ": no device memory for the grouping's pair arrays (16 bytes x cap)");
+    }
+    f.gs_p[0] = f.gs_k[0] + c;
+    f.gs_k[1] = f.gs_k[0] + 2 * c;
+    f.gs_p[1] = f.gs_k[0] + 3 * c;
+    f.gs_cap = c;
+    return TM_OK;
+}
+
+// the passes the live lanes' grouping calls ran (which 0) / skipped (1) so far
+// (caller holds ix->mu; waits for nothing: a call still in flight is not counted)
+int group_passes(tm_index *ix, int which, uint64_t &out) {
+    out = 0;
+    int dev = 0;
+    HIPCHK(ix, hipGetDevice(&dev));
+    for (auto &l : ix->lanes) {
+        if (!l->f.gs_fix) continue;
+        uint64_t st[2] = {0, 0};
+        HIPCHK(ix, hipSetDevice(ix->rep[l->r].device));
+        HIPCHK(ix, hipMemcpy(st, l->f.gs_fix + GS_STAT, 16, hipMemcpyDeviceToHost));
+        out += st[which];
+    }
+    HIPCHK(ix, hipSetDevice(dev));
+    return TM_OK;
+}
+
 // group g's state array holds `need` slots (caller holds ix->mu and
 // ix->dst_mu; the calling thread is on the group's device).  It grows with
 // its contents kept and the new words UNDEF: no pick may still use the old
@@ -2959,6 +3012,27 @@ int tm_dispatch_dev(tm_index *ix, uint32_t n_dests, const uint64_t *dest_offs, u
     if (!sub_span && (rc = subs_upload(ix, b.grp, b.s, sub_span, span_len, sub_pool, pool_len))) return rc;
     HIPCHK(ix, launch_dispatch(b.ln->f, n_dests, dest_offs, bucket, topic, value, cap, sub_span, span_len, sub_pool,
                                pool_len, out_head, out_offsets, out_topic, out_value, out_sub, out_cap, b.s));
+    return b.done();
+}
+
+int tm_group_subs_dev(tm_index *ix, const uint64_t *head, const uint32_t *topic, const uint32_t *value,
+                      const uint32_t *sub, uint64_t cap, uint64_t *out_ghead, uint32_t *out_gsub, uint64_t *out_goff,
+                      uint64_t gcap, uint32_t *out_topic, uint32_t *out_value, uint32_t *out_sub, uint32_t *out_perm,
+                      void *stream) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_group_subs_dev: null handle");
+    if (!head || !out_ghead || !out_goff || (gcap && !out_gsub) ||
+        (cap && (!topic || !value || !sub || !out_topic || !out_value || !out_sub)))
+        return fail(ix, TM_EINVAL, "tm_group_subs_dev: null buffer");
+    if ((uintptr_t)head & 7) return fail(ix, TM_EINVAL, "tm_group_subs_dev: d_head must be 8-byte aligned");
+    if ((uintptr_t)out_ghead & 7) return fail(ix, TM_EINVAL, "tm_group_subs_dev: d_out_ghead must be 8-byte aligned");
+    if ((uintptr_t)out_goff & 7) return fail(ix, TM_EINVAL, "tm_group_subs_dev: d_out_goff must be 8-byte aligned");
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
+    DevBatch b(ix, stream);
+    int rc;
+    if ((rc = b.open_fanout())) return rc;
+    if ((rc = ensure_group(ix, *b.ln, cap, "tm_group_subs_dev"))) return rc;
+    HIPCHK(ix, launch_group_subs(b.ln->f, head, topic, value, sub, cap, out_ghead, out_gsub, out_goff, gcap, out_topic,
+                                 out_value, out_sub, out_perm, b.s));
     return b.done();
 }
 
@@ -3771,6 +3845,38 @@ static int dispatch_scratch(tm_index *ix, Lane &ln, uint64_t vcap, uint64_t want
     return grow_dev(ix, ln.s, ln.d_ds, ln.d_ds_cap, want);
 }
 
+// tm_deliver_batch's grouping half: the caller's group outputs (the three
+// delivery arrays of the dispatch half arrive grouped)
+struct RouteGroup {
+    uint64_t *out_ghead;
+    uint32_t *out_gsub;
+    uint64_t *out_goff;
+    uint64_t gcap;
+};
+
+// room on the lane for `want` grouped deliveries and min(gcap, want) groups
+// (G <= W <= want: a lane array that is short means the caller's is)
+static int group_scratch(tm_index *ix, Lane &ln, uint64_t want, uint64_t gcap, const char *who) {
+    int rc;
+    const uint64_t groom = std::min(gcap, want);
+    if ((rc = ensure_group(ix, ln, want, who))) return rc;
+    if ((rc = grow_dev(ix, ln.s, ln.d_gt, ln.d_gt_cap, want))) return rc;
+    if ((rc = grow_dev(ix, ln.s, ln.d_gv, ln.d_gv_cap, want))) return rc;
+    if ((rc = grow_dev(ix, ln.s, ln.d_gs, ln.d_gs_cap, want))) return rc;
+    if ((rc = grow_dev(ix, ln.s, ln.d_gsub, ln.d_gsub_cap, groom))) return rc;
+    return grow_dev(ix, ln.s, ln.d_goff, ln.d_goff_cap, groom + 1);
+}
+
+// queues the grouping of the lane's deliveries (d_dt / d_dv / d_ds, the first
+// min(d_head[1], out_cap) of them: what queue_dispatch was given) into d_gt /
+// d_gv / d_gs, d_gsub and d_goff; d_ghead = [G, W] (caller holds ix->mu)
+static int queue_group(tm_index *ix, Lane &ln, const uint64_t *d_head, uint64_t out_cap, uint64_t gcap,
+                       uint64_t *d_ghead) {
+    HIPCHK(ix, launch_group_subs(ln.f, d_head, ln.d_dt, ln.d_dv, ln.d_ds, out_cap, d_ghead, ln.d_gsub, ln.d_goff,
+                                 std::min(gcap, out_cap), ln.d_gt, ln.d_gv, ln.d_gs, nullptr, ln.s));
+    return TM_OK;
+}
+
 // tm_publish_batch's pick half: the per-topic key words (host, n each, may be
 // null), the seed, and the caller's member array (aligned with out_topic)
 struct RoutePick {
@@ -3846,7 +3952,8 @@ static int copy_route_out(tm_index *ix, Lane &ln, uint32_t n_dests, uint64_t tot
 
 // One request of the route family (tm_route_batch, tm_dispatch_batch,
 // tm_publish_batch and their 32-bit forms): everything the six entry points
-// share.  dp / pk: the dispatch and the pick, null when the call has none.
+// share.  dp / pk / gp: the dispatch, the pick and the grouping of the
+// deliveries (tm_deliver_batch; with dp only), null when the call has none.
 // who: the entry point the caller called -- every refusal and failure names
 // it.  Only the topic offsets and out_dest_offsets differ in width; they travel
 // beside the request.
@@ -3860,6 +3967,7 @@ struct RouteReq {
     uint8_t *out_err;
     const RouteDispatch *dp;
     const RoutePick *pk;
+    const RouteGroup *gp = nullptr;
     bool aggre() const { return flags & TM_ROUTE_AGGRE; }
 };
 
@@ -3883,6 +3991,8 @@ static int route_check(tm_index *ix, const RouteReq &rq, bool offsets, bool narr
     if (!offsets || (narrow && !rq.out_err) ||
         (rq.cap && (!rq.out_topic || !rq.out_values || (rq.pk && !rq.pk->out_member))) ||
         (dp && (!dp->out_head || (dp->dcap && (!dp->out_topic || !dp->out_value || !dp->out_sub)))))
+        return route_fail(ix, rq, TM_EINVAL, "null buffer");
+    if (rq.gp && (!dp || !rq.gp->out_ghead || !rq.gp->out_goff || (rq.gp->gcap && !rq.gp->out_gsub)))
         return route_fail(ix, rq, TM_EINVAL, "null buffer");
     if (narrow && dp && ((uintptr_t)dp->out_head & 7)) return route_fail(ix, rq, TM_EINVAL, "out_head must be 8-byte aligned");
     if (rq.n >= 0xFFFFFFFFull) return route_fail(ix, rq, TM_EINVAL, "batch too large");
@@ -3919,12 +4029,17 @@ static int pick_after_run(tm_index *ix, HostBatch &hb, const RouteReq &rq, uint6
 // bucket dp->local_dest over the results; the lane's delivery scratch grows
 // from the T that comes back with the results, and then only the dispatch
 // kernels are queued again.
+// gp (tm_deliver_batch): behind every dispatch queued, on the same lane, the
+// grouping of its deliveries; the copies out read the grouped arrays.  The
+// lane's group arrays hold min(gcap, deliveries) groups, so nothing but the
+// dispatch's own retry ever queues it again.
 // pk (tm_publish_batch): pick_after_run, when the kept entries fit.
 static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to, uint64_t *out_dest_offsets) {
     const uint64_t n = rq.n, cap = rq.cap;
     const uint32_t n_dests = rq.n_dests;
     const bool aggre = rq.aggre();
     const RouteDispatch *dp = rq.dp;
+    const RouteGroup *gp = rq.gp;
     HostBatch hb(ix, rq.who);
     int rc;
     if ((rc = hb.open(n))) return rc;
@@ -3934,14 +4049,16 @@ static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to
     const uint8_t *dbytes;
     const uint64_t *doffs;
     if ((rc = stage_in(ix, ln, n, rq.tb, to, nullptr, dbytes, doffs))) return rc;
-    // hit offsets, then the err flags; with a dispatch its two head words after them
+    // hit offsets, then the err flags; with a dispatch its two head words after them, then the grouping's
     const uint64_t hoff = ((n + 1) * 8 + n + 7) & ~7ull;
-    const uint64_t rbytes = dp ? hoff + 16 : (n + 1) * 8 + n;
+    const uint64_t hbytes = gp ? 32 : 16;
+    const uint64_t rbytes = dp ? hoff + hbytes : (n + 1) * 8 + n;
     uint8_t *dres;
     if ((rc = stage_out(ix, ln, n, rbytes, dres))) return rc;
     uint64_t *dhit = reinterpret_cast<uint64_t *>(dres);
     uint8_t *derr = dres + (n + 1) * 8;
     uint64_t *dhead = reinterpret_cast<uint64_t *>(dres + hoff);
+    const uint64_t gcap = gp ? gp->gcap : 0;
     const uint64_t dcap = dp ? std::min<uint64_t>(dp->dcap, 0xFFFFFFFFull) : 0;
     uint64_t total = 0, vcap = std::max<uint64_t>({ln.d_vals_cap, 4 * n, 1 << 16});
     uint64_t dwant = dp ? std::max<uint64_t>(ln.d_ds_cap, 1 << 16) : 0;   // deliveries the lane has room for
@@ -3950,6 +4067,7 @@ static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to
         if ((rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, vcap))) return rc;
         if ((rc = route_scratch(ix, ln, n_dests, vcap, aggre, false, 0))) return rc;
         if (dp && (rc = dispatch_scratch(ix, ln, vcap, dwant))) return rc;
+        if (gp && (rc = group_scratch(ix, ln, dwant, gcap, rq.who))) return rc;
         rc = hb.run([&](const DevIndex &d, uint32_t tag) -> int {
             int path = PATH_PHASES;
             HIPCHK(ix, launch_match(d, ln.w, n, dbytes, doffs, dhit, derr, ln.d_vals, vcap, tag, next_lb(ix),
@@ -3960,6 +4078,8 @@ static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to
             if (dp)
                 if (int rc = queue_dispatch(ix, ln, n_dests, dp->local_dest, aggre, vcap, std::min(dwant, dcap), dhead))
                     return rc;
+            if (gp)
+                if (int rc = queue_group(ix, ln, dhead, std::min(dwant, dcap), gcap, dhead + 2)) return rc;
             return fetch_out(ix, ln, n, rbytes);
         });
         if (rc) return rc;
@@ -3969,9 +4089,9 @@ static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to
         vcap = total + total / 4;
         if ((rc = hb.relock())) return rc;
     }
-    uint64_t head[2] = {0, 0};
+    uint64_t head[4] = {0, 0, 0, 0};   // [M, T], then the grouping's [G, W]
     if (dp) {
-        std::memcpy(head, ln.pin_out + hoff, 16);
+        std::memcpy(head, ln.pin_out + hoff, hbytes);
         for (int attempt = 0; std::min(head[1], dcap) > dwant; attempt++) {
             // more deliveries than the lane had room for: the scratch grows and the
             // dispatch alone runs again on the results still in the lane (no walk)
@@ -3979,12 +4099,14 @@ static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to
             dwant = std::min(head[1] + head[1] / 4, dcap);
             if ((rc = hb.relock())) return rc;
             if ((rc = dispatch_scratch(ix, ln, vcap, dwant))) return rc;
+            if (gp && (rc = group_scratch(ix, ln, dwant, gcap, rq.who))) return rc;
             if ((rc = queue_dispatch(ix, ln, n_dests, dp->local_dest, aggre, vcap, dwant, dhead))) return rc;
-            if (n > ZC_TOPICS) HIPCHK(ix, hipMemcpyAsync(ln.pin_out + hoff, dhead, 16, hipMemcpyDeviceToHost, s));
+            if (gp && (rc = queue_group(ix, ln, dhead, dwant, gcap, dhead + 2))) return rc;
+            if (n > ZC_TOPICS) HIPCHK(ix, hipMemcpyAsync(ln.pin_out + hoff, dhead, hbytes, hipMemcpyDeviceToHost, s));
             if ((rc = batch_done(ix, ln))) return rc;
             hb.g.unlock();
             HIPCHK(ix, hipStreamSynchronize(s));
-            std::memcpy(head, ln.pin_out + hoff, 16);
+            std::memcpy(head, ln.pin_out + hoff, hbytes);
         }
     }
     rc = copy_route_out(ix, ln, n_dests, total, cap, aggre, aggre && total <= cap, out_dest_offsets, nullptr, rq.out_topic,
@@ -3996,14 +4118,20 @@ static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to
     if (dp) {
         dp->out_head[0] = head[0];
         dp->out_head[1] = head[1];
-        const uint64_t keep = std::min(head[1], dcap);
+        const uint64_t keep = std::min(head[1], dcap), gkeep = gp ? std::min(head[2], gcap) : 0;
         if (keep) {
-            HIPCHK(ix, hipMemcpyAsync(dp->out_topic, ln.d_dt, keep * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(ix, hipMemcpyAsync(dp->out_value, ln.d_dv, keep * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(ix, hipMemcpyAsync(dp->out_sub, ln.d_ds, keep * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(ix, hipStreamSynchronize(s));
+            HIPCHK(ix, hipMemcpyAsync(dp->out_topic, gp ? ln.d_gt : ln.d_dt, keep * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipMemcpyAsync(dp->out_value, gp ? ln.d_gv : ln.d_dv, keep * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipMemcpyAsync(dp->out_sub, gp ? ln.d_gs : ln.d_ds, keep * 4, hipMemcpyDeviceToHost, s));
         }
-        if (head[1] > dp->dcap) rc = TM_ECAP;
+        if (gp) {
+            gp->out_ghead[0] = head[2];
+            gp->out_ghead[1] = head[3];
+            if (gkeep) HIPCHK(ix, hipMemcpyAsync(gp->out_gsub, ln.d_gsub, gkeep * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipMemcpyAsync(gp->out_goff, ln.d_goff, (gkeep + 1) * 8, hipMemcpyDeviceToHost, s));
+        }
+        if (keep || gp) HIPCHK(ix, hipStreamSynchronize(s));
+        if (head[1] > dp->dcap || (gp && head[2] > gcap)) rc = TM_ECAP;
     }
     return rc;
 }
@@ -4035,6 +4163,17 @@ int tm_dispatch_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_
                       uint32_t *out_dsub, uint64_t dcap, uint8_t *out_err) {
     const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
     const RouteReq rq{"tm_dispatch_batch", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, &dp, nullptr};
+    return route_batch64(ix, rq, to, out_dest_offsets);
+}
+
+int tm_deliver_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
+                     uint32_t local_dest, uint32_t flags, uint64_t *out_dest_offsets, uint32_t *out_topic,
+                     uint32_t *out_values, uint64_t cap, uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue,
+                     uint32_t *out_dsub, uint64_t dcap, uint64_t *out_ghead, uint32_t *out_gsub, uint64_t *out_goff,
+                     uint64_t gcap, uint8_t *out_err) {
+    const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
+    const RouteGroup gp{out_ghead, out_gsub, out_goff, gcap};
+    const RouteReq rq{"tm_deliver_batch", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, &dp, nullptr, &gp};
     return route_batch64(ix, rq, to, out_dest_offsets);
 }
 
@@ -4682,6 +4821,14 @@ int tm_debug_get(tm_index *ix, uint32_t key, uint64_t *value) {
     case TM_DEBUG_DISPATCH_GRID: *value = ix->dispatch_grid.load(); break;
     case TM_DEBUG_PUBLISH_ONE: *value = ix->publish_one.load(); break;
     case TM_DEBUG_PUBLISH_GRID: *value = ix->publish_grid.load(); break;
+    case TM_DEBUG_GROUP_TILE: *value = GS_TILE; break;
+    case TM_DEBUG_GROUP_GRID: *value = GS_GRID; break;
+    case TM_DEBUG_GROUP_PASSES_RUN:
+    case TM_DEBUG_GROUP_PASSES_SKIPPED: {
+        std::lock_guard<std::mutex> g(ix->mu);
+        if (int rc = group_passes(ix, key == TM_DEBUG_GROUP_PASSES_SKIPPED, *value)) return rc;
+        break;
+    }
     case TM_DEBUG_DP1_MAX: {
         std::lock_guard<std::mutex> g(ix->mu);
         *value = ix->dp1_max;

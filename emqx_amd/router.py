@@ -688,9 +688,58 @@ class Router:
             raise ValueError("match_routes_dispatch: the router has no local_subs")
         return self._routes_by_dest(topics, errors, aggre, True)
 
-    def _routes_by_dest(self, topics, errors, aggre, dispatch, publish=None):
+    def match_routes_deliver(self, topics, errors: str = "raise", aggre: bool = False):
+        """match_routes_dispatch with the deliveries also grouped by subscriber
+        on the device (tm_deliver_batch) -> (ByDest, deliveries, by_sub):
+        deliveries is match_routes_dispatch's list; by_sub = {pid: [(message
+        index, To)]} is that list grouped stably by pid -- what one connection
+        process gathers from its mailbox (emqx_connection.erl:611-612), one
+        list per subscriber per batch, in publish order.  The device's groups
+        are in traversal order inside a message; a pid's run per message is
+        reversed here into match_routes_batch's order, behind the bag's
+        exact-topic row, which is expanded here.  Needs local_subs."""
+        if self.local_subs is None:
+            raise ValueError("match_routes_deliver: the router has no local_subs")
+        return self._routes_by_dest(topics, errors, aggre, True, grouped=True)
+
+    @staticmethod
+    def group_deliveries(deliveries) -> dict:
+        """[(message index, To, pid)] -> {pid: [(message index, To)]}, stably"""
+        by_sub: dict = {}
+        for i, to, p in deliveries:
+            by_sub.setdefault(p, []).append((i, to))
+        return by_sub
+
+    def _ungroup(self, mirror, doff, tidx, kids, local, grouped, groups):
+        """tm_deliver_batch's grouped deliveries back in tm_dispatch_batch's
+        order -> (dt, dk, ds), and the device's groups as {sub id: [(message
+        index, kid)]} in device order.  A delivery's place: its entry's place in
+        the local bucket (one entry per (message, kid)), then its subscriber's
+        place in the kid's list (local_subs; an id no longer there: last, by id)."""
+        gt, gk, gs = (a.tolist() for a in grouped)
+        gsub, goff = groups[0].tolist(), groups[1].tolist()
+        lo, hi = int(doff[local]), int(doff[local + 1])
+        rank = {e: q for q, e in enumerate(zip(tidx[lo:hi].tolist(), kids[lo:hi].tolist()))}
+        place: dict = {}   # kid -> {sub id: position in its list}
+        dev_groups, keyed = {}, []
+        for g, sub in enumerate(gsub):
+            run = dev_groups[sub] = []
+            for j in range(goff[g], goff[g + 1]):
+                i, kid = gt[j], gk[j]
+                run.append((i, kid))
+                if kid not in place:
+                    k = mirror.decode(np.array([kid], dtype=np.uint32))
+                    ids = self.local_subs.dispatch_ids(ti.get_topic(k[0])) if k else []
+                    place[kid] = {s: n for n, s in enumerate(ids)}
+                keyed.append((rank.get((i, kid), hi), place[kid].get(sub, 1 << 32), sub, j))
+        keyed.sort()
+        order = [j for _, _, _, j in keyed]
+        return tuple(np.asarray(a, dtype=np.uint32)[order] for a in grouped), dev_groups
+
+    def _routes_by_dest(self, topics, errors, aggre, dispatch, publish=None, grouped=False):
         topics = [bytes(t) for t in topics]
         member = None
+        dev_groups = None
         mirror = self._live_mirror()
         out = ByDest()
         deliveries: list = []
@@ -708,6 +757,9 @@ class Router:
                 if publish is not None:
                     pub = mirror.publish_kids32 if self._route_in_place else mirror.publish_kids
                     (doff, tidx, kids, err), (dt, dk, ds), member = pub(topics, n_dests, local, *publish)
+                elif grouped:
+                    (doff, tidx, kids, err), gdel, ggrp = mirror.deliver_kids(topics, n_dests, local, aggre=aggre)
+                    (dt, dk, ds), dev_groups = self._ungroup(mirror, doff, tidx, kids, local, gdel, ggrp)
                 else:
                     disp = mirror.dispatch_kids32 if self._route_in_place else mirror.dispatch_kids
                     (doff, tidx, kids, err), (dt, dk, ds) = disp(topics, n_dests, local, aggre=aggre)
@@ -823,6 +875,8 @@ class Router:
                 # matches/3's order: the reverse of the traversal
                 for to, pids in reversed(dev_del.get(i, ())):
                     deliveries.extend((i, to, p) for p in pids)
+        if grouped:
+            return out, deliveries, self._by_sub(mirror, topics, out.errors, dev_groups)
         if publish is None:
             return out, deliveries
         picks = self._host_picks(topics, out.errors, *publish)
@@ -831,6 +885,37 @@ class Router:
         for g in picks:
             picks[g].sort(key=lambda e: e[0])   # (stable: a message's bag row stays first)
         return out, deliveries, picks
+
+    def _by_sub(self, mirror, topics, errors, dev_groups) -> dict:
+        """{pid: [(message index, To)]} from the device's groups ({sub id: [(message
+        index, kid)]}, message order, traversal order inside a message): per
+        message the bag's exact-topic row first (expanded here), then the pid's
+        run reversed -- matches/3's order is the reverse of the traversal."""
+        per: dict = {}   # pid -> {message index: [To]}
+        for i, t in enumerate(topics):
+            if i not in errors and self.node in self._bag.get(t, ()):
+                for p in self.local_subs.dispatch_order(t):
+                    per.setdefault(p, {}).setdefault(i, []).append(t)
+        tos: dict = {}
+        for sub, run in dev_groups.items():
+            mine, at = None, 0
+            while at < len(run):
+                i, e = run[at][0], at + 1
+                while e < len(run) and run[e][0] == i:
+                    e += 1
+                row = []
+                for _, kid in reversed(run[at:e]):
+                    if kid not in tos:
+                        k = mirror.decode(np.array([kid], dtype=np.uint32))
+                        tos[kid] = ti.get_topic(k[0]) if k else None
+                    if tos[kid] is not None:   # (a key deleted since the batch began is dropped, as decode drops it)
+                        row.append(tos[kid])
+                if row and i not in errors:
+                    if mine is None:
+                        mine = per.setdefault(self.local_subs.pid_of(sub), {})
+                    mine.setdefault(i, []).extend(row)
+                at = e
+        return {p: [(i, to) for i in sorted(m) for to in m[i]] for p, m in per.items()}
 
     def topics(self):
         """topics/0 = list_topics_v2 (emqx_router.erl:627-630): the bag's topics,

@@ -345,6 +345,15 @@ class Tab:
         blob, offs = _native.pack_strings(topics)
         return self._index.dispatch_batch(blob, offs, n_dests, local_dest, aggre=aggre)
 
+    def deliver_kids(self, topics, n_dests: int, local_dest: int, aggre: bool = False):
+        """tm_deliver_batch -> (route_kids' result, dispatch_kids' three delivery
+        arrays GROUPED by subscriber id -- ascending ids, a subscriber's
+        deliveries in dispatch_kids' order -- and (subscriber id u32[G], offsets
+        u64[G + 1]): subscriber g owns the deliveries [offsets[g], offsets[g + 1]))."""
+        self.flush()
+        blob, offs = _native.pack_strings(topics)
+        return self._index.deliver_batch(blob, offs, n_dests, local_dest, aggre=aggre)
+
     def _route_set(self, n: int, nbytes: int, n_dests: int, cap: int, dcap: int | None = None, pick: bool = False) -> dict:
         """A set of pinned buffers (host_array) large enough for the batch, from
         the pool or new -- what a NIF keeps per scheduler.  Arrays too small are

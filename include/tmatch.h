@@ -883,6 +883,78 @@ int tm_publish_batch32(tm_index *h, uint64_t n, const uint8_t *topic_bytes, cons
                        uint64_t dcap, const uint32_t *key_clientid, const uint32_t *key_topic, uint32_t seed,
                        uint32_t *out_member, uint8_t *out_err);
 
+/* Deliveries grouped by subscriber on the device (ABI minor 20).  The calls
+ * above end with the local node's deliveries (message, route value,
+ * subscriber) in message order; their consumer is one process per subscriber:
+ * do_dispatch2/3 sends SubPid ! {deliver, To, Msg} (emqx_broker.erl:745-752),
+ * and a connection process first gathers its mailbox's delivers back into one
+ * list (emqx_connection.erl:611-612, emqx_channel.erl:1099-1137).  For a
+ * micro-batched broker the hand-off is one list per subscriber per batch, the
+ * subscriber's deliveries in publish order.
+ *
+ * tm_group_subs_dev: device buffers, asynchronous on `stream`.  The input is
+ * what tm_dispatch_dev wrote: d_head = [M, T] (read on the device, so the call
+ * chains behind tm_dispatch_dev with no host synchronisation) and the three
+ * delivery arrays, of which cap were there to be written.  cap is clamped to
+ * 2^32 - 1.  In numpy:
+ *   W = min(head[1], cap);  s = sub[:W]
+ *   p = argsort(s, kind="stable")                      -- u32 positions
+ *   out_topic, out_value, out_sub = topic[p], value[p], s[p];  out_perm = p  (when given)
+ *   gs, cnt = unique(s, return_counts=True);  G = len(gs);  Gw = min(G, gcap)
+ *   out_gsub[:Gw] = gs[:Gw];  out_goff[0..Gw] = concatenate([0], cumsum(cnt))[:Gw + 1]
+ *   ghead = [G, W]
+ * Groups come in ascending subscriber id (unsigned); inside a group the
+ * deliveries keep their input order -- the order that preserves MQTT's
+ * per-subscriber ordering.  Every u32 is a legal id, 0 and 0xFFFFFFFF included.
+ * Nothing at or past W is written in the four per-delivery outputs, nothing at
+ * or past Gw in d_out_gsub and nothing past d_out_goff[Gw] (d_out_goff holds
+ * gcap + 1 words; entry 0 is written whatever gcap is); the inputs are not
+ * modified and no input position >= W is read.  The outputs MUST NOT overlap
+ * the inputs.  The grouped per-delivery arrays are complete whatever gcap is;
+ * G > gcap: the caller reruns with room for G; ghead is exact either way.
+ * A stable least-significant-digit radix sort of (subscriber, position) pairs
+ * in 8-bit digits over a fixed grid -- per pass a per-block histogram, a scan
+ * and a scatter that ranks stably inside the block -- then the group heads are
+ * flagged and scanned and the payload gathered; every step a launch of its own
+ * in stream order, no block waiting for another.  A digit on which all W ids
+ * agree is skipped on the device (interned ids are dense: ids below 2^16 cost
+ * two passes, not four) with the same results; TM_DEBUG_GROUP_PASSES_RUN /
+ * _SKIPPED count both.  The stream's scratch (kept with the fan-out's and the
+ * dispatch's, tm_stream_release) holds 16 bytes x cap and 1.1 MiB (TM_ENOMEM
+ * if that cannot be had, as for tm_dispatch_dev).  It is sized from cap, not
+ * from T, which only the device knows when the call is queued: pass the size
+ * of the buffers, never 2^32 - 1 for "no bound" -- that asks for about 70 GB a
+ * stream.  TM_EINVAL before any device work: a null handle, a null required
+ * pointer (d_head, d_out_ghead, d_out_goff; the six arrays when cap > 0;
+ * d_out_gsub when gcap > 0), d_head, d_out_ghead or d_out_goff not 8-byte
+ * aligned.
+ *
+ * tm_deliver_batch: the host product path -- tm_dispatch_batch with the same
+ * arguments, followed on the same lane and in the same run by the grouping of
+ * the local bucket's deliveries.  The route outputs, out_head and every
+ * TM_ECAP rule are tm_dispatch_batch's; the three delivery arrays arrive
+ * GROUPED (tm_group_subs_dev's out_topic / out_value / out_sub over the first
+ * min(T, dcap) deliveries), out_ghead = [G, W], out_gsub takes the first
+ * min(G, gcap) subscribers and out_goff (gcap + 1 words) their offsets and
+ * the end of the last.  TM_ECAP also when G > gcap: out_ghead[0] sizes the
+ * retry.  When the lane's delivery scratch was short the dispatch and the
+ * grouping are queued again on the results still in the lane: never a second
+ * walk.  flags: 0 or TM_ROUTE_AGGRE.  TM_EINVAL: whatever tm_dispatch_batch
+ * refuses, a null out_ghead or out_goff, a null out_gsub with gcap > 0.
+ * Lanes, read-your-writes, the device-failure retry and the out_err rules are
+ * unchanged. */
+int tm_group_subs_dev(tm_index *h, const uint64_t *d_head,
+                      const uint32_t *d_topic, const uint32_t *d_value, const uint32_t *d_sub, uint64_t cap,
+                      uint64_t *d_out_ghead, uint32_t *d_out_gsub, uint64_t *d_out_goff, uint64_t gcap,
+                      uint32_t *d_out_topic, uint32_t *d_out_value, uint32_t *d_out_sub,
+                      uint32_t *d_out_perm, void *stream);
+int tm_deliver_batch(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint64_t *topic_offsets,
+                     uint32_t n_dests, uint32_t local_dest, uint32_t flags,
+                     uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                     uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
+                     uint64_t dcap, uint64_t *out_ghead, uint32_t *out_gsub, uint64_t *out_goff, uint64_t gcap,
+                     uint8_t *out_err);
+
 /* Release the batch scratch kept for `stream` (after its batches finish);
  * a caller that retires a stream calls this.  No reference counterpart. */
 int tm_stream_release(tm_index *h, void *stream);
@@ -990,7 +1062,12 @@ int tm_profile_read(tm_index *h, double *walk_ms, double *batch_ms, uint64_t *ba
  * bucket up to which the one-launch kernel expands them itself, clamped to the
  * compiled bound (32768).  TM_DEBUG_PUBLISH_ONE / TM_DEBUG_PUBLISH_GRID (get
  * only): tm_publish_batch32 calls the one-launch pick kernel picked for / that
- * the grid pick or the staged path finished. */
+ * the grid pick or the staged path finished.  TM_DEBUG_GROUP_TILE (get only):
+ * the keys a block of tm_group_subs_dev ranks per pass at a time, and
+ * TM_DEBUG_GROUP_GRID (get only) the blocks of its fixed grid;
+ * TM_DEBUG_GROUP_PASSES_RUN / TM_DEBUG_GROUP_PASSES_SKIPPED (get only): the
+ * digit passes the grouping calls that have finished ran / skipped, summed
+ * over the streams whose scratch is live (four per call together). */
 enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES = 3, TM_DEBUG_PHASES = 4,
        TM_DEBUG_FAILED_BATCHES = 5, TM_DEBUG_RETRIED_BATCHES = 6, TM_DEBUG_PATH_PHASES = 7,
        TM_DEBUG_PATH_SMALL = 8, TM_DEBUG_PATH_LANE = 9, TM_DEBUG_SMALL_KERNEL = 10,
@@ -1000,7 +1077,9 @@ enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES =
        TM_DEBUG_CMB_SPIN = 23, TM_DEBUG_PATCH_ZC = 24, TM_DEBUG_FANOUT_GRID = 25,
        TM_DEBUG_ROUTE_ONE = 26, TM_DEBUG_ROUTE_GRID = 27, TM_DEBUG_ANNEX0 = 28, TM_DEBUG_ANNEX1 = 29,
        TM_DEBUG_HINT_AUDIT = 30, TM_DEBUG_SUB_COMPACTIONS = 31, TM_DEBUG_DISPATCH_ONE = 32,
-       TM_DEBUG_DISPATCH_GRID = 33, TM_DEBUG_DP1_MAX = 34, TM_DEBUG_PUBLISH_ONE = 35, TM_DEBUG_PUBLISH_GRID = 36 };
+       TM_DEBUG_DISPATCH_GRID = 33, TM_DEBUG_DP1_MAX = 34, TM_DEBUG_PUBLISH_ONE = 35, TM_DEBUG_PUBLISH_GRID = 36,
+       TM_DEBUG_GROUP_TILE = 37, TM_DEBUG_GROUP_PASSES_RUN = 38, TM_DEBUG_GROUP_PASSES_SKIPPED = 39,
+       TM_DEBUG_GROUP_GRID = 40 };
 int tm_debug_set(tm_index *h, uint32_t key, uint64_t value);
 int tm_debug_get(tm_index *h, uint32_t key, uint64_t *value);
 

@@ -48,6 +48,20 @@ interleaved), one JSON line per batch size with three legs:
 (a)'s and (c)'s outputs are compared first (they must be identical); the line
 also says which fan-out (c) took (TM_DEBUG_ROUTE_ONE / _GRID).
 
+--group: deliveries grouped by subscriber (nothing of the first part runs, no
+index): 1M synthetic deliveries whose subscriber ids come from 1,000 and from
+1M pids, uniform and skewed (one pid holding half); tm_group_subs_dev against
+the torch composition on the same device tensors -- torch.sort(stable=True),
+unique_consecutive with counts, cumsum, the two gathers -- outputs compared
+first (identical), then interleaved under HIP events; one JSON line per input
+with the digit passes the call ran and skipped.  --small --group: the --small
+index with a subscriber table of dense ids and one fan-in consumer;
+tm_deliver_batch beside tm_dispatch_batch, host to host and interleaved, at 64
+/ 1,024 / 4,096 topics (--sizes), tm_deliver_batch's outputs checked against
+tm_dispatch_batch's grouped on the host; the grouping's added time is
+deliver_minus_dispatch_ms.  With a library from before tm_deliver_batch the
+dispatch leg runs alone.
+
 --aggre: aggre/1 on the device (nothing of the first part runs).  The batch is
 matched as pairs and fanned out with tm_fanout_dev_pairs over a destination
 table that puts a share p of the values on destination 0 (the local node) and
@@ -709,6 +723,9 @@ def small_batches(a, sizes=(64, 1024, 4096, 16384), n_dests=16, warmup=20, reps=
     ix.sync(None)
     P = _native._ptr
     lib, h = ix._lib, ix._h
+    if a.group:
+        small_group(a, ix, len(fs), nvals, sizes if a.sizes else (64, 1024, 4096), n_dests, warmup, reps)
+        return
     if a.share:
         small_share(a, ix, len(fs), nvals, sizes, n_dests, warmup, reps)
         return
@@ -888,6 +905,139 @@ def small_dispatch(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=0):
                 ix.host_free(x)
 
 
+def torch_group(torch, t, v, s):
+    """the grouping as a torch composition on the same device tensors (ids below 2^31: int32 order is u32 order)"""
+    ss, perm = torch.sort(s, stable=True)
+    gs, cnt = torch.unique_consecutive(ss, return_counts=True)
+    goff = torch.zeros(len(gs) + 1, dtype=torch.int64, device=s.device)
+    goff[1:] = torch.cumsum(cnt, 0)
+    return t[perm], v[perm], ss, gs, goff
+
+
+def group_legs(torch, a, T=1_000_000):
+    """--group: tm_group_subs_dev against the torch composition (stable sort, unique_consecutive, gathers),
+    interleaved, on T synthetic deliveries whose subscribers come from 1,000 / 1M pids, uniform / one pid holding half"""
+    dev = torch.device("cuda")
+    ix = _native.Index()
+    s = torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(7)
+    RUN, SKIP = _native.TM_DEBUG_GROUP_PASSES_RUN, _native.TM_DEBUG_GROUP_PASSES_SKIPPED
+    for pids in (1_000, 1_000_000):
+        for shape in ("uniform", "skewed"):
+            sub = rng.integers(0, pids, T, dtype=np.int64)
+            if shape == "skewed":
+                sub[rng.random(T) < 0.5] = pids // 3
+            d_s = torch.from_numpy(sub.astype(np.int32)).to(dev)
+            d_t = torch.from_numpy(np.sort(rng.integers(0, T // 4, T)).astype(np.int32)).to(dev)
+            d_v = torch.from_numpy(rng.integers(0, 1 << 20, T).astype(np.int32)).to(dev)
+            d_head = torch.tensor([T, T], dtype=torch.int64, device=dev)
+            o_t, o_v, o_s = (torch.zeros(T, dtype=torch.int32, device=dev) for _ in range(3))
+            o_gsub = torch.zeros(T, dtype=torch.int32, device=dev)
+            o_goff = torch.zeros(T + 1, dtype=torch.int64, device=dev)
+            o_ghead = torch.zeros(2, dtype=torch.int64, device=dev)
+
+            def hip():
+                ix.group_subs_dev(d_head.data_ptr(), d_t.data_ptr(), d_v.data_ptr(), d_s.data_ptr(), T, o_ghead.data_ptr(),
+                                  o_gsub.data_ptr(), o_goff.data_ptr(), T, o_t.data_ptr(), o_v.data_ptr(), o_s.data_ptr(),
+                                  stream=s)
+
+            def tor():
+                return torch_group(torch, d_t, d_v, d_s)
+
+            torch.cuda.synchronize()
+            p0 = (ix.debug_get(RUN), ix.debug_get(SKIP))
+            hip()
+            r_t, r_v, r_s, r_gs, r_goff = tor()
+            torch.cuda.synchronize()
+            passes = (ix.debug_get(RUN) - p0[0], ix.debug_get(SKIP) - p0[1])
+            G = int(o_ghead[0])
+            assert G == len(r_gs) and int(o_ghead[1]) == T and torch.equal(o_t, r_t) and torch.equal(o_v, r_v) and \
+                torch.equal(o_s, r_s) and torch.equal(o_gsub[:G], r_gs) and torch.equal(o_goff[:G + 1], r_goff), \
+                f"{pids} pids, {shape}: the two paths differ"
+            del r_t, r_v, r_s, r_gs, r_goff
+            t_hip, t_tor = timed_pair(torch, hip, tor, a.warmup, a.reps)
+            h, t = stats(t_hip), stats(t_tor)
+            nbytes = T * (4 + passes[0] * 20 + 8 + 28)   # pre, per pass run hist + scatter, heads, emit
+            print(json.dumps({"tool": "fanout_bench", "kind": "group", "deliveries": T, "pids": pids, "shape": shape,
+                              "groups": G, "passes_run": passes[0], "passes_skipped": passes[1], "reps": a.reps,
+                              "hip": h, "torch": t, "torch_over_hip": round(t["median_ms"] / h["median_ms"], 2),
+                              "algorithmic_bytes": nbytes,
+                              "hip_algorithmic_GBps": round(nbytes / (h["median_ms"] * 1e-3) / 1e9, 1),
+                              "identical": True}), flush=True)
+
+
+def small_group(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=0):
+    """--small --group: tm_deliver_batch beside tm_dispatch_batch, host to host, interleaved"""
+    import time
+    P = _native._ptr
+    lib, h = ix._lib, ix._h
+    has = hasattr(lib, "tm_deliver_batch")   # (a library from before it: the dispatch leg alone)
+    flags = _native.TM_ROUTE_AGGRE if a.aggre else 0
+    rng = np.random.default_rng(7)
+    cnt = rng.integers(a.subs[0], a.subs[1] + 1, nvals)
+    loffs = np.zeros(nvals + 1, np.uint64)
+    loffs[1:] = np.cumsum(cnt)
+    subs = rng.integers(0, 100_000, int(loffs[-1]), dtype=np.int64).astype(np.uint32)   # interned, dense pids
+    subs[rng.random(len(subs)) < 0.3] = 7                                              # and one fan-in consumer
+    assert lib.tm_set_subscribers(h, nvals, P(np.arange(nvals, dtype=np.uint32)), P(loffs), P(subs)) == 0
+    for n in sizes:
+        tp = wl.topics(3, a.filters, n)
+        nb = int(tp.offs[-1])
+        blob, offs64 = ix.host_array(nb + 16, np.uint8), ix.host_array(n + 1, np.uint64)
+        blob[:nb] = tp.blob[:nb]
+        offs64[:] = tp.offs
+        err = np.zeros(n, np.uint8)
+        cap = 16 * n + 1024
+        d64, head, ghead = (np.zeros(k, np.uint64) for k in (n_dests + 2, 2, 2))
+        rc = lib.tm_dispatch_batch(h, n, P(blob), P(offs64), n_dests, local, flags, P(d64), None, None, 0, P(head),
+                                   None, None, None, 0, P(err))
+        assert rc in (0, _native.TM_ECAP)
+        T = int(head[1])
+        dcap = T + 1024
+        ra, rb = ((np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)) for _ in range(2))
+        da, db = (tuple(np.zeros(dcap, np.uint32) for _ in range(3)) for _ in range(2))
+        gsub, goff = np.zeros(dcap, np.uint32), np.zeros(dcap + 1, np.uint64)
+
+        def leg_d():
+            return lib.tm_dispatch_batch(h, n, P(blob), P(offs64), n_dests, local, flags, P(d64), P(ra[0]), P(ra[1]), cap,
+                                         P(head), P(da[0]), P(da[1]), P(da[2]), dcap, P(err))
+
+        def leg_g():
+            return lib.tm_deliver_batch(h, n, P(blob), P(offs64), n_dests, local, flags, P(d64), P(rb[0]), P(rb[1]), cap,
+                                        P(head), P(db[0]), P(db[1]), P(db[2]), dcap, P(ghead), P(gsub), P(goff), dcap, P(err))
+
+        assert leg_d() == 0, "the dispatch leg failed (or cap too small)"
+        legs = [("dispatch_batch", leg_d)]
+        G = None
+        if has:
+            assert leg_g() == 0
+            G = int(ghead[0])
+            p = np.argsort(da[2][:T], kind="stable")
+            gs, c = np.unique(da[2][:T], return_counts=True)
+            assert int(ghead[1]) == T and all(np.array_equal(x[:T][p], y[:T]) for x, y in zip(da, db)) and \
+                np.array_equal(gsub[:G], gs) and np.array_equal(goff[:G + 1], np.concatenate([[0], np.cumsum(c)])), \
+                f"n {n}: tm_deliver_batch differs from tm_dispatch_batch grouped on the host"
+            legs.append(("deliver_batch", leg_g))
+        ms = {k: [] for k, _ in legs}
+        for r in range(warmup + reps):
+            for k, f in legs:
+                t0 = time.perf_counter_ns()
+                f()
+                t1 = time.perf_counter_ns()
+                if r >= warmup:
+                    ms[k].append((t1 - t0) * 1e-6)
+        st = {k: dict(stats(v), p50_ms=round(float(np.median(v)), 4), p99_ms=round(float(np.percentile(v, 99)), 4))
+              for k, v in ms.items()}
+        line = {"tool": "fanout_bench", "kind": "small_group", "filters": fs_len, "topics": n, "entries": int(d64[n_dests + 1]),
+                "n_dests": n_dests, "subs": list(a.subs), "aggre": bool(a.aggre), "deliveries": T, "groups": G,
+                "warmup": warmup, "reps": reps, **st, "identical": True if has else None}
+        if has:
+            line["deliver_minus_dispatch_ms"] = round(st["deliver_batch"]["p50_ms"] - st["dispatch_batch"]["p50_ms"], 4)
+        print(json.dumps(line), flush=True)
+        for x in (blob, offs64):
+            ix.host_free(x)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--filters", type=int, default=1_000_000)
@@ -902,6 +1052,9 @@ def main():
     p.add_argument("--share", action="store_true",
                    help="the shared-subscription pick: tm_share_pick_dev vs the torch composition; with --small: "
                         "tm_publish_batch beside tm_dispatch_batch, host to host")
+    p.add_argument("--group", action="store_true",
+                   help="deliveries grouped by subscriber: tm_group_subs_dev vs the torch composition at 1M deliveries; "
+                        "with --small: tm_deliver_batch beside tm_dispatch_batch, host to host")
     p.add_argument("--dispatch-leg-only", action="store_true",
                    help="--small --share: time tm_dispatch_batch alone, as a library without tm_publish_batch is timed")
     p.add_argument("--sizes", type=int, nargs="+", default=None, help="--small: the batch sizes")
@@ -915,6 +1068,9 @@ def main():
         sys.exit("fanout_bench: no HIP device (this measurement has no CPU form)")
     if a.small:
         small_batches(a, **({"sizes": tuple(a.sizes)} if a.sizes else {}))
+        return
+    if a.group:
+        group_legs(torch, a)
         return
     dev = torch.device("cuda")
     fs = wl.filters(3, a.filters)
