@@ -15,7 +15,7 @@ void tmn_pool_init(tmn_pool *p, tm_index *h) {
 static void set_free(tm_index *h, tmn_set *s) {
     tmn_buf *all[] = {&s->blob, &s->offs, &s->hit, &s->vals, &s->err, &s->uniq, &s->offs64,
                       &s->rdoff, &s->rtopic, &s->dhead, &s->dtopic, &s->dvalue, &s->dsub,
-                      &s->skc, &s->skt, &s->smember};
+                      &s->skc, &s->skt, &s->smember, &s->ghead, &s->gsub, &s->goff};
     for (unsigned i = 0; i < sizeof all / sizeof all[0]; i++)
         if (all[i]->p) tm_host_free(h, all[i]->p);
     free(s);

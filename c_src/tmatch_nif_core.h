@@ -37,11 +37,15 @@ typedef struct tmn_set {         /* one caller's batch buffers (tm_host_alloc: t
                                                     allocated by its first call only */
     uint64_t deliveries;                         /* T of the set's last tmn_dispatch */
     uint32_t dispatched;                         /* that call succeeded: tmn_deliveries has something to read
-                                                    (2: it was a tmn_publish, tmn_picks has too) */
+                                                    (2: it was a tmn_publish, tmn_picks has too; 3: a tmn_deliver,
+                                                    the deliveries are grouped and tmn_groups has something) */
     tmn_buf skc, skt, smember;                   /* tmn_publish (tmatch_nif_share.h): the key words per topic, the picked
                                                     members (u32); allocated by tmn_share_keys / its first call only */
     uint32_t key_n, key_mask;                    /* tmn_share_keys: for how many topics, which arrays (1 clientid, 2 topic) */
     uint64_t picks;                              /* K of the set's last tmn_publish */
+    tmn_buf ghead, gsub, goff;                   /* tmn_deliver (tmatch_nif_deliver.h): [G, W] (u64), the groups' subscribers
+                                                    and offsets (u32); allocated by its first call only */
+    uint64_t groups;                             /* G of the set's last tmn_deliver */
     uint32_t in_flags;           /* the pool's input placement (tmn_pool.in_flags) */
     uint64_t reruns;             /* batches rerun after TM_ECAP (diagnostics) */
     struct tmn_set *next;

@@ -32,7 +32,7 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_route_batch32_ex", "tm_set_subscribers", "tm_dispatch_dev", "tm_dispatch_batch",
            "tm_dispatch_batch32", "tm_set_share_slots", "tm_set_share_members", "tm_share_state_set",
            "tm_share_state_get", "tm_share_pick_dev", "tm_publish_batch", "tm_publish_batch32",
-           "tm_group_subs_dev", "tm_deliver_batch")
+           "tm_group_subs_dev", "tm_deliver_batch", "tm_deliver_batch32")
 TM_ALLOC_VRAM = 1
 TM_ROUTE_AGGRE = 1          # tm_route_batch_ex / tm_route_batch32_ex: aggre/1 applied to the buckets
 NO_FILTER = 0xFFFFFFFF      # tm_set_route_filters: no filter known (equal to nothing)
@@ -64,6 +64,9 @@ TM_DEBUG_PUBLISH_ONE, TM_DEBUG_PUBLISH_GRID = 35, 36   # (get only) publish_batc
 # (get only) keys a block of group_subs_dev ranks per pass at a time; the digit passes its calls ran / skipped
 TM_DEBUG_GROUP_TILE, TM_DEBUG_GROUP_PASSES_RUN, TM_DEBUG_GROUP_PASSES_SKIPPED = 37, 38, 39
 TM_DEBUG_GROUP_GRID = 40    # (get only) the blocks of group_subs_dev's fixed grid
+TM_DEBUG_DELIVER_ONE, TM_DEBUG_DELIVER_GRID = 41, 42   # (get only) deliver_batch32 calls per grouping leg
+TM_DEBUG_GS1_MAX = 43       # deliveries the one-workgroup grouping takes itself (clamped to GS1_DELIVERIES)
+GS1_DELIVERIES = 16384
 MAX_DESTS = 65536           # tm_fanout_dev / tm_route_batch: n_dests is 1 .. MAX_DESTS
 
 
@@ -166,6 +169,8 @@ def load_library(path: Path | None = None):
         "tm_publish_batch32": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u32, vp,
                                      vp]),
         "tm_group_subs_dev": (i32, [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp]),
+        "tm_deliver_batch32": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, u64,
+                                     vp]),
         "tm_deliver_batch": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, u64,
                                    vp]),
         "tm_debug_set": (i32, [vp, u32, u64]),
@@ -705,6 +710,37 @@ class Index:
                                                   cap, _ptr(head), _ptr(dt), _ptr(dv), _ptr(ds), dcap, _ptr(err)))
         total, T = int(doff[n_dests + 1]), int(head[1])
         return (doff[: n_dests + 2], topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T])
+
+    def deliver_batch32(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, local_dest: int, out,
+                        cap: int | None = None, dcap: int | None = None, gcap: int | None = None, aggre: bool = False):
+        """tm_deliver_batch32: deliver_batch with u32 topic offsets in and u32
+        bucket and group offsets out.  out = dispatch_batch32's eight arrays,
+        then (ghead u64[2], gsub u32[gcap], goff u32[gcap + 1]) ->
+        (dispatch_batch32's two tuples, the deliveries GROUPED by subscriber,
+        (gsub[:G], goff[:G + 1])) as views; in place (no staging, one
+        synchronisation) when every array comes from host_array() and the batch
+        is a micro-batch (include/tmatch.h).  gcap: use only that many groups
+        of gsub / goff (default: all that both hold).  Raises TmError(TM_ECAP)
+        when something does not fit: dest_offsets[n_dests+1], head[1] and
+        ghead[0] size the retry."""
+        n = len(offs) - 1
+        if len(out) != 11:
+            raise ValueError("deliver_batch32: out is dispatch_batch32's eight arrays, then ghead, gsub and goff")
+        doff, topic, vals, err, head, dt, dv, ds, ghead, gsub, goff = out
+        cap, dcap = self._out32("deliver_batch32", offs, n_dests, out[:8], cap=cap, dcap=dcap)
+        if ghead.dtype != np.uint64 or len(ghead) < 2 or gsub.dtype != np.uint32 or goff.dtype != np.uint32 or len(goff) < 1:
+            raise ValueError("deliver_batch32: ghead u64[2], gsub u32[gcap] and goff u32[gcap + 1] expected")
+        groom = min(len(gsub), len(goff) - 1)
+        gcap = groom if gcap is None else gcap
+        if gcap < 0 or gcap > groom:
+            raise ValueError("deliver_batch32: gcap exceeds the group arrays")
+        self._check(self._lib.tm_deliver_batch32(self._h, n, _ptr(blob), _ptr(offs), n_dests, local_dest,
+                                                 TM_ROUTE_AGGRE if aggre else 0, _ptr(doff), _ptr(topic), _ptr(vals), cap,
+                                                 _ptr(head), _ptr(dt), _ptr(dv), _ptr(ds), dcap, _ptr(ghead), _ptr(gsub),
+                                                 _ptr(goff), gcap, _ptr(err)))
+        total, T, G = int(doff[n_dests + 1]), int(head[1]), int(ghead[0])
+        return (doff[: n_dests + 2], topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T]), \
+            (gsub[:G], goff[: G + 1])
 
     # ---- shared-subscription pick (include/tmatch.h "Shared-subscription pick on the device")
     def set_share_slots(self, values, slots):

@@ -459,6 +459,31 @@ hipError_t launch_group_subs(const FanoutScratch &fs, const uint64_t *head, cons
                              const uint32_t *in_value, const uint32_t *in_sub, uint64_t cap, uint64_t *ghead,
                              uint32_t *out_gsub, uint64_t *out_goff, uint64_t gcap, uint32_t *out_topic,
                              uint32_t *out_value, uint32_t *out_sub, uint32_t *out_perm, hipStream_t s);
+// A micro-batch's grouping in ONE launch of ONE workgroup (k_gs_one;
+// tm_deliver_batch32), queued behind launch_dispatch_one, which is then given
+// the lane's delivery arrays (in_topic / in_value / in_sub, GS1_DELIVERIES
+// words each), `head` (two u64 in device memory) for its out_head, and
+// min(dp1_max, GS1_DELIVERIES) for its dp1_max.  status_in: the status block
+// launch_dispatch_one itself was given (device memory).  With FO1_DONE there
+// the kernel passes head = [M, T] on to out_head and, when T <= dp1_max (the
+// dispatch expanded), writes launch_group_subs' results over the first W =
+// min(T, dcap) deliveries: the grouped arrays, out_ghead = [G, W], the first
+// min(G, gcap) subscribers and offsets with the end entry -- out_goff as u32.
+// Every output may be mapped host memory, none is read.  status (may be
+// mapped host memory): [GS1_ST_STATE] = GS1_GROUPED with the digit passes run
+// and skipped and G beside it, or GS1_SKIPPED and nothing else (the caller
+// takes the grid kernels).  The kernel moves no state and keeps none: a run queued again
+// writes the same outputs again.  head, out_head and out_ghead must be 8-byte
+// aligned.  No scratch: a stable sort of 16-bit positions inside LDS, which
+// is why one workgroup stops at 16384 deliveries and not at DP1_DELIVERIES.
+constexpr uint32_t GS1_DELIVERIES = 16384;
+enum { GS1_ST_STATE = 0, GS1_ST_RUN = 1, GS1_ST_SKIPPED = 2, GS1_ST_G = 3, GS1_ST_WORDS = 4 };
+enum : uint32_t { GS1_GROUPED = 1, GS1_SKIPPED = 2 };
+hipError_t launch_group_one(const uint32_t *status_in, const uint64_t *head, const uint32_t *in_topic,
+                            const uint32_t *in_value, const uint32_t *in_sub, uint64_t dcap, uint64_t dp1_max,
+                            uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
+                            uint64_t *out_ghead, uint32_t *out_gsub, uint32_t *out_goff, uint64_t gcap, uint32_t *status,
+                            hipStream_t s);
 // delta upload: run i copies runs[i].n u32 words from data + runs[i].src to
 // word (dst & PATCH_OFF) of table (dst >> 48), whose device address on the
 // replica being patched is bases.b[table] (the same runs patch every replica)

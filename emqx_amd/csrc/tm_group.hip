@@ -381,7 +381,227 @@ __global__ __launch_bounds__(GS_BLOCK) void k_gs_emit(const uint64_t *head, uint
     }
 }
 
+// ---- a micro-batch's grouping in ONE workgroup (tm_deliver_batch32), queued
+// behind k_dp_one, which under a grouping request writes its deliveries and
+// its head to the lane (in_t / in_v / in_s, head) and not to the caller.
+//   gate   st_in is the status block k_dp_one itself read (k_fo_one's, under
+//          aggre k_ag_one's, in device memory); with FO1_DONE there k_dp_one
+//          left head = [M, T], which goes on to the caller's out_head, and
+//          expanded the deliveries exactly when T <= dp1_max (the same value
+//          both kernels are given, at most GS1_DELIVERIES).  Anything else:
+//          GS1_SKIPPED and nothing more, the host takes the grid kernels.
+//          The run that queued the kernel may be run again (a value scratch
+//          that grew, a look-back retry).  k_sh_one gates itself against that
+//          because it moves the slots' state; the grouping moves no state, so
+//          a second run would simply write the same outputs again.  (Today a
+//          run that is queued again never gets as far as grouping: the lane's
+//          first value scratch holds 65,536 values or more, a total above it
+//          is more than FO1_ENTRIES entries, so both runs end FO1_TOO_LARGE
+//          and the kernel writes GS1_SKIPPED twice; the pairs walk has no
+//          look-back to retry.)
+//   sort   the W = min(T, dcap) subscriber ids in s_key, their positions as
+//          16 bits in s_ix[0]; a block-wide AND and OR of the keys tell which
+//          of the four digits every key agrees on (skipped: the grid form's
+//          rule, k_gs_plan); per digit left a stable LSD pass between the two
+//          index arrays: a row of 256 bins per wave, the rows scanned over the
+//          waves and then the bins, and a scatter in which the lanes of a step
+//          with the same digit rank themselves by a peer mask.
+//          This is k_sh_one's pass (tm_share.hip).  It is a copy, not a shared
+//          helper: lifting it would change k_sh_one's code, whose register
+//          allocation (and zero scratch) was measured as it stands, and the
+//          pass here runs on whole keys and a digit chosen at run time.
+//   heads  position p is a head when its key differs from its predecessor's;
+//          a ballot and popcount per step, the counts scanned over the waves;
+//          head g < gcap gives out_gsub[g], g <= gcap out_goff[g].
+//   out    out_ds[p] from LDS, out_dt[p] / out_dv[p] gathered from the lane's
+//          arrays through the position; consecutive threads write consecutive
+//          words of mapped host memory that is never read.
+// status (mapped host memory): GS1_ST_* (tm_dev.h).  LDS: 64 KiB keys + 2 x 32
+// KiB indices + 16 KiB bins + 88 B.
+constexpr uint32_t GS1_WAVES = FO1_BLOCK / 64;
+constexpr uint32_t GS1_STEPS = GS1_DELIVERIES / FO1_BLOCK;   // 64-position steps of a wave, at most
+static_assert(GS1_DELIVERIES <= 0x10000u, "k_gs_one: positions are staged as 16 bits");
+static_assert(GS1_DELIVERIES % FO1_BLOCK == 0 && GS_BINS <= FO1_BLOCK && GS_BINS % 64 == 0,
+              "k_gs_one: whole steps per wave, one thread per bin");
+
+__device__ __forceinline__ void gs1_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(FO1_BLOCK) void k_gs_one(const uint32_t *__restrict__ st_in, const uint64_t *__restrict__ head,
+                                                      const uint32_t *__restrict__ in_t, const uint32_t *__restrict__ in_v,
+                                                      const uint32_t *__restrict__ in_s, uint64_t dcap, uint64_t dp1_max,
+                                                      uint64_t *__restrict__ out_head, uint32_t *__restrict__ out_dt,
+                                                      uint32_t *__restrict__ out_dv, uint32_t *__restrict__ out_ds,
+                                                      uint64_t *__restrict__ out_ghead, uint32_t *__restrict__ out_gsub,
+                                                      uint32_t *__restrict__ out_goff, uint64_t gcap,
+                                                      uint32_t *__restrict__ status) {
+    __shared__ uint32_t s_key[GS1_DELIVERIES];
+    __shared__ __attribute__((aligned(4))) uint16_t s_ix[2][GS1_DELIVERIES];
+    __shared__ uint32_t s_h[GS1_WAVES * GS_BINS];
+    __shared__ uint32_t s_wt[GS1_WAVES];
+    __shared__ uint32_t s_bw[GS_BINS / 64];
+    __shared__ uint32_t s_red[2];   // the AND and the OR of the keys
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (st_in[FO1_ST_STATE] != FO1_DONE) {   // (block-uniform) k_dp_one wrote nothing: the head is an older run's
+        if (tid == 0) status[GS1_ST_STATE] = GS1_SKIPPED;
+        return;
+    }
+    const uint64_t M = head[0], T = head[1];
+    if (tid == 0) {
+        out_head[0] = M;
+        out_head[1] = T;
+    }
+    if (T > dp1_max || T > GS1_DELIVERIES) {   // (block-uniform) DP1_TOO_LARGE: no deliveries on the lane
+        if (tid == 0) status[GS1_ST_STATE] = GS1_SKIPPED;
+        return;
+    }
+    const uint32_t W = T < dcap ? (uint32_t)T : (uint32_t)dcap;   // (<= GS1_DELIVERIES)
+    if (tid == 0) {
+        s_red[0] = 0xFFFFFFFFu;
+        s_red[1] = 0;
+    }
+    __syncthreads();
+    // ---- the keys and the positions 0, 1, ..
+    uint32_t k_and = 0xFFFFFFFFu, k_or = 0;
+    for (uint32_t i = tid; i < W; i += FO1_BLOCK) {
+        const uint32_t key = in_s[i];
+        s_key[i] = key;
+        s_ix[0][i] = (uint16_t)i;
+        k_and &= key;
+        k_or |= key;
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {
+        k_and &= __shfl_xor(k_and, d, 64);
+        k_or |= __shfl_xor(k_or, d, 64);
+    }
+    if (lane == 0) {
+        atomicAnd(&s_red[0], k_and);
+        atomicOr(&s_red[1], k_or);
+    }
+    __syncthreads();
+    const uint32_t diff = W ? s_red[0] ^ s_red[1] : 0u;   // bits on which two keys differ (no key: none)
+    // ---- sorted by key.  Wave w owns the positions [w * D, (w + 1) * D) of [0, W)
+    const uint32_t D = ((W + GS1_WAVES - 1) / GS1_WAVES + 63) & ~63u;   // (<= 64 * GS1_STEPS)
+    const uint32_t d0 = wv * D < W ? wv * D : W, d1 = d0 + D < W ? d0 + D : W;
+    uint32_t *my_h = s_h + wv * GS_BINS;
+    uint32_t cur = 0, run = 0;
+    for (uint32_t pass = 0, shift = 0; pass < GS_PASSES; pass++, shift += 8) {   // (block-uniform)
+        if (!((diff >> shift) & (GS_BINS - 1))) continue;                         // every key in one bin: the identity
+        run++;
+        const uint16_t *src = s_ix[cur];
+        uint16_t *dst_ix = s_ix[cur ^ 1];
+        for (uint32_t i = tid; i < GS1_WAVES * GS_BINS; i += FO1_BLOCK) s_h[i] = 0;
+        __syncthreads();
+        for (uint32_t p0 = d0; p0 < d1; p0 += 64) {
+            const uint32_t p = p0 + lane;
+            if (p < d1) atomicAdd(&my_h[(s_key[src[p]] >> shift) & (GS_BINS - 1)], 1u);
+        }
+        __syncthreads();
+        // bin b: its counts' exclusive scan over the waves, then over the bins
+        uint32_t tot = 0;
+        if (tid < GS_BINS)
+            for (uint32_t q = 0; q < GS1_WAVES; q++) {
+                const uint32_t x = s_h[q * GS_BINS + tid];
+                s_h[q * GS_BINS + tid] = tot;
+                tot += x;
+            }
+        const uint32_t binc = gs_incl_scan32(tot, lane);
+        if (tid < GS_BINS && lane == 63) s_bw[wv] = binc;
+        __syncthreads();
+        if (tid < GS_BINS) {
+            uint32_t exc = binc - tot;
+            for (uint32_t q = 0; q < wv; q++) exc += s_bw[q];
+            for (uint32_t q = 0; q < GS1_WAVES; q++) s_h[q * GS_BINS + tid] += exc;
+        }
+        __syncthreads();
+        // the stable scatter: waves, steps and lanes are in position order
+        for (uint32_t p0 = d0; p0 < d1; p0 += 64) {   // (wave-uniform)
+            const uint32_t p = p0 + lane;
+            const bool ok = p < d1;
+            const uint32_t ix = ok ? src[p] : 0u;
+            const uint32_t d = ok ? (s_key[ix] >> shift) & (GS_BINS - 1) : 0u;
+            const uint64_t peers = gs_match(d, ok);
+            uint32_t dst = 0;
+            if (ok) dst = my_h[d] + gs_below(peers, lane);
+            gs1_wave_sync();
+            if (ok && (peers >> lane) == 1ull) my_h[d] += (uint32_t)__popcll(peers);   // (the run's last lane)
+            gs1_wave_sync();
+            if (ok && dst < W) dst_ix[dst] = (uint16_t)ix;   // (dst < W always: the histogram saw these keys)
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    // ---- heads.  I: the positions by (key, position)
+    const uint16_t *I = s_ix[cur];
+    uint32_t n_heads = 0;
+    for (uint32_t p0 = d0; p0 < d1; p0 += 64) {   // (wave-uniform)
+        const uint32_t p = p0 + lane;
+        const bool h = p < d1 && (p == 0 || s_key[I[p - 1]] != s_key[I[p]]);
+        n_heads += (uint32_t)__popcll(__ballot(h));
+    }
+    if (lane == 0) s_wt[wv] = n_heads;
+    __syncthreads();
+    uint32_t g0 = 0, G = 0;
+    for (uint32_t q = 0; q < GS1_WAVES; q++) {
+        if (q < wv) g0 += s_wt[q];
+        G += s_wt[q];
+    }
+    // ---- the groups and the payload
+#pragma unroll 4
+    for (uint32_t k = 0; k < GS1_STEPS; k++) {
+        if (k * 64 >= D) break;   // (block-uniform)
+        const uint32_t p = d0 + k * 64 + lane;
+        const bool ok = p < d1;
+        uint32_t pos = ok ? I[p] : 0u;
+        if (pos >= W) pos = 0;    // (never: I is a permutation of [0, W))
+        const uint32_t key = ok ? s_key[pos] : 0u;
+        const bool h = ok && (p == 0 || s_key[I[p - 1]] != key);
+        const uint64_t hm = __ballot(h);
+        if (h) {
+            const uint64_t g = (uint64_t)g0 + gs_below(hm, lane);
+            if (g < gcap) out_gsub[g] = key;
+            if (g <= gcap) out_goff[g] = p;   // (g == gcap < G: where the first group left out starts)
+        }
+        g0 += (uint32_t)__popcll(hm);
+        if (ok) {
+            out_dt[p] = in_t[pos];
+            out_dv[p] = in_v[pos];
+            out_ds[p] = key;
+        }
+    }
+    if (tid == 0) {
+        if (G <= gcap) out_goff[G] = W;
+        out_ghead[0] = G;
+        out_ghead[1] = W;
+        status[GS1_ST_RUN] = run;
+        status[GS1_ST_SKIPPED] = GS_PASSES - run;
+        status[GS1_ST_G] = G;
+        status[GS1_ST_STATE] = GS1_GROUPED;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_group_one(const uint32_t *status_in, const uint64_t *head, const uint32_t *in_topic,
+                            const uint32_t *in_value, const uint32_t *in_sub, uint64_t dcap, uint64_t dp1_max,
+                            uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
+                            uint64_t *out_ghead, uint32_t *out_gsub, uint32_t *out_goff, uint64_t gcap, uint32_t *status,
+                            hipStream_t s) {
+    if (!status_in || !head || !out_head || !out_ghead || !out_goff || !status ||
+        (((uintptr_t)head | (uintptr_t)out_head | (uintptr_t)out_ghead) & 7))
+        return hipErrorInvalidValue;
+    if (dcap > GS1_DELIVERIES) dcap = GS1_DELIVERIES;
+    if (dp1_max > GS1_DELIVERIES) dp1_max = GS1_DELIVERIES;
+    if ((dcap && (!in_topic || !in_value || !in_sub || !out_dtopic || !out_dvalue || !out_dsub)) || (gcap && !out_gsub))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_gs_one, dim3(1), dim3(FO1_BLOCK), 0, s, status_in, head, in_topic, in_value, in_sub, dcap, dp1_max,
+                       out_head, out_dtopic, out_dvalue, out_dsub, out_ghead, out_gsub, out_goff, gcap, status);
+    return hipGetLastError();
+}
 
 hipError_t launch_group_subs(const FanoutScratch &fs, const uint64_t *head, const uint32_t *in_topic,
                              const uint32_t *in_value, const uint32_t *in_sub, uint64_t cap, uint64_t *ghead,

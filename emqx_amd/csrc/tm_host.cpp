@@ -125,12 +125,16 @@ struct Lane {
     // tm_route_batch32 in place: the match's pairs (its values go to d_vals) and
     // the one-launch kernels' status words (mapped pinned: DP1_ST_WORDS, then
     // the [M, T] of a tm_dispatch_batch32 the grid kernels finished, then
-    // k_sh_one's SH1_ST_WORDS under tm_publish_batch32)
+    // k_sh_one's SH1_ST_WORDS under tm_publish_batch32, then k_gs_one's
+    // GS1_ST_WORDS and the [M, T, G, W] of a tm_deliver_batch32 the grid
+    // kernels finished)
     uint32_t *d_pr = nullptr; uint64_t d_pr_cap = 0;
     uint32_t *fo1_h = nullptr, *fo1_d = nullptr;
     // TM_ROUTE_AGGRE: the aggregated device results of the grid kernels, and the
     // one-launch fan-out's status words in device memory (k_ag_one passes them
-    // on; under tm_dispatch_batch32 into a second pair, which k_dp_one reads)
+    // on; under tm_dispatch_batch32 into a second pair, which k_dp_one reads;
+    // then, 8-byte aligned, the [M, T] k_dp_one leaves for k_gs_one under
+    // tm_deliver_batch32 and the [G, W] of the grid grouping: FO1S_WORDS)
     uint32_t *d_at = nullptr, *d_av = nullptr; uint64_t d_at_cap = 0, d_av_cap = 0;
     uint64_t *d_ao = nullptr; uint64_t d_ao_cap = 0;
     uint32_t *fo1_s = nullptr;
@@ -357,6 +361,10 @@ struct tm_index {
     // tm_publish_batch32 calls k_sh_one picked for / that the grid pick or the staged path finished
     std::atomic<uint64_t> publish_one{0}, publish_grid{0};
     uint64_t dp1_max = DP1_DELIVERIES;   // TM_DEBUG_DP1_MAX: deliveries k_dp_one expands itself
+    // tm_deliver_batch32 calls k_gs_one grouped / that the grid kernels or the staged path finished; the
+    // digit passes k_gs_one ran / skipped (TM_DEBUG_GROUP_PASSES_*: added to the grid form's)
+    std::atomic<uint64_t> deliver_one{0}, deliver_grid{0}, gs1_passes[2] = {};
+    uint64_t gs1_max = GS1_DELIVERIES;   // TM_DEBUG_GS1_MAX: deliveries k_gs_one groups itself
     // The host-batch combiner (small_combined): small in-place 32-bit batches
     // of concurrent callers queue here; up to cmb_leaders callers at a time
     // each take what is queued and run it as ONE k_walk_small launch
@@ -2168,7 +2176,7 @@ struct HostBatch {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 20u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 21u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 
@@ -3852,6 +3860,7 @@ struct RouteGroup {
     uint32_t *out_gsub;
     uint64_t *out_goff;
     uint64_t gcap;
+    uint32_t *out_goff32 = nullptr;   // tm_deliver_batch32: the caller's offsets, narrowed on the way out (out_goff null)
 };
 
 // room on the lane for `want` grouped deliveries and min(gcap, want) groups
@@ -3975,6 +3984,47 @@ static int route_fail(tm_index *ix, const RouteReq &rq, int code, const char *wh
     return fail(ix, code, std::string(rq.who) + ": " + what);
 }
 
+// What a grouping left on the lane (d_gt / d_gv / d_gs, d_gsub, d_goff), to
+// the caller (the lock is not held; the lane is still checked out): head = [M,
+// T, G, W] as the device left it, the first min(T, dcap) grouped deliveries,
+// the first min(G, gcap) subscribers, and their offsets with the end entry --
+// into out_goff, or narrowed into out_goff32 (tm_deliver_batch32) through a
+// per-thread buffer of min(G, gcap) + 1 words: sized from G, never from the
+// caller's capacities.  The caller's arrays are pageable memory or
+// tm_host_alloc buffers.
+static int copy_group_out(tm_index *ix, Lane &ln, const RouteReq &rq, const uint64_t head[4]) {
+    const hipStream_t s = ln.s;
+    const RouteDispatch *dp = rq.dp;
+    const RouteGroup *gp = rq.gp;
+    const uint64_t dcap = std::min<uint64_t>(dp->dcap, 0xFFFFFFFFull);
+    const uint64_t keep = std::min(head[1], dcap), gkeep = std::min(head[2], gp->gcap);
+    static thread_local std::vector<uint64_t> wide;
+    uint64_t *goff = gp->out_goff;
+    if (!goff) {
+        try {
+            wide.resize(gkeep + 1);
+        } catch (const std::bad_alloc &) {
+            return route_fail(ix, rq, TM_ENOMEM, "out of host memory");
+        }
+        goff = wide.data();
+    }
+    dp->out_head[0] = head[0];
+    dp->out_head[1] = head[1];
+    gp->out_ghead[0] = head[2];
+    gp->out_ghead[1] = head[3];
+    if (keep) {
+        HIPCHK(ix, hipMemcpyAsync(dp->out_topic, ln.d_gt, keep * 4, hipMemcpyDefault, s));
+        HIPCHK(ix, hipMemcpyAsync(dp->out_value, ln.d_gv, keep * 4, hipMemcpyDefault, s));
+        HIPCHK(ix, hipMemcpyAsync(dp->out_sub, ln.d_gs, keep * 4, hipMemcpyDefault, s));
+    }
+    if (gkeep) HIPCHK(ix, hipMemcpyAsync(gp->out_gsub, ln.d_gsub, gkeep * 4, hipMemcpyDefault, s));
+    HIPCHK(ix, hipMemcpyAsync(goff, ln.d_goff, (gkeep + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ix, hipStreamSynchronize(s));
+    if (!gp->out_goff)
+        for (uint64_t i = 0; i <= gkeep; i++) gp->out_goff32[i] = (uint32_t)goff[i];
+    return TM_OK;
+}
+
 // The family's argument checks, once per call, before anything is locked or
 // queued.  offsets: the topic offsets and out_dest_offsets are both there.
 // narrow: a 32-bit call, which may run in place -- out_err is required (the
@@ -3992,9 +4042,12 @@ static int route_check(tm_index *ix, const RouteReq &rq, bool offsets, bool narr
         (rq.cap && (!rq.out_topic || !rq.out_values || (rq.pk && !rq.pk->out_member))) ||
         (dp && (!dp->out_head || (dp->dcap && (!dp->out_topic || !dp->out_value || !dp->out_sub)))))
         return route_fail(ix, rq, TM_EINVAL, "null buffer");
-    if (rq.gp && (!dp || !rq.gp->out_ghead || !rq.gp->out_goff || (rq.gp->gcap && !rq.gp->out_gsub)))
+    if (rq.gp && (!dp || !rq.gp->out_ghead || !(narrow ? (const void *)rq.gp->out_goff32 : (const void *)rq.gp->out_goff) ||
+                  (rq.gp->gcap && !rq.gp->out_gsub)))
         return route_fail(ix, rq, TM_EINVAL, "null buffer");
     if (narrow && dp && ((uintptr_t)dp->out_head & 7)) return route_fail(ix, rq, TM_EINVAL, "out_head must be 8-byte aligned");
+    if (narrow && rq.gp && ((uintptr_t)rq.gp->out_ghead & 7))
+        return route_fail(ix, rq, TM_EINVAL, "out_ghead must be 8-byte aligned");
     if (rq.n >= 0xFFFFFFFFull) return route_fail(ix, rq, TM_EINVAL, "batch too large");
     return TM_OK;
 }
@@ -4115,23 +4168,20 @@ static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to
     if (rq.out_err && n) std::memcpy(rq.out_err, ln.pin_out + (n + 1) * 8, n);
     if (rq.pk && aggre && total <= cap)
         if (int prc = pick_after_run(ix, hb, rq, vcap, std::min(out_dest_offsets[n_dests + 1], cap))) return prc;
-    if (dp) {
+    if (gp) {
+        if (int grc = copy_group_out(ix, ln, rq, head)) return grc;
+        if (head[1] > dp->dcap || head[2] > gcap) rc = TM_ECAP;
+    } else if (dp) {
         dp->out_head[0] = head[0];
         dp->out_head[1] = head[1];
-        const uint64_t keep = std::min(head[1], dcap), gkeep = gp ? std::min(head[2], gcap) : 0;
+        const uint64_t keep = std::min(head[1], dcap);
         if (keep) {
-            HIPCHK(ix, hipMemcpyAsync(dp->out_topic, gp ? ln.d_gt : ln.d_dt, keep * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(ix, hipMemcpyAsync(dp->out_value, gp ? ln.d_gv : ln.d_dv, keep * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(ix, hipMemcpyAsync(dp->out_sub, gp ? ln.d_gs : ln.d_ds, keep * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipMemcpyAsync(dp->out_topic, ln.d_dt, keep * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipMemcpyAsync(dp->out_value, ln.d_dv, keep * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipMemcpyAsync(dp->out_sub, ln.d_ds, keep * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(ix, hipStreamSynchronize(s));
         }
-        if (gp) {
-            gp->out_ghead[0] = head[2];
-            gp->out_ghead[1] = head[3];
-            if (gkeep) HIPCHK(ix, hipMemcpyAsync(gp->out_gsub, ln.d_gsub, gkeep * 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(ix, hipMemcpyAsync(gp->out_goff, ln.d_goff, (gkeep + 1) * 8, hipMemcpyDeviceToHost, s));
-        }
-        if (keep || gp) HIPCHK(ix, hipStreamSynchronize(s));
-        if (head[1] > dp->dcap || (gp && head[2] > gcap)) rc = TM_ECAP;
+        if (head[1] > dp->dcap) rc = TM_ECAP;
     }
     return rc;
 }
@@ -4320,9 +4370,16 @@ int tm_match_batch32_pairs(tm_index *ix, uint64_t n, const uint8_t *tb, const ui
 constexpr int ROUTE32_OTHER = 1;   // (not a TM_ code)
 constexpr int DP1_GRID_HEAD = DP1_ST_WORDS;   // status word of the [M, T] a grid dispatch leaves (8-byte aligned)
 constexpr int SH1_HOST = DP1_GRID_HEAD + 4;   // k_sh_one's status words (its head 8-byte aligned)
-constexpr int DP1_HOST_WORDS = SH1_HOST + SH1_ST_WORDS;
+constexpr int GS1_HOST = SH1_HOST + SH1_ST_WORDS;        // k_gs_one's status words
+constexpr int GS1_GRID_HEAD = GS1_HOST + GS1_ST_WORDS;   // the [M, T, G, W] a grid dispatch and grouping leave
+constexpr int DP1_HOST_WORDS = GS1_GRID_HEAD + 8;
+// the lane's device words (Lane::fo1_s): the two status pairs, then k_dp_one's head under a grouping
+// request and the grid grouping's [G, W] behind it
+constexpr int FO1S_HEAD = 2 * FO1_ST_WORDS;
+constexpr int FO1S_WORDS = FO1S_HEAD + 8;
 static_assert(DP1_GRID_HEAD % 2 == 0, "the grid dispatch's head is two u64");
 static_assert((SH1_HOST + SH1_ST_HEAD) % 2 == 0, "the pick's head is two u64");
+static_assert(GS1_GRID_HEAD % 2 == 0 && FO1S_HEAD % 2 == 0, "the grouping's heads are u64");
 
 // The device addresses of one request's buffers.  An absent or empty optional
 // buffer is null (opt_dev); the delivery arrays, the head, out_member and the
@@ -4336,6 +4393,8 @@ struct Route32Dev {
     uint32_t *dtopic, *dvalue, *dsub;
     uint32_t *member;
     const uint32_t *kc, *kt;
+    uint64_t *ghead;
+    uint32_t *gsub, *goff;
 };
 
 // fills `v` (caller holds ix->mu: the list of tm_host_alloc buffers);
@@ -4344,6 +4403,7 @@ static bool route32_resolve(tm_index *ix, const RouteReq &rq, const uint32_t *to
                             uint32_t *out_dest_offsets, Route32Dev &v) {
     const RouteDispatch *dp = rq.dp;
     const RoutePick *pk = rq.pk;
+    const RouteGroup *gp = rq.gp;
     bool ok = rq.tb || !nbytes;
     const auto words = [&](const void *p, uint64_t k) { return reinterpret_cast<uint32_t *>(opt_dev(ix, p, k * 4, ok)); };
     v.bytes = opt_dev(ix, rq.tb, nbytes, ok);
@@ -4360,7 +4420,10 @@ static bool route32_resolve(tm_index *ix, const RouteReq &rq, const uint32_t *to
     v.member = pk ? words(pk->out_member, rq.cap) : nullptr;
     v.kc = pk ? words(pk->key_clientid, rq.n) : nullptr;
     v.kt = pk ? words(pk->key_topic, rq.n) : nullptr;
-    return ok && v.err && (!dp || v.head);
+    v.ghead = gp ? reinterpret_cast<uint64_t *>(pinned_dev(ix, gp->out_ghead, 16)) : nullptr;
+    v.gsub = gp ? words(gp->out_gsub, gp->gcap) : nullptr;
+    v.goff = gp ? reinterpret_cast<uint32_t *>(pinned_dev(ix, gp->out_goff32, (gp->gcap + 1) * 4)) : nullptr;
+    return ok && v.err && (!dp || v.head) && (!gp || (v.ghead && v.goff));
 }
 
 // room on the lane for one attempt with vcap values: the match's pairs and
@@ -4382,6 +4445,11 @@ static int route32_scratch(tm_index *ix, Lane &ln, const RouteReq &rq, uint64_t 
         if ((rc = grow_dev(ix, s, ln.d_av, ln.d_av_cap, FO1_ENTRIES))) return rc;
         if ((rc = grow_dev(ix, s, ln.d_ao, ln.d_ao_cap, nfo))) return rc;
     }
+    if (rq.gp) {   // k_dp_one's deliveries stay on the lane: k_gs_one writes the caller's
+        if ((rc = grow_dev(ix, s, ln.d_dt, ln.d_dt_cap, GS1_DELIVERIES))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_dv, ln.d_dv_cap, GS1_DELIVERIES))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_ds, ln.d_ds_cap, GS1_DELIVERIES))) return rc;
+    }
     return TM_OK;
 }
 
@@ -4395,7 +4463,11 @@ static int route32_scratch(tm_index *ix, Lane &ln, const RouteReq &rq, uint64_t 
 // snapshot and ONE more workgroup, k_sh_one, over k_ag_one's entries.  The run
 // may be run again (a value scratch that grows, a look-back retry), so
 // k_sh_one gates itself on the device (tm_dev.h launch_share_one) and reports
-// into the lane's status block.
+// into the lane's status block.  gp: k_dp_one is the same code with other
+// pointers -- its deliveries and its head go to the lane, it expands up to
+// min(dp1_max, gs1_max) deliveries -- and ONE more workgroup, k_gs_one, groups
+// them into the caller's buffers (tm_dev.h launch_group_one); it moves no
+// state, so a run queued again just writes again.
 static int route32_queue(tm_index *ix, Lane &ln, const RouteReq &rq, const Route32Dev &v, const DevIndex &d,
                          uint32_t tag, uint64_t vcap) {
     int rc;
@@ -4420,6 +4492,7 @@ static int route32_queue(tm_index *ix, Lane &ln, const RouteReq &rq, const Route
     if ((rc = dest_upload(ix, grp, s, dtab, dlen))) return rc;
     st[FO1_ST_STATE] = 0;   // (the lane's stream is idle: nothing else writes the words)
     st[SH1_HOST + SH1_ST_STATE] = 0;
+    st[GS1_HOST + GS1_ST_STATE] = 0;
     if (!aggre && !dp) {
         HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, v.fo, v.topic, v.value, cap,
                                      ln.fo1_d, s));
@@ -4444,6 +4517,16 @@ static int route32_queue(tm_index *ix, Lane &ln, const RouteReq &rq, const Route
     const uint32_t *span = nullptr, *pool = nullptr;
     uint64_t span_len = 0, pool_len = 0;
     if ((rc = subs_upload(ix, grp, s, span, span_len, pool, pool_len))) return rc;
+    if (const RouteGroup *gp = rq.gp) {
+        uint64_t *lhead = reinterpret_cast<uint64_t *>(ln.fo1_s + FO1S_HEAD);
+        const uint64_t ldcap = std::min<uint64_t>(v.dcap, GS1_DELIVERIES), lmax = std::min(ix->dp1_max, ix->gs1_max);
+        HIPCHK(ix, launch_dispatch_one(st_dev, lfo, ln.d_ft, ln.d_fv, lao, ln.d_at, ln.d_av, n_dests, dp->local_dest, span,
+                                       span_len, pool, pool_len, v.fo, v.topic, v.value, cap, lhead, ln.d_dt, ln.d_dv,
+                                       ln.d_ds, ldcap, lmax, ln.fo1_d, s));
+        HIPCHK(ix, launch_group_one(st_dev, lhead, ln.d_dt, ln.d_dv, ln.d_ds, ldcap, lmax, v.head, v.dtopic, v.dvalue,
+                                    v.dsub, v.ghead, v.gsub, v.goff, gp->gcap, ln.fo1_d + GS1_HOST, s));
+        return TM_OK;   // (no pick under a grouping: route_check)
+    }
     HIPCHK(ix, launch_dispatch_one(st_dev, lfo, ln.d_ft, ln.d_fv, lao, ln.d_at, ln.d_av, n_dests, dp->local_dest, span,
                                    span_len, pool, pool_len, v.fo, v.topic, v.value, cap, v.head, v.dtopic, v.dvalue,
                                    v.dsub, v.dcap, ix->dp1_max, ln.fo1_d, s));
@@ -4470,16 +4553,73 @@ static int route32_pick_status(tm_index *ix, Lane &ln, const RouteReq &rq, uint6
     return TM_OK;
 }
 
+// k_gs_one's status against the host's view of the run that stands: it grouped
+// exactly when k_dp_one expanded the deliveries (FO1_DONE)
+static int route32_group_status(tm_index *ix, Lane &ln, const RouteReq &rq, uint32_t state) {
+    const uint32_t gs = ln.fo1_h[GS1_HOST + GS1_ST_STATE];
+    if ((gs != GS1_GROUPED && gs != GS1_SKIPPED) || (gs == GS1_GROUPED) != (state == FO1_DONE))
+        return route_fail(ix, rq, TM_EDEVICE, "the grouping kernel and the host disagree on whether the dispatch expanded");
+    return TM_OK;
+}
+
 // ending 1, FO1_DONE: everything is in the caller's buffers
 static int route32_end_in_place(tm_index *ix, Lane &ln, const RouteReq &rq, uint64_t total) {
     if (!rq.dp) {
         ix->route_one++;
         return total > rq.cap ? TM_ECAP : TM_OK;
     }
-    ix->dispatch_one++;
     const volatile uint32_t *st = ln.fo1_h;
     const uint64_t T = (uint64_t)st[DP1_ST_T_HI] << 32 | st[DP1_ST_T_LO];
+    if (rq.gp) {
+        ix->deliver_one++;
+        ix->gs1_passes[0] += st[GS1_HOST + GS1_ST_RUN];
+        ix->gs1_passes[1] += st[GS1_HOST + GS1_ST_SKIPPED];
+        return total > rq.cap || T > rq.dp->dcap || st[GS1_HOST + GS1_ST_G] > rq.gp->gcap ? TM_ECAP : TM_OK;
+    }
+    ix->dispatch_one++;
     return total > rq.cap || T > rq.dp->dcap ? TM_ECAP : TM_OK;
+}
+
+// A grid ending under a grouping request (caller holds the lock, which is
+// dropped for the wait; `doff`: the final bucket offsets on the lane, whatever
+// comes before them already queued): the grid dispatch of the local bucket
+// into the lane's delivery scratch and the grid grouping behind it, as
+// route_batch_impl queues them; head = [M, T, G, W].  dwant: the deliveries the
+// lane makes room for at first -- T where k_dp_one left it; more than that and
+// the two run again on the arrays still on the lane.
+static int route32_grid_group(tm_index *ix, HostBatch &hb, const RouteReq &rq, const uint64_t *doff, bool aggre,
+                              uint64_t vcap, uint64_t dwant, uint64_t head[4]) {
+    int rc;
+    Lane &ln = *hb.ln;
+    const hipStream_t s = ln.s;
+    const RouteDispatch *dp = rq.dp;
+    const uint64_t dcap = std::min<uint64_t>(dp->dcap, 0xFFFFFFFFull), gcap = rq.gp->gcap;
+    uint64_t *lhead = reinterpret_cast<uint64_t *>(ln.fo1_s + FO1S_HEAD);
+    dwant = std::min(dwant, dcap);
+    for (int attempt = 0;; attempt++) {
+        if ((rc = dispatch_scratch(ix, ln, vcap, dwant))) return rc;
+        if ((rc = group_scratch(ix, ln, dwant, gcap, rq.who))) return rc;
+        if ((rc = queue_dispatch_to(ix, ln, rq.n_dests, dp->local_dest, doff, aggre, vcap, dwant, lhead, ln.d_dt, ln.d_dv,
+                                    ln.d_ds)))
+            return rc;
+        if ((rc = queue_group(ix, ln, lhead, dwant, gcap, lhead + 2))) return rc;
+        HIPCHK(ix, hipMemcpyAsync(ln.fo1_h + GS1_GRID_HEAD, lhead, 32, hipMemcpyDeviceToHost, s));
+        if ((rc = batch_done(ix, ln))) return rc;
+        hb.g.unlock();
+        HIPCHK(ix, hipStreamSynchronize(s));
+        std::memcpy(head, ln.fo1_h + GS1_GRID_HEAD, 32);
+        if (std::min(head[1], dcap) <= dwant) return TM_OK;
+        if (attempt >= 2) return route_fail(ix, rq, TM_EDEVICE, "the delivery total kept growing past the scratch");
+        dwant = std::min(head[1] + head[1] / 4, dcap);
+        if ((rc = hb.relock())) return rc;
+    }
+}
+
+// what route32_grid_group left on the lane, to the caller (the lock is not held)
+static int route32_group_out(tm_index *ix, Lane &ln, const RouteReq &rq, const uint64_t head[4], uint64_t total) {
+    if (int rc = copy_group_out(ix, ln, rq, head)) return rc;
+    ix->deliver_grid++;
+    return total > rq.cap || head[1] > rq.dp->dcap || head[2] > rq.gp->gcap ? TM_ECAP : TM_OK;
 }
 
 // the [M, T] a grid dispatch left with the lane's status words, to the caller
@@ -4506,6 +4646,13 @@ static int route32_end_grid_dispatch(tm_index *ix, HostBatch &hb, const RouteReq
     if ((rc = ensure_dispatch(ix, ln, FO1_ENTRIES, true))) return rc;
     if ((rc = grow_dev(ix, s, ln.d_o64, ln.d_o64_cap, nfo))) return rc;
     HIPCHK(ix, launch_offs_widen(reinterpret_cast<const uint32_t *>(aggre ? ln.d_ao : ln.d_fo), ln.d_o64, nfo, s));
+    if (rq.gp) {   // into the lane's scratch, grouped there, copied out
+        const volatile uint32_t *st = ln.fo1_h;
+        const uint64_t T = (uint64_t)st[DP1_ST_T_HI] << 32 | st[DP1_ST_T_LO];
+        uint64_t head[4];
+        if ((rc = route32_grid_group(ix, hb, rq, ln.d_o64, aggre, FO1_ENTRIES, T, head))) return rc;
+        return route32_group_out(ix, ln, rq, head, total);
+    }
     if ((rc = queue_dispatch_to(ix, ln, rq.n_dests, rq.dp->local_dest, ln.d_o64, aggre, FO1_ENTRIES, v.dcap,
                                 reinterpret_cast<uint64_t *>(ln.fo1_d + DP1_GRID_HEAD), v.dtopic, v.dvalue, v.dsub)))
         return rc;
@@ -4538,17 +4685,26 @@ static int route32_end_grid(tm_index *ix, HostBatch &hb, const RouteReq &rq, con
     if ((rc = route_scratch(ix, ln, n_dests, vcap, ag, true, rq.n))) return rc;
     if (dp && (rc = ensure_dispatch(ix, ln, vcap, true))) return rc;
     if ((rc = queue_grid_fanout(ix, ln, rq.n, nullptr, ln.d_pr, vcap, n_dests, ag))) return rc;
-    if (dp && (rc = queue_dispatch_to(ix, ln, n_dests, dp->local_dest, ag ? ln.d_ao : ln.d_fo, ag, vcap, v.dcap,
-                                      reinterpret_cast<uint64_t *>(ln.fo1_d + DP1_GRID_HEAD), v.dtopic, v.dvalue, v.dsub)))
-        return rc;
-    if ((rc = batch_done(ix, ln))) return rc;
-    hb.g.unlock();
+    uint64_t ghead[4] = {0, 0, 0, 0};
+    if (rq.gp) {
+        if ((rc = route32_grid_group(ix, hb, rq, ag ? ln.d_ao : ln.d_fo, ag, vcap, std::max<uint64_t>(ln.d_ds_cap, 1 << 16),
+                                     ghead)))
+            return rc;
+    } else {
+        if (dp && (rc = queue_dispatch_to(ix, ln, n_dests, dp->local_dest, ag ? ln.d_ao : ln.d_fo, ag, vcap, v.dcap,
+                                          reinterpret_cast<uint64_t *>(ln.fo1_d + DP1_GRID_HEAD), v.dtopic, v.dvalue,
+                                          v.dsub)))
+            return rc;
+        if ((rc = batch_done(ix, ln))) return rc;
+        hb.g.unlock();
+    }
     rc = copy_route_out(ix, ln, n_dests, total, rq.cap, rq.aggre(), ag_out, fo.data(), out_dest_offsets, rq.out_topic,
                         rq.out_values);
     if (rc != TM_OK && rc != TM_ECAP) return rc;
     if (rq.pk && ag_out)
         if (int prc = pick_after_run(ix, hb, rq, vcap, std::min(fo[n_dests + 1], rq.cap))) return prc;
     if (rq.pk) ix->publish_grid++;
+    if (rq.gp) return route32_group_out(ix, ln, rq, ghead, total);
     if (dp) return route32_grid_head(ix, ln, rq, total);
     ix->route_grid++;
     return rc;
@@ -4570,7 +4726,7 @@ static int route32_in_place(tm_index *ix, const RouteReq &rq, const uint32_t *to
         HIPCHK(ix, hipHostMalloc(&ln.fo1_h, DP1_HOST_WORDS * 4, hipHostMallocMapped));
         HIPCHK(ix, hipHostGetDevicePointer(reinterpret_cast<void **>(&ln.fo1_d), ln.fo1_h, 0));
     }
-    if ((rq.aggre() || rq.dp) && !ln.fo1_s) HIPCHK(ix, hipMalloc(&ln.fo1_s, 2 * FO1_ST_WORDS * 4));
+    if ((rq.aggre() || rq.dp) && !ln.fo1_s) HIPCHK(ix, hipMalloc(&ln.fo1_s, FO1S_WORDS * 4));
     volatile uint32_t *st = ln.fo1_h;
     uint64_t total = 0, vcap = std::max<uint64_t>({ln.d_vals_cap, 4 * n, 1 << 16});
     for (int attempt = 0;; attempt++) {
@@ -4586,6 +4742,7 @@ static int route32_in_place(tm_index *ix, const RouteReq &rq, const uint32_t *to
     }
     const uint32_t state = st[FO1_ST_STATE];
     if (rq.pk && (rc = route32_pick_status(ix, ln, rq, total, state))) return rc;
+    if (rq.gp && (rc = route32_group_status(ix, ln, rq, state))) return rc;
     if (state == FO1_DONE) return route32_end_in_place(ix, ln, rq, total);
     if (rq.dp && state == DP1_TOO_LARGE) return route32_end_grid_dispatch(ix, hb, rq, v, total);
     if (state != FO1_TOO_LARGE) return route_fail(ix, rq, TM_EDEVICE, "the fan-out kernel left no status");
@@ -4616,7 +4773,8 @@ static int route_batch32(tm_index *ix, RouteReq rq, const uint32_t *to, uint32_t
     const int rc = route_batch_impl(ix, rq, o64.data(), fo.data());
     if (rc != TM_OK && rc != TM_ECAP) return rc;
     for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
-    (rq.pk ? ix->publish_grid : rq.dp ? ix->dispatch_grid : ix->route_grid)++;
+    // (rq.gp: copy_group_out narrowed the groups' offsets into out_goff32)
+    (rq.gp ? ix->deliver_grid : rq.pk ? ix->publish_grid : rq.dp ? ix->dispatch_grid : ix->route_grid)++;
     return rc;
 }
 
@@ -4652,6 +4810,18 @@ int tm_publish_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32
     const RoutePick pk{key_clientid, key_topic, seed, out_member};
     return route_batch32(ix, {"tm_publish_batch32", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, &dp, &pk}, to,
                          out_dest_offsets);
+}
+
+int tm_deliver_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint32_t n_dests,
+                       uint32_t local_dest, uint32_t flags, uint32_t *out_dest_offsets, uint32_t *out_topic,
+                       uint32_t *out_values, uint64_t cap, uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue,
+                       uint32_t *out_dsub, uint64_t dcap, uint64_t *out_ghead, uint32_t *out_gsub, uint32_t *out_goff,
+                       uint64_t gcap, uint8_t *out_err) {
+    const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
+    // (G <= W < 2^32: a larger gcap asks for nothing more)
+    const RouteGroup gp{out_ghead, out_gsub, nullptr, std::min<uint64_t>(gcap, 0xFFFFFFFFull), out_goff};
+    return route_batch32(ix, {"tm_deliver_batch32", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, &dp, nullptr, &gp},
+                         to, out_dest_offsets);
 }
 
 int tm_match_batch32_dev(tm_index *ix, uint64_t n, const uint8_t *bytes, const uint32_t *offs, uint32_t *hit_offs,
@@ -4789,6 +4959,7 @@ int tm_debug_set(tm_index *ix, uint32_t key, uint64_t value) {
     case TM_DEBUG_SMALL_TICKET: ix->small_ticket = value != 0; break;
     case TM_DEBUG_PATCH_ZC: ix->patch_zc = value != 0; break;
     case TM_DEBUG_DP1_MAX: ix->dp1_max = std::min<uint64_t>(value, DP1_DELIVERIES); break;
+    case TM_DEBUG_GS1_MAX: ix->gs1_max = std::min<uint64_t>(value, GS1_DELIVERIES); break;
     case TM_DEBUG_SMALL_KERNEL:
         if (value != SMALL_AUTO && value != SMALL_WAVE && value != SMALL_WAVE8)
             return fail(ix, TM_EINVAL, "tm_debug_set: TM_DEBUG_SMALL_KERNEL is 0, 1 or 3 (2, the lane kernel, was removed)");
@@ -4827,6 +4998,14 @@ int tm_debug_get(tm_index *ix, uint32_t key, uint64_t *value) {
     case TM_DEBUG_GROUP_PASSES_SKIPPED: {
         std::lock_guard<std::mutex> g(ix->mu);
         if (int rc = group_passes(ix, key == TM_DEBUG_GROUP_PASSES_SKIPPED, *value)) return rc;
+        *value += ix->gs1_passes[key == TM_DEBUG_GROUP_PASSES_SKIPPED].load();   // (k_gs_one's, counted on the host)
+        break;
+    }
+    case TM_DEBUG_DELIVER_ONE: *value = ix->deliver_one.load(); break;
+    case TM_DEBUG_DELIVER_GRID: *value = ix->deliver_grid.load(); break;
+    case TM_DEBUG_GS1_MAX: {
+        std::lock_guard<std::mutex> g(ix->mu);
+        *value = ix->gs1_max;
         break;
     }
     case TM_DEBUG_DP1_MAX: {

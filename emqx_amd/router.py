@@ -152,7 +152,8 @@ class Router:
         is matched and fanned out in place) instead of route_kids, and
         match_routes_dispatch through dispatch_kids32 (tm_dispatch_batch32)
         instead of dispatch_kids, match_routes_publish through publish_kids32
-        (tm_publish_batch32) instead of publish_kids.
+        (tm_publish_batch32) instead of publish_kids, match_routes_deliver
+        through deliver_kids32 (tm_deliver_batch32) instead of deliver_kids.
         local_subs: this node's subscribers.LocalSubs; the device list of every
         route key {Filter, node()} then follows it (tm_set_subscribers), for
         match_routes_dispatch.
@@ -690,7 +691,8 @@ class Router:
 
     def match_routes_deliver(self, topics, errors: str = "raise", aggre: bool = False):
         """match_routes_dispatch with the deliveries also grouped by subscriber
-        on the device (tm_deliver_batch) -> (ByDest, deliveries, by_sub):
+        on the device (tm_deliver_batch; tm_deliver_batch32 with
+        route_in_place) -> (ByDest, deliveries, by_sub):
         deliveries is match_routes_dispatch's list; by_sub = {pid: [(message
         index, To)]} is that list grouped stably by pid -- what one connection
         process gathers from its mailbox (emqx_connection.erl:611-612), one
@@ -758,7 +760,8 @@ class Router:
                     pub = mirror.publish_kids32 if self._route_in_place else mirror.publish_kids
                     (doff, tidx, kids, err), (dt, dk, ds), member = pub(topics, n_dests, local, *publish)
                 elif grouped:
-                    (doff, tidx, kids, err), gdel, ggrp = mirror.deliver_kids(topics, n_dests, local, aggre=aggre)
+                    dlv = mirror.deliver_kids32 if self._route_in_place else mirror.deliver_kids
+                    (doff, tidx, kids, err), gdel, ggrp = dlv(topics, n_dests, local, aggre=aggre)
                     (dt, dk, ds), dev_groups = self._ungroup(mirror, doff, tidx, kids, local, gdel, ggrp)
                 else:
                     disp = mirror.dispatch_kids32 if self._route_in_place else mirror.dispatch_kids

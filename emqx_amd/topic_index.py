@@ -354,13 +354,17 @@ class Tab:
         blob, offs = _native.pack_strings(topics)
         return self._index.deliver_batch(blob, offs, n_dests, local_dest, aggre=aggre)
 
-    def _route_set(self, n: int, nbytes: int, n_dests: int, cap: int, dcap: int | None = None, pick: bool = False) -> dict:
+    def _route_set(self, n: int, nbytes: int, n_dests: int, cap: int, dcap: int | None = None, pick: bool = False,
+                   group: bool = False) -> dict:
         """A set of pinned buffers (host_array) large enough for the batch, from
         the pool or new -- what a NIF keeps per scheduler.  Arrays too small are
         replaced; the set goes back with _route_put.  dcap: the head and the
         three delivery arrays of dispatch_kids32 as well (a set that never
         dispatched has none); pick: publish_kids32's member array -- a pick per
-        entry the set has room for -- and its two key arrays."""
+        entry the set has room for -- and its two key arrays; group:
+        deliver_kids32's group head, subscribers and offsets, with room for a
+        group per delivery (G <= T: the groups never ask for a rerun of their
+        own)."""
         with self._lock:
             s = self._route_pool.pop() if self._route_pool else {}
         want = {"blob": (nbytes + 16, np.uint8), "offs": (n + 1, np.uint32), "doff": (n_dests + 2, np.uint32),
@@ -368,6 +372,9 @@ class Tab:
         if dcap is not None:
             want.update({"head": (2, np.uint64), "dtopic": (dcap, np.uint32), "dvals": (dcap, np.uint32),
                          "dsubs": (dcap, np.uint32)})
+        if group:
+            room = max(dcap, len(s.get("dsubs", ())))
+            want.update({"ghead": (2, np.uint64), "gsub": (room, np.uint32), "goff": (room + 1, np.uint32)})
         if pick:
             want.update({"member": (max(cap, len(s.get("topic", ()))), np.uint32), "kc": (max(n, 1), np.uint32),
                          "kt": (max(n, 1), np.uint32)})
@@ -390,11 +397,14 @@ class Tab:
         for a in s.values():
             self._index.host_free(a)
 
-    def _kids32(self, topics, n_dests: int, local_dest: int | None = None, aggre: bool = False, pick=None):
+    def _kids32(self, topics, n_dests: int, local_dest: int | None = None, aggre: bool = False, pick=None,
+                group: bool = False):
         """The pooled, in-place call behind route_kids32 (local_dest None),
-        dispatch_kids32 and publish_kids32 (pick: (key_clientid, key_topic,
-        seed); always with aggre) -> (route outputs, deliveries or (), members
-        or None), copies: the buffers go back to the pool.  One retry on TM_ECAP."""
+        dispatch_kids32, publish_kids32 (pick: (key_clientid, key_topic,
+        seed); always with aggre) and deliver_kids32 (group) -> (route outputs,
+        deliveries or (), members or None -- under group the (subscribers,
+        offsets) pair), copies: the buffers go back to the pool.  One retry on
+        TM_ECAP."""
         self.flush()
         ix = self._index
         blob, offs = _native.pack_strings(topics)
@@ -402,11 +412,13 @@ class Tab:
         if nbytes >= 1 << 32:   # no 32-bit offsets for them: the staged calls
             if local_dest is None:
                 return ix.route_batch(blob, offs, n_dests, aggre=aggre), (), None
+            if group:
+                return ix.deliver_batch(blob, offs, n_dests, local_dest, aggre=aggre)
             if pick is None:
                 return ix.dispatch_batch(blob, offs, n_dests, local_dest, aggre=aggre) + (None,)
             return ix.publish_batch(blob, offs, n_dests, local_dest, key_clientid=pick[0], key_topic=pick[1], seed=pick[2])
         first = max(4 * n, 1024)
-        s = self._route_set(n, nbytes, n_dests, first, None if local_dest is None else first, pick is not None)
+        s = self._route_set(n, nbytes, n_dests, first, None if local_dest is None else first, pick is not None, group)
 
         def copied(doff, tidx, kids, err):
             return doff.astype(np.uint64), tidx.copy(), kids.copy(), err.copy()
@@ -433,6 +445,9 @@ class Tab:
                 try:
                     if local_dest is None:
                         res = ix.route_batch32(b, o, n_dests, out, aggre=aggre), (), None
+                    elif group:
+                        res = ix.deliver_batch32(b, o, n_dests, local_dest, out + (s["ghead"], s["gsub"], s["goff"]),
+                                                 aggre=aggre)
                     elif pick is None or kept is not None:
                         res = ix.dispatch_batch32(b, o, n_dests, local_dest, out, aggre=aggre) + (None,)
                     else:
@@ -455,8 +470,13 @@ class Tab:
                     if need > len(s[names[0]]):
                         for name in names:
                             self._route_grow(s, name, need)
+                if group and len(s["gsub"]) < len(s["dsubs"]):   # (a group per delivery, as _route_set sizes them)
+                    self._route_grow(s, "gsub", len(s["dsubs"]))
+                    self._route_grow(s, "goff", len(s["dsubs"]) + 1)
             route, deliveries, member = res
             deliveries = tuple(a.copy() for a in deliveries)
+            if group:
+                return copied(*route), deliveries, (member[0].copy(), member[1].astype(np.uint64))
             if kept is not None:
                 return kept[0], deliveries, kept[1]
             return copied(*route), deliveries, None if member is None else member.copy()
@@ -478,6 +498,15 @@ class Tab:
         bucket offsets and the head.  Returns what dispatch_kids returns
         (copies: the buffers go back to the pool)."""
         return self._kids32(topics, n_dests, local_dest, aggre)[:2]
+
+    def deliver_kids32(self, topics, n_dests: int, local_dest: int, aggre: bool = False):
+        """deliver_kids through tm_deliver_batch32 on pooled pinned buffers: a
+        micro-batch is matched, fanned out, dispatched and grouped by subscriber
+        in place (one synchronisation, no staging copy).  One retry on TM_ECAP,
+        sized from the bucket offsets and the head; the group arrays have room
+        for a group per delivery.  Returns what deliver_kids returns (copies:
+        the buffers go back to the pool)."""
+        return self._kids32(topics, n_dests, local_dest, aggre, group=True)
 
     def publish_kids32(self, topics, n_dests: int, local_dest: int, key_clientid=None, key_topic=None, seed: int = 0):
         """publish_kids through tm_publish_batch32 on pooled pinned buffers: a

@@ -955,6 +955,40 @@ int tm_deliver_batch(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const 
                      uint64_t dcap, uint64_t *out_ghead, uint32_t *out_gsub, uint64_t *out_goff, uint64_t gcap,
                      uint8_t *out_err);
 
+/* tm_deliver_batch32 (ABI minor 21): tm_deliver_batch with 32-bit offsets in
+ * and out, for the NIF's micro-batches.  For the same index state and
+ * arguments the return code and every output are tm_deliver_batch's:
+ * out_dest_offsets narrowed to u32 as in tm_dispatch_batch32, out_goff
+ * narrowed to u32 (gcap + 1 words; entry 0 is written whatever gcap is);
+ * out_head and out_ghead stay u64[2] and must be 8-byte aligned.  Nothing is
+ * written at or past min(total, cap) in out_topic / out_values, min(T, dcap)
+ * in the three delivery arrays, min(G, gcap) in out_gsub, nor past
+ * out_goff[min(G, gcap)].  TM_ECAP: tm_deliver_batch's three rules (total >
+ * cap, T > dcap, G > gcap: out_ghead[0] sizes the retry).  TM_EINVAL: whatever
+ * tm_dispatch_batch32 refuses, a null out_ghead or out_goff, a null out_gsub
+ * with gcap > 0, a misaligned out_ghead.  flags: 0 or TM_ROUTE_AGGRE; there is
+ * no pick.
+ * In place -- no staging copy, no copy out, one synchronisation -- when
+ * tm_dispatch_batch32's conditions hold and out_ghead, out_gsub and out_goff
+ * lie in this index's tm_host_alloc memory too; the device never reads a
+ * caller's buffer.  The one-workgroup dispatch then leaves its deliveries on
+ * the device and ONE more workgroup behind it, on the same stream and under
+ * the same hold of the index lock, sorts their subscriber ids inside LDS
+ * (stable 8-bit LSD passes over 16-bit positions, a digit all ids agree on
+ * skipped as in tm_group_subs_dev) and writes the grouped arrays, the groups
+ * and both heads into the caller's buffers.  It takes at most 16384
+ * deliveries (TM_DEBUG_GS1_MAX lowers that, TM_DEBUG_DP1_MAX too: the smaller
+ * wins): more than that, or more than 16384 route entries, and the grid
+ * dispatch and the grid grouping run on the arrays still on the device and
+ * the results are copied out -- never a second walk.  Every other batch is
+ * widened, run by tm_deliver_batch, and narrowed. */
+int tm_deliver_batch32(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint32_t *topic_offsets,
+                       uint32_t n_dests, uint32_t local_dest, uint32_t flags,
+                       uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                       uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
+                       uint64_t dcap, uint64_t *out_ghead, uint32_t *out_gsub, uint32_t *out_goff, uint64_t gcap,
+                       uint8_t *out_err);
+
 /* Release the batch scratch kept for `stream` (after its batches finish);
  * a caller that retires a stream calls this.  No reference counterpart. */
 int tm_stream_release(tm_index *h, void *stream);
@@ -1067,7 +1101,12 @@ int tm_profile_read(tm_index *h, double *walk_ms, double *batch_ms, uint64_t *ba
  * TM_DEBUG_GROUP_GRID (get only) the blocks of its fixed grid;
  * TM_DEBUG_GROUP_PASSES_RUN / TM_DEBUG_GROUP_PASSES_SKIPPED (get only): the
  * digit passes the grouping calls that have finished ran / skipped, summed
- * over the streams whose scratch is live (four per call together). */
+ * over the streams whose scratch is live (four per call together), and those
+ * of tm_deliver_batch32's one-workgroup grouping.  TM_DEBUG_DELIVER_ONE /
+ * TM_DEBUG_DELIVER_GRID (get only): tm_deliver_batch32 calls the one-workgroup
+ * grouping completed / that the grid kernels or the staged path finished.
+ * TM_DEBUG_GS1_MAX (set / get): the deliveries up to which that workgroup
+ * groups them itself, clamped to the compiled bound (16384). */
 enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES = 3, TM_DEBUG_PHASES = 4,
        TM_DEBUG_FAILED_BATCHES = 5, TM_DEBUG_RETRIED_BATCHES = 6, TM_DEBUG_PATH_PHASES = 7,
        TM_DEBUG_PATH_SMALL = 8, TM_DEBUG_PATH_LANE = 9, TM_DEBUG_SMALL_KERNEL = 10,
@@ -1079,7 +1118,7 @@ enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES =
        TM_DEBUG_HINT_AUDIT = 30, TM_DEBUG_SUB_COMPACTIONS = 31, TM_DEBUG_DISPATCH_ONE = 32,
        TM_DEBUG_DISPATCH_GRID = 33, TM_DEBUG_DP1_MAX = 34, TM_DEBUG_PUBLISH_ONE = 35, TM_DEBUG_PUBLISH_GRID = 36,
        TM_DEBUG_GROUP_TILE = 37, TM_DEBUG_GROUP_PASSES_RUN = 38, TM_DEBUG_GROUP_PASSES_SKIPPED = 39,
-       TM_DEBUG_GROUP_GRID = 40 };
+       TM_DEBUG_GROUP_GRID = 40, TM_DEBUG_DELIVER_ONE = 41, TM_DEBUG_DELIVER_GRID = 42, TM_DEBUG_GS1_MAX = 43 };
 int tm_debug_set(tm_index *h, uint32_t key, uint64_t value);
 int tm_debug_get(tm_index *h, uint32_t key, uint64_t *value);
 

@@ -59,8 +59,12 @@ index with a subscriber table of dense ids and one fan-in consumer;
 tm_deliver_batch beside tm_dispatch_batch, host to host and interleaved, at 64
 / 1,024 / 4,096 topics (--sizes), tm_deliver_batch's outputs checked against
 tm_dispatch_batch's grouped on the host; the grouping's added time is
-deliver_minus_dispatch_ms.  With a library from before tm_deliver_batch the
-dispatch leg runs alone.
+deliver_minus_dispatch_ms.  Beside them the in-place forms on tm_host_alloc
+buffers, tm_dispatch_batch32 and tm_deliver_batch32 (outputs checked against
+tm_deliver_batch's; grouped_by says whether the one-workgroup grouping
+finished it): deliver32_minus_dispatch32_ms is what the grouping adds there.
+With a library from before tm_deliver_batch the dispatch legs run alone, from
+before tm_deliver_batch32 all but that one.
 
 --aggre: aggre/1 on the device (nothing of the first part runs).  The batch is
 matched as pairs and fanned out with tm_fanout_dev_pairs over a destination
@@ -1018,6 +1022,42 @@ def small_group(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=0):
                 np.array_equal(gsub[:G], gs) and np.array_equal(goff[:G + 1], np.concatenate([[0], np.cumsum(c)])), \
                 f"n {n}: tm_deliver_batch differs from tm_dispatch_batch grouped on the host"
             legs.append(("deliver_batch", leg_g))
+        pinned, took = [], None
+        has_d32 = hasattr(lib, "tm_dispatch_batch32")
+        has_g32 = hasattr(lib, "tm_deliver_batch32") and not a.no_deliver32_leg
+        if has_d32:
+            # the in-place forms on tm_host_alloc buffers: tm_dispatch_batch32 and, grouped, tm_deliver_batch32
+            def pin(k, dt):
+                pinned.append(ix.host_array(k, dt))
+                return pinned[-1]
+            b32, o32, e32 = pin(nb + 16, np.uint8), pin(n + 1, np.uint32), pin(n, np.uint8)
+            b32[:nb], o32[:] = blob[:nb], offs64.astype(np.uint32)
+            d32, h32, gh32 = pin(n_dests + 2, np.uint32), pin(2, np.uint64), pin(2, np.uint64)
+            t32, v32 = (pin(cap, np.uint32) for _ in range(2))
+            dd32 = tuple(pin(dcap, np.uint32) for _ in range(3))
+            gs32, go32 = pin(dcap, np.uint32), pin(dcap + 1, np.uint32)
+
+            def leg_d32():
+                return lib.tm_dispatch_batch32(h, n, P(b32), P(o32), n_dests, local, flags, P(d32), P(t32), P(v32), cap,
+                                               P(h32), P(dd32[0]), P(dd32[1]), P(dd32[2]), dcap, P(e32))
+
+            def leg_g32():
+                return lib.tm_deliver_batch32(h, n, P(b32), P(o32), n_dests, local, flags, P(d32), P(t32), P(v32), cap,
+                                              P(h32), P(dd32[0]), P(dd32[1]), P(dd32[2]), dcap, P(gh32), P(gs32), P(go32),
+                                              dcap, P(e32))
+
+            assert leg_d32() == 0, "the in-place dispatch leg failed"
+            legs.append(("dispatch_batch32", leg_d32))
+            if has_g32:
+                ONE = _native.TM_DEBUG_DELIVER_ONE
+                c0 = ix.debug_get(ONE)
+                assert leg_g() == 0 and leg_g32() == 0
+                took = "one_workgroup" if ix.debug_get(ONE) > c0 else "grid_or_staged"
+                assert gh32.tolist() == ghead.tolist() and h32.tolist() == head.tolist() and \
+                    all(np.array_equal(x[:T], y[:T]) for x, y in zip(dd32, db)) and np.array_equal(gs32[:G], gsub[:G]) and \
+                    np.array_equal(go32[:G + 1].astype(np.uint64), goff[:G + 1]), \
+                    f"n {n}: tm_deliver_batch32 differs from tm_deliver_batch"
+                legs.append(("deliver_batch32", leg_g32))
         ms = {k: [] for k, _ in legs}
         for r in range(warmup + reps):
             for k, f in legs:
@@ -1033,8 +1073,13 @@ def small_group(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=0):
                 "warmup": warmup, "reps": reps, **st, "identical": True if has else None}
         if has:
             line["deliver_minus_dispatch_ms"] = round(st["deliver_batch"]["p50_ms"] - st["dispatch_batch"]["p50_ms"], 4)
+        if took is not None:
+            line["grouped_by"] = took
+            line["deliver32_minus_dispatch32_ms"] = round(st["deliver_batch32"]["p50_ms"] -
+                                                          st["dispatch_batch32"]["p50_ms"], 4)
+            line["deliver_over_deliver32"] = round(st["deliver_batch"]["p50_ms"] / st["deliver_batch32"]["p50_ms"], 2)
         print(json.dumps(line), flush=True)
-        for x in (blob, offs64):
+        for x in [blob, offs64] + pinned:
             ix.host_free(x)
 
 
@@ -1057,6 +1102,8 @@ def main():
                         "with --small: tm_deliver_batch beside tm_dispatch_batch, host to host")
     p.add_argument("--dispatch-leg-only", action="store_true",
                    help="--small --share: time tm_dispatch_batch alone, as a library without tm_publish_batch is timed")
+    p.add_argument("--no-deliver32-leg", action="store_true",
+                   help="--small --group: leave the tm_deliver_batch32 leg out, as a library without it is timed")
     p.add_argument("--sizes", type=int, nargs="+", default=None, help="--small: the batch sizes")
     p.add_argument("--dp1-max", type=int, default=None,
                    help="--small --dispatch: TM_DEBUG_DP1_MAX for the dispatch_batch32 leg (default: the compiled bound)")
