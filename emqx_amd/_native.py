@@ -32,7 +32,8 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_route_batch32_ex", "tm_set_subscribers", "tm_dispatch_dev", "tm_dispatch_batch",
            "tm_dispatch_batch32", "tm_set_share_slots", "tm_set_share_members", "tm_share_state_set",
            "tm_share_state_get", "tm_share_pick_dev", "tm_publish_batch", "tm_publish_batch32",
-           "tm_group_subs_dev", "tm_deliver_batch", "tm_deliver_batch32")
+           "tm_group_subs_dev", "tm_deliver_batch", "tm_deliver_batch32", "tm_set_member_subs",
+           "tm_group_picks_dev", "tm_publish_deliver_batch")
 TM_ALLOC_VRAM = 1
 TM_ROUTE_AGGRE = 1          # tm_route_batch_ex / tm_route_batch32_ex: aggre/1 applied to the buckets
 NO_FILTER = 0xFFFFFFFF      # tm_set_route_filters: no filter known (equal to nothing)
@@ -173,6 +174,11 @@ def load_library(path: Path | None = None):
                                      vp]),
         "tm_deliver_batch": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, u64,
                                    vp]),
+        "tm_set_member_subs": (i32, [vp, u64, vp, vp]),
+        "tm_group_picks_dev": (i32, [vp, vp, vp, vp, vp, u64, u32, vp, vp, vp, vp, u64, vp, u64, vp, vp, vp, u64, vp, vp, vp,
+                                     vp, u64, vp]),
+        "tm_publish_deliver_batch": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u32,
+                                           vp, vp, vp, vp, u64, vp]),
         "tm_debug_set": (i32, [vp, u32, u64]),
         "tm_debug_get": (i32, [vp, u32, C.POINTER(u64)]),
     }
@@ -816,6 +822,84 @@ class Index:
         if any(k is not None and len(k) < n for k in (kc, kt)):
             raise ValueError("publish_batch: one key word per topic")
         return self._dispatch_loop(blob, offs, n_dests, local_dest, cap, dcap, TM_ROUTE_AGGRE, pick=(kc, kt, seed))
+
+    # ---- picks grouped with the deliveries (include/tmatch.h, ABI minor 22)
+    def set_member_subs(self, members, sub_ids):
+        """tm_set_member_subs: sub_ids[i] becomes the local subscriber id of share
+        member members[i] (u32 each; TM_SHARE_NONE: not a connection of this node)."""
+        members = np.ascontiguousarray(members, dtype=np.uint32)
+        sub_ids = np.ascontiguousarray(sub_ids, dtype=np.uint32)
+        if len(members) != len(sub_ids):
+            raise ValueError("set_member_subs: one subscriber id per member")
+        self._check(self._lib.tm_set_member_subs(self._h, len(members), _ptr(members), _ptr(sub_ids)))
+
+    def group_picks_dev(self, d_head: int, d_topic: int, d_value: int, d_sub: int, cap: int, n_dests: int,
+                        d_dest_offs: int, d_etopic: int, d_evalue: int, d_member: int, ecap: int, d_out_ghead: int,
+                        d_out_gsub: int, d_out_goff: int, gcap: int, d_out_topic: int, d_out_value: int, d_out_sub: int,
+                        out_cap: int, d_out_src: int | None = None, d_sub_of: int | None = None, sub_of_len: int = 0,
+                        stream: int | None = None):
+        """tm_group_picks_dev on device pointers: the first min(d_head[1], cap)
+        deliveries a dispatch wrote and the local picks (d_sub_of[d_member[q]] !=
+        TM_SHARE_NONE) among the first min(d_dest_offs[n_dests + 1], ecap)
+        aggregated entries, merged by message and stably sorted by subscriber
+        into d_out_topic / d_out_value / d_out_sub (d_out_src: a delivery's
+        position, or W + a pick's rank); d_out_ghead u64[2] = (groups G, merged
+        deliveries N), groups as group_subs_dev.  d_sub_of None: the table of
+        set_member_subs."""
+        self._check(self._lib.tm_group_picks_dev(self._h, d_head, d_topic, d_value, d_sub, cap, n_dests, d_dest_offs,
+                                                 d_etopic, d_evalue, d_member, ecap, d_sub_of, sub_of_len, d_out_ghead,
+                                                 d_out_gsub, d_out_goff, gcap, d_out_topic, d_out_value, d_out_sub,
+                                                 d_out_src, out_cap, stream))
+
+    def publish_deliver_batch(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, local_dest: int,
+                              cap: int | None = None, dcap: int | None = None, gcap: int | None = None,
+                              key_clientid=None, key_topic=None, seed: int = 0):
+        """tm_publish_deliver_batch -> (route tuple, (dtopic, dvalue, dsub) u32[N]
+        -- the direct deliveries and the local picks merged and GROUPED by
+        subscriber --, member u32[K], (gsub u32[G], goff u64[G + 1]), T the
+        direct deliveries' number).  cap and dcap are sized from a first try:
+        a call that returns TM_ECAP for either made no pick and moved no state,
+        and is repeated once.  A gcap that proves too small is NOT retried (the
+        picks of that call stand): the groups are read off the sorted dsub."""
+        n = len(offs) - 1
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        kc = None if key_clientid is None else np.ascontiguousarray(key_clientid, dtype=np.uint32)
+        kt = None if key_topic is None else np.ascontiguousarray(key_topic, dtype=np.uint32)
+        if any(k is not None and len(k) < n for k in (kc, kt)):
+            raise ValueError("publish_deliver_batch: one key word per topic")
+        doff = np.zeros(n_dests + 2, dtype=np.uint64)
+        head, ghead = np.zeros(2, dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+        err = np.zeros(max(n, 1), dtype=np.uint8)
+        cap = max(4 * n, 1024) if cap is None else cap
+        dcap = max(8 * n, 2048) if dcap is None else dcap
+        gcap = 1024 if gcap is None else gcap
+        for attempt in range(3):
+            topic, vals, member = (np.empty(max(cap, 1), dtype=np.uint32) for _ in range(3))
+            dt, dv, ds = (np.empty(max(dcap, 1), dtype=np.uint32) for _ in range(3))
+            gsub, goff = np.empty(max(gcap, 1), dtype=np.uint32), np.zeros(gcap + 1, dtype=np.uint64)
+            rc = self._lib.tm_publish_deliver_batch(self._h, n, _ptr(blob), _ptr(offs), n_dests, local_dest, TM_ROUTE_AGGRE,
+                                                    _ptr(doff), _ptr(topic), _ptr(vals), cap, _ptr(head), _ptr(dt),
+                                                    _ptr(dv), _ptr(ds), dcap, _ptr(kc), _ptr(kt), seed, _ptr(member),
+                                                    _ptr(ghead), _ptr(gsub), _ptr(goff), gcap, _ptr(err))
+            total, T = int(doff[-1]), int(head[1])
+            if rc == TM_ECAP and (total > cap or T + total > dcap):
+                # no pick was made and no state moved: sized from what came back (under total > cap the
+                # un-aggregated total, an upper bound of K)
+                cap, dcap = max(cap, total), max(dcap, T + total)
+                continue
+            G, N = int(ghead[0]), int(ghead[1])
+            if rc == TM_ECAP and G > gcap:
+                # the picks stand and the grouped arrays are complete: the groups from the sorted subscribers
+                s = ds[:N]
+                starts = np.flatnonzero(np.concatenate(([True], s[1:] != s[:-1]))) if N else np.zeros(0, np.int64)
+                gsub, goff = s[starts].copy(), np.concatenate((starts, [N])).astype(np.uint64)
+            else:
+                self._check(rc)
+                gsub, goff = gsub[:G], goff[:G + 1]
+            return (doff, topic[:total], vals[:total], err[:n]), (dt[:N], dv[:N], ds[:N]), member[:total], \
+                (gsub, goff), T
+        raise TmError(TM_ECAP, "publish_deliver_batch: the totals kept growing")
 
     def publish_batch32(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, local_dest: int, out, member,
                         key_clientid=None, key_topic=None, seed: int = 0, cap: int | None = None,

@@ -61,7 +61,7 @@ class Broker:
                  max_batch: int = 4096, max_wait_ms: float = 0.2, start: bool = False,
                  aggre_on_device: bool = False, dispatch_on_device: bool = False, deliver=None,
                  share_on_device: bool = False, share_send=None, share_keys=None, share_seed: int = 0,
-                 deliver_grouped: bool = False, deliver_batch=None):
+                 deliver_grouped: bool = False, deliver_batch=None, share_grouped: bool = False):
         """aggre_on_device: publish_batch_by_dest asks the router for buckets
         the device has already applied aggre/1 to (TM_ROUTE_AGGRE).
         dispatch_on_device: publish_batch_by_dest asks the router for the local
@@ -81,7 +81,21 @@ class Broker:
         message)]) once per subscriber per batch, the list in publish order --
         what the connection process gathers from its mailbox
         (emqx_connection.erl:611-612) -- in place of one deliver per delivery.
-        What publish_batch_by_dest returns is unchanged."""
+        What publish_batch_by_dest returns is unchanged.
+        share_grouped (needs share_on_device; deliver_grouped beside
+        share_on_device alone stays without effect): publish_batch_by_dest asks
+        the router for the local picks grouped with the local deliveries
+        (Router.match_routes_publish_deliver).  Each local subscriber then gets
+        ONE deliver_batch(SubPid, [(To, message)]) per batch, direct and picked
+        items together in publish order, and share_send is called only for picks
+        whose member is not a connection of this node.  A deliver_batch that
+        returns a reason other than None or "ok" (a dead pid): the subscriber's
+        picked items re-enter the host's dispatch/4 recursion with the pid in
+        FailedSubs, its direct items are dropped, as do_dispatch2 drops them.
+        What publish_batch_by_dest returns is what share_on_device alone returns."""
+        if share_grouped and not share_on_device:
+            raise ValueError("share_grouped needs share_on_device")
+        self.share_grouped = share_grouped
         self.deliver_grouped = deliver_grouped
         self.deliver_batch = deliver_batch or (lambda sub, items: None)
         self.share_on_device = share_on_device
@@ -165,8 +179,14 @@ class Broker:
         deliveries = picks = keys = by_sub = None
         if self.share_on_device:
             keys = [self.share_keys(m) for m in msgs]
-            by_dest, deliveries, picks = self.router.match_routes_publish(
-                [m.topic for m in msgs], [k[0] for k in keys], [k[1] for k in keys], seed=self.share_seed, errors="return")
+            if self.share_grouped:
+                by_dest, deliveries, picks, by_sub = self.router.match_routes_publish_deliver(
+                    [m.topic for m in msgs], [k[0] for k in keys], [k[1] for k in keys], seed=self.share_seed,
+                    errors="return")
+            else:
+                by_dest, deliveries, picks = self.router.match_routes_publish(
+                    [m.topic for m in msgs], [k[0] for k in keys], [k[1] for k in keys], seed=self.share_seed,
+                    errors="return")
             on_dev = True
         elif self.deliver_grouped:
             by_dest, deliveries, by_sub = self.router.match_routes_deliver([m.topic for m in msgs], errors="return",
@@ -202,7 +222,15 @@ class Broker:
         for dest, plan in plans.items():
             plan.sort(key=lambda e: e[0])   # several classes in one plan (every ("external", X)): message order again
             out[dest] = [(i, to) + (self._route2((to, dest), msgs[i])[2],) for i, to in plan]
-        if deliveries:
+        failed: dict = {}   # share_grouped: SubPid -> the reason its deliver_batch gave
+        if self.share_grouped:
+            for sub, items in by_sub.items():
+                reason = self.deliver_batch(sub, [(to, msgs[i]) for i, to in items])
+                if reason is not None and reason != "ok":
+                    failed[sub] = reason
+            if deliveries:
+                out[self.node] = list(deliveries)
+        elif deliveries:
             if by_sub is not None:
                 for sub, items in by_sub.items():
                     self.deliver_batch(sub, [(to, msgs[i]) for i, to in items])
@@ -211,7 +239,14 @@ class Broker:
                     self.deliver(sub, to, msgs[i])
             out[self.node] = list(deliveries)
         for group, rows in (picks or {}).items():
-            out[group] = [(i, to, self._share_deliver(group, to, i, pid, msgs[i], keys[i])) for i, to, pid in rows]
+            plan = out[group] = []
+            for i, to, pid in rows:
+                if self.share_grouped and pid is not None and self.router.member_is_local(pid):
+                    # its deliver_batch carried the message; a dead pid: dispatch/4's recursion on the host
+                    res = pid if pid not in failed else self._share_failed(group, to, i, pid, failed[pid], msgs[i], keys[i])
+                else:
+                    res = self._share_deliver(group, to, i, pid, msgs[i], keys[i])
+                plan.append((i, to, res))
         return out, by_dest.errors
 
     def _share_deliver(self, group, to, i, pid, msg, hashes):
@@ -225,6 +260,10 @@ class Broker:
         reason = self.share_send(pid, to, msg)
         if reason == "ok":
             return pid
+        return self._share_failed(group, to, i, pid, reason, msg, hashes)
+
+    def _share_failed(self, group, to, i, pid, reason, msg, hashes):
+        """dispatch/4's recursion after the send to `pid` failed with `reason`"""
         ss = self.router.shared_subs
         slot = ss.slot(group, to)
         if slot is not None:

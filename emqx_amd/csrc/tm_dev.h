@@ -236,6 +236,11 @@ struct FanoutScratch {
     // ping-pong (gs_k[b], gs_p[b]: 16 bytes in all)
     uint32_t *gs_fix, *gs_k[2], *gs_p[2];
     uint64_t gs_cap;
+    // picks merged with the deliveries (launch_group_picks; the grouping's scratch above carries its two
+    // sorts): one allocation -- GP_FIX_WORDS fixed words, the merged (topic, value, sub, src) arrays below
+    // gp_cap (cap + ecap), the local picks' compacted (topic, value, sub) below gp_ecap
+    uint32_t *gp_fix, *gp_m[4], *gp_c[3];
+    uint64_t gp_cap, gp_ecap;
 };
 constexpr uint32_t FP_TILES = 1024;
 #if defined(__HIPCC__)
@@ -459,6 +464,28 @@ hipError_t launch_group_subs(const FanoutScratch &fs, const uint64_t *head, cons
                              const uint32_t *in_value, const uint32_t *in_sub, uint64_t cap, uint64_t *ghead,
                              uint32_t *out_gsub, uint64_t *out_goff, uint64_t gcap, uint32_t *out_topic,
                              uint32_t *out_value, uint32_t *out_sub, uint32_t *out_perm, hipStream_t s);
+// The shared-subscription picks merged with the deliveries and grouped
+// (tm_group.hip; include/tmatch.h tm_group_picks_dev has the definition): the
+// first W = min(head[1], cap) deliveries a dispatch wrote (ascending topic
+// index) and, of the first E = min(dest_offsets[n_dests + 1], ecap) aggregated
+// entries, those whose picked member is a local subscriber (sub_of[member]
+// != NONE), merged by topic index and stably sorted by subscriber.  ghead =
+// [G, N], N = W + P; the first min(N, out_cap) merged deliveries are written,
+// out_src (when given) naming a delivery (< W) or W + the pick's rank.  Needs
+// fs.gs_fix, fs.gs_cap >= cap + ecap, fs.gp_cap >= cap + ecap, fs.gp_ecap >=
+// ecap (both clamped to 2^32 - 1, their sum too: the caller checks).
+// msg_passes: every topic index is below 2^(8 * msg_passes) (GS_PASSES: no
+// bound known) -- the picks' sort by message queues that many digit passes.
+// fs.gp_fix, in u32 words: the picks' head [0, P] and the merged head [0, N]
+// (two u64 each, written on the device), the blocks' local-pick counts.
+enum { GP_PH = 0, GP_MH = 4, GP_CNT = 8, GP_FIX_WORDS = GP_CNT + GS_GRID };
+hipError_t launch_group_picks(const FanoutScratch &fs, const uint64_t *head, const uint32_t *in_topic,
+                              const uint32_t *in_value, const uint32_t *in_sub, uint64_t cap, uint32_t n_dests,
+                              const uint64_t *dest_offsets, const uint32_t *e_topic, const uint32_t *e_value,
+                              const uint32_t *member, uint64_t ecap, const uint32_t *sub_of, uint64_t sub_of_len,
+                              uint64_t *ghead, uint32_t *out_gsub, uint64_t *out_goff, uint64_t gcap, uint32_t *out_topic,
+                              uint32_t *out_value, uint32_t *out_sub, uint32_t *out_src, uint64_t out_cap,
+                              uint32_t msg_passes, hipStream_t s);
 // A micro-batch's grouping in ONE launch of ONE workgroup (k_gs_one;
 // tm_deliver_batch32), queued behind launch_dispatch_one, which is then given
 // the lane's delivery arrays (in_topic / in_value / in_sub, GS1_DELIVERIES

@@ -381,6 +381,227 @@ __global__ __launch_bounds__(GS_BLOCK) void k_gs_emit(const uint64_t *head, uint
     }
 }
 
+// ---- the shared-subscription picks merged with the deliveries and grouped
+// (tm_group_picks_dev).  A connection process receives {deliver, To, Msg} from
+// do_dispatch2 and from emqx_shared_sub:dispatch/3 in one mailbox; its list of
+// a batch holds both kinds in publish order.  The deliveries come in ascending
+// message order, the picks in entry order (bucket by bucket), so the picks are
+// merged in by message before the subscriber sort, which is stable:
+//   k_gp_count    block k counts the local picks (sub_of[member[q]] != NONE)
+//                 among its chunk of the E entries (a ballot and popcount per
+//                 wave);
+//   k_gp_scan     one block: the exclusive scan of the GS_GRID counts; the
+//                 picks' head [0, P] and the merged head [0, N = W + P];
+//   k_gp_compact  the block's local picks (topic, value, subscriber) to their
+//                 ranks, ascending q: rank = the block's base + the picks of
+//                 earlier tiles and waves + the set lanes below;
+//   the k_gs_pre / plan / hist / scan / scatter passes above over the P picks'
+//   topic indices, head [0, P]: a stable sort by message, a digit all agree on
+//   skipped -- a batch of at most 256 messages costs one pass;
+//   k_gp_merge    two binary searches on sorted arrays: delivery p goes to p +
+//                 the picks with a message < t_p, the pick of sorted rank r to
+//                 r + the deliveries with a message <= t_r -- inside one
+//                 message the deliveries first, then its picks in ascending q;
+//                 writes the merged (topic, value, subscriber, src);
+//   the same k_gs_* passes, k_gs_heads and k_gs_gscan over the N merged
+//   subscriber ids, head [0, N];
+//   k_gp_emit     k_gs_emit with a bound on the positions written (out_cap)
+//                 and out_src through the merged src.
+// Bytes per entry below E: 8 read twice (member, sub_of), per local pick 8 read
+// + 12 written (compact), 4 + per pass 28 (the sort), 16 gathered + 16 written
+// and two searches (merge); per delivery 12 read + 16 written and one search
+// (merge); per merged delivery the grouping's bytes above, k_gp_emit's 16
+// gathered for k_gs_emit's 8.  Scratch: 32 bytes per (cap + ecap), 12 per ecap.
+constexpr uint32_t GP_NONE = 0xFFFFFFFFu;
+
+__device__ __forceinline__ uint64_t gp_e(const uint64_t *doff, uint32_t n_dests, uint64_t ecap) {
+    const uint64_t K = doff[(uint64_t)n_dests + 1];
+    return K < ecap ? K : ecap;
+}
+
+// the entries block `blk` owns: [c0, c1) of [0, E), whole GS_BLOCK tiles
+__device__ __forceinline__ void gp_chunk(uint64_t E, uint32_t blk, uint64_t &c0, uint64_t &c1) {
+    const uint64_t chunk = ((E + GS_GRID - 1) / GS_GRID + GS_BLOCK - 1) / GS_BLOCK * GS_BLOCK;
+    c0 = (uint64_t)blk * chunk;
+    if (c0 > E) c0 = E;
+    c1 = c0 + chunk < E ? c0 + chunk : E;
+}
+
+// the local subscriber entry q's pick goes to (NONE: no pick, or not a connection of this node)
+__device__ __forceinline__ uint32_t gp_local(const uint32_t *member, const uint32_t *sub_of, uint64_t sub_of_len,
+                                             uint64_t q) {
+    const uint32_t m = member[q];
+    return m < sub_of_len ? sub_of[m] : GP_NONE;
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void k_gp_count(uint32_t n_dests, const uint64_t *doff, uint64_t ecap,
+                                                       const uint32_t *member, const uint32_t *sub_of,
+                                                       uint64_t sub_of_len, uint32_t *gfix) {
+    __shared__ uint32_t s_w[GS_WAVES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint64_t c0, c1;
+    gp_chunk(gp_e(doff, n_dests, ecap), blockIdx.x, c0, c1);
+    uint32_t n = 0;
+    for (uint64_t i0 = c0 + wv * 64; i0 < c1; i0 += GS_BLOCK) {   // (wave-uniform)
+        const uint64_t i = i0 + lane;
+        const bool f = i < c1 && gp_local(member, sub_of, sub_of_len, i) != GP_NONE;
+        n += (uint32_t)__popcll(__ballot(f));
+    }
+    if (lane == 0) s_w[wv] = n;
+    __syncthreads();
+    if (tid == 0) gfix[GP_CNT + blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];   // (every word, every call)
+}
+
+__global__ __launch_bounds__(1024) void k_gp_scan(const uint64_t *head, uint64_t cap, uint32_t *gfix) {
+    __shared__ uint32_t s_w[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint32_t c = gfix[GP_CNT + tid];
+    const uint32_t inc = gs_incl_scan32(c, lane);
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    uint32_t base = inc - c;
+    for (uint32_t w = 0; w < wv; w++) base += s_w[w];
+    gfix[GP_CNT + tid] = base;
+    if (tid == 1023) {
+        const uint64_t P = (uint64_t)base + c;
+        uint64_t *ph = reinterpret_cast<uint64_t *>(gfix + GP_PH), *mh = reinterpret_cast<uint64_t *>(gfix + GP_MH);
+        ph[0] = 0;
+        ph[1] = P;
+        mh[0] = 0;
+        mh[1] = gs_w(head, cap) + P;
+    }
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void k_gp_compact(uint32_t n_dests, const uint64_t *doff, uint64_t ecap,
+                                                         const uint32_t *e_topic, const uint32_t *e_value,
+                                                         const uint32_t *member, const uint32_t *sub_of,
+                                                         uint64_t sub_of_len, const uint32_t *gfix, uint32_t *pt,
+                                                         uint32_t *pv, uint32_t *ps) {
+    __shared__ uint32_t s_w[GS_WAVES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint64_t c0, c1;
+    gp_chunk(gp_e(doff, n_dests, ecap), blockIdx.x, c0, c1);
+    uint64_t base = gfix[GP_CNT + blockIdx.x];
+    for (uint64_t t0 = c0; t0 < c1; t0 += GS_BLOCK) {   // (block-uniform)
+        const uint64_t i = t0 + tid;
+        const uint32_t ls = i < c1 ? gp_local(member, sub_of, sub_of_len, i) : GP_NONE;
+        const bool f = ls != GP_NONE;
+        const uint64_t m = __ballot(f);
+        if (lane == 0) s_w[wv] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint64_t at = base + gs_below(m, lane);
+        uint32_t all = 0;
+        for (uint32_t w = 0; w < GS_WAVES; w++) {
+            if (w < wv) at += s_w[w];
+            all += s_w[w];
+        }
+        if (f && at < ecap) {   // (at < P <= E <= ecap always)
+            pt[at] = e_topic[i];
+            pv[at] = e_value[i];
+            ps[at] = ls;
+        }
+        base += all;
+        __syncthreads();
+    }
+}
+
+// the keys of k[0 .. n) (ascending) below x / at or below x
+__device__ __forceinline__ uint64_t gp_lower(const uint32_t *k, uint64_t n, uint32_t x) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (k[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ uint64_t gp_upper(const uint32_t *k, uint64_t n, uint32_t x) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (k[mid] <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(GS_BLOCK) void k_gp_merge(const uint64_t *head, uint64_t cap, const uint32_t *in_topic,
+                                                       const uint32_t *in_value, const uint32_t *in_sub, uint64_t ecap,
+                                                       GsBufs bufs, const uint32_t *gfix, const uint32_t *pt,
+                                                       const uint32_t *pv, const uint32_t *ps, uint32_t *mt, uint32_t *mv,
+                                                       uint32_t *ms, uint32_t *msrc) {
+    const uint64_t W = gs_w(head, cap);
+    uint64_t P = reinterpret_cast<const uint64_t *>(gfix + GP_PH)[1];
+    if (P > ecap) P = ecap;   // (never)
+    const uint64_t N = W + P;
+    const uint32_t *k, *p;   // the picks' topic indices, sorted, and their ranks before the sort
+    gs_source(bufs, pt, bufs.fix[GS_SRC + GS_PASSES], k, p);
+    for (uint64_t i = (uint64_t)blockIdx.x * GS_BLOCK + threadIdx.x; i < N; i += (uint64_t)GS_GRID * GS_BLOCK) {
+        uint64_t d;
+        uint32_t t, v, s, src;
+        if (i < W) {
+            t = in_topic[i];
+            v = in_value[i];
+            s = in_sub[i];
+            src = (uint32_t)i;
+            d = i + gp_lower(k, P, t);
+        } else {
+            const uint64_t r = i - W;
+            uint32_t pos = p ? p[r] : (uint32_t)r;
+            if (pos >= P) pos = 0;   // (never: a permutation of [0, P))
+            t = k[r];
+            v = pv[pos];
+            s = ps[pos];
+            src = (uint32_t)(W + pos);
+            d = r + gp_upper(in_topic, W, t);
+        }
+        if (d < N) {   // (always)
+            mt[d] = t;
+            mv[d] = v;
+            ms[d] = s;
+            msrc[d] = src;
+        }
+    }
+}
+
+// k_gs_emit over the merged arrays (head = [0, N]): only positions below out_cap are written, out_src
+// names the input through the merged src
+__global__ __launch_bounds__(GS_BLOCK) void k_gp_emit(const uint64_t *head, uint64_t cap, const uint32_t *mt,
+                                                      const uint32_t *mv, const uint32_t *ms, const uint32_t *msrc,
+                                                      GsBufs bufs, uint32_t *out_gsub, uint64_t *out_goff, uint64_t gcap,
+                                                      uint32_t *out_topic, uint32_t *out_value, uint32_t *out_sub,
+                                                      uint32_t *out_src, uint64_t out_cap) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t N = gs_w(head, cap);
+    uint64_t c0, c1, q;
+    gs_chunk(N, blockIdx.x, c0, c1, q);
+    const uint32_t *k, *p;
+    gs_source(bufs, ms, bufs.fix[GS_SRC + GS_PASSES], k, p);
+    const uint64_t w0 = c0 + wv * q < c1 ? c0 + wv * q : c1, w1 = w0 + q < c1 ? w0 + q : c1;
+    uint64_t g0 = bufs.fix[GS_GCNT + blockIdx.x * GS_WAVES + wv];   // groups that start before w0
+    for (uint64_t i0 = w0; i0 < w1; i0 += 64) {
+        const uint64_t i = i0 + lane;
+        const bool ok = i < w1;
+        const uint32_t key = ok ? k[i] : 0u;
+        const uint32_t pos = !ok ? 0u : p ? p[i] : (uint32_t)i;
+        const bool h = ok && gs_is_head(k, i, key);
+        const uint64_t hm = __ballot(h);
+        if (h) {
+            const uint64_t g = g0 + gs_below(hm, lane);
+            if (g < gcap) out_gsub[g] = key;
+            if (g <= gcap) out_goff[g] = i;   // (g == gcap < G: where the first group left out starts)
+        }
+        g0 += (uint32_t)__popcll(hm);
+        if (ok && pos < N && i < out_cap) {   // (pos < N always)
+            out_topic[i] = mt[pos];
+            out_value[i] = mv[pos];
+            out_sub[i] = key;
+            if (out_src) out_src[i] = msrc[pos];
+        }
+    }
+}
+
 // ---- a micro-batch's grouping in ONE workgroup (tm_deliver_batch32), queued
 // behind k_dp_one, which under a grouping request writes its deliveries and
 // its head to the lane (in_t / in_v / in_s, head) and not to the caller.
@@ -626,6 +847,66 @@ hipError_t launch_group_subs(const FanoutScratch &fs, const uint64_t *head, cons
     hipLaunchKernelGGL(k_gs_gscan, one, wide, 0, s, head, cap, b.fix, ghead, out_goff, gcap);
     hipLaunchKernelGGL(k_gs_emit, g, t, 0, s, head, cap, in_topic, in_value, in_sub, b, out_gsub, out_goff, gcap,
                        out_topic, out_value, out_sub, out_perm);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_picks(const FanoutScratch &fs, const uint64_t *head, const uint32_t *in_topic,
+                              const uint32_t *in_value, const uint32_t *in_sub, uint64_t cap, uint32_t n_dests,
+                              const uint64_t *dest_offsets, const uint32_t *e_topic, const uint32_t *e_value,
+                              const uint32_t *member, uint64_t ecap, const uint32_t *sub_of, uint64_t sub_of_len,
+                              uint64_t *ghead, uint32_t *out_gsub, uint64_t *out_goff, uint64_t gcap, uint32_t *out_topic,
+                              uint32_t *out_value, uint32_t *out_sub, uint32_t *out_src, uint64_t out_cap,
+                              uint32_t msg_passes, hipStream_t s) {
+    if (!head || !dest_offsets || !ghead || !out_goff ||
+        (((uintptr_t)head | (uintptr_t)dest_offsets | (uintptr_t)ghead | (uintptr_t)out_goff) & 7))
+        return hipErrorInvalidValue;
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;
+    if (ecap > 0xFFFFFFFFull) ecap = 0xFFFFFFFFull;
+    if (out_cap > 0xFFFFFFFFull) out_cap = 0xFFFFFFFFull;
+    const uint64_t all = cap + ecap;
+    if (all > 0xFFFFFFFFull || !n_dests || n_dests > FO_MAX_DESTS || sub_of_len > 0xFFFFFFFFull ||
+        (sub_of_len && !sub_of))
+        return hipErrorInvalidValue;
+    if (!fs.gs_fix || !fs.gp_fix || all > fs.gs_cap || all > fs.gp_cap || ecap > fs.gp_ecap ||
+        (all && !fs.gs_k[0]) || (cap && (!in_topic || !in_value || !in_sub)) ||
+        (ecap && (!e_topic || !e_value || !member)) || (out_cap && (!out_topic || !out_value || !out_sub)) ||
+        (gcap && !out_gsub))
+        return hipErrorInvalidValue;
+    const GsBufs b{fs.gs_fix, {fs.gs_k[0], fs.gs_k[1]}, {fs.gs_p[0], fs.gs_p[1]}};
+    uint32_t *gfix = fs.gp_fix;
+    const uint64_t *ph = reinterpret_cast<const uint64_t *>(gfix + GP_PH);
+    const uint64_t *mh = reinterpret_cast<const uint64_t *>(gfix + GP_MH);
+    uint32_t *mt = fs.gp_m[0], *mv = fs.gp_m[1], *ms = fs.gp_m[2], *msrc = fs.gp_m[3];
+    uint32_t *pt = fs.gp_c[0], *pv = fs.gp_c[1], *ps = fs.gp_c[2];
+    const dim3 g(GS_GRID), t(GS_BLOCK), one(1), wide(1024);
+    hipLaunchKernelGGL(k_gp_count, g, t, 0, s, n_dests, dest_offsets, ecap, member, sub_of, sub_of_len, gfix);
+    hipLaunchKernelGGL(k_gp_scan, one, wide, 0, s, head, cap, gfix);
+    hipLaunchKernelGGL(k_gp_compact, g, t, 0, s, n_dests, dest_offsets, ecap, e_topic, e_value, member, sub_of,
+                       sub_of_len, gfix, pt, pv, ps);
+    // the P picks by message
+    hipLaunchKernelGGL(k_gs_pre, g, t, 0, s, ph, ecap, pt, b.fix);
+    hipLaunchKernelGGL(k_gs_plan, one, wide, 0, s, ph, ecap, b.fix);
+    // (a digit above the caller's bound on the topic indices is one all picks agree on: k_gs_plan skips
+    // it, the pass's three kernels would return at once and are not queued)
+    for (uint32_t p = 0; p < GS_PASSES && p < msg_passes; p++) {
+        hipLaunchKernelGGL(k_gs_hist, g, t, 0, s, ph, ecap, pt, b, p);
+        hipLaunchKernelGGL(k_gs_scan, dim3(GS_BINS), t, 0, s, ph, ecap, b.fix, p);
+        hipLaunchKernelGGL(k_gs_scatter, g, t, 0, s, ph, ecap, pt, b, p);
+    }
+    hipLaunchKernelGGL(k_gp_merge, g, t, 0, s, head, cap, in_topic, in_value, in_sub, ecap, b, gfix, pt, pv, ps, mt, mv,
+                       ms, msrc);
+    // the N merged deliveries by subscriber
+    hipLaunchKernelGGL(k_gs_pre, g, t, 0, s, mh, all, ms, b.fix);
+    hipLaunchKernelGGL(k_gs_plan, one, wide, 0, s, mh, all, b.fix);
+    for (uint32_t p = 0; p < GS_PASSES; p++) {
+        hipLaunchKernelGGL(k_gs_hist, g, t, 0, s, mh, all, ms, b, p);
+        hipLaunchKernelGGL(k_gs_scan, dim3(GS_BINS), t, 0, s, mh, all, b.fix, p);
+        hipLaunchKernelGGL(k_gs_scatter, g, t, 0, s, mh, all, ms, b, p);
+    }
+    hipLaunchKernelGGL(k_gs_heads, g, t, 0, s, mh, all, ms, b);
+    hipLaunchKernelGGL(k_gs_gscan, one, wide, 0, s, mh, all, b.fix, ghead, out_goff, gcap);
+    hipLaunchKernelGGL(k_gp_emit, g, t, 0, s, mh, all, mt, mv, ms, msrc, b, out_gsub, out_goff, gcap, out_topic, out_value,
+                       out_sub, out_src, out_cap);
     return hipGetLastError();
 }
 

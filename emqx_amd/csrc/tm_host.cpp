@@ -318,6 +318,11 @@ struct tm_index {
     SubPool share_h;
     DestDev share_slot[MAX_REPLICAS], share_rec[MAX_REPLICAS], share_pool[MAX_REPLICAS];
     struct ShareState { uint32_t *d = nullptr; uint64_t cap = 0; } share_state[MAX_REPLICAS];
+    // share member id -> local subscriber id (tm_set_member_subs; NONE: not a
+    // connection of this node): kept exactly as the destinations are, under
+    // the same lock (table_upload)
+    std::vector<uint32_t> msub_h;
+    DestDev msub[MAX_REPLICAS];
 
     // caller buffers from tm_host_alloc (host address -> size, device address;
     // vram: TM_ALLOC_VRAM device memory, the same address on both sides)
@@ -1831,7 +1836,7 @@ void free_lane(Lane &l) {
     void *dv[] = {l.d_in, l.d_res, l.d_vals, l.d_o64, l.d_h64, l.f.tab, l.f.tot, l.f.t, l.f.v, l.f.b, l.f.voff, l.f.sums, l.f.b2,
                   l.d_ft, l.d_fv, l.d_fo, l.d_pr, l.f.ag_bits, l.f.ag_pre, l.f.ag_cnt, l.d_at, l.d_av, l.d_ao, l.fo1_s,
                   l.f.dp_cnt, l.f.dp_off, l.f.dp_tot, l.d_dt, l.d_dv, l.d_ds, l.f.sh_key, l.f.sh_cnt, l.d_sm, l.d_sk,
-                  l.f.gs_fix, l.f.gs_k[0], l.d_gt, l.d_gv, l.d_gs, l.d_gsub, l.d_goff};
+                  l.f.gs_fix, l.f.gs_k[0], l.f.gp_fix, l.d_gt, l.d_gv, l.d_gs, l.d_gsub, l.d_goff};
     for (void *p : dv) if (p) (void)hipFree(p);
     void *pins[] = {l.pin_in, l.pin_out, l.pin_vals, l.fo1_h};
     for (void *p : pins) if (p) (void)hipHostFree(p);
@@ -2176,7 +2181,7 @@ struct HostBatch {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 21u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 22u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 
@@ -2292,7 +2297,7 @@ int tm_destroy(tm_index *ix) {
         for (int r = 0; r < ix->nrep; r++)
             if (ix->rep[r].group == g) { (void)hipSetDevice(ix->rep[r].device); break; }
         for (auto *D : {&ix->dest[g], &ix->filt[g], &ix->sub_pool[g], &ix->sub_span[g], &ix->share_slot[g],
-                        &ix->share_rec[g], &ix->share_pool[g]}) {
+                        &ix->share_rec[g], &ix->share_pool[g], &ix->msub[g]}) {
             if (D->d) (void)hipFree(D->d);
             if (D->pin) (void)hipHostFree(D->pin);
             if (D->ev) (void)hipEventDestroy(D->ev);
@@ -2795,6 +2800,37 @@ int ensure_group(tm_index *ix, Lane &ln, uint64_t cap, const char *who) {
     return TM_OK;
 }
 
+// the scratch of the picks' merge on a lane (grow-only; freed with the lane):
+// one allocation -- the fixed words, four merged arrays below `all` (cap +
+// ecap), three compacted pick arrays below ecap
+int ensure_group_picks(tm_index *ix, Lane &ln, uint64_t all, uint64_t ecap, const char *who) {
+    FanoutScratch &f = ln.f;
+    if (f.gp_fix && all <= f.gp_cap && ecap <= f.gp_ecap) return TM_OK;
+    HIPCHK(ix, hipStreamSynchronize(ln.s));   // only this lane's stream uses them
+    if (f.gp_fix) (void)hipFree(f.gp_fix);
+    f.gp_fix = nullptr;
+    const uint64_t c = std::max<uint64_t>({std::min<uint64_t>(all + all / 4, 0xFFFFFFFFull), f.gp_cap, 4096});
+    const uint64_t e = std::max<uint64_t>({std::min<uint64_t>(ecap + ecap / 4, 0xFFFFFFFFull), f.gp_ecap, 4096});
+    f.gp_cap = f.gp_ecap = 0;
+    const uint64_t fixw = ((uint64_t)GP_FIX_WORDS + 63) & ~63ull;
+    if (hipMalloc(&f.gp_fix, (fixw + 4 * c + 3 * e) * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        f.gp_fix = nullptr;
+        return fail(ix, TM_ENOMEM, std::string(who) + ": no device memory for the merge's arrays (16 bytes x (cap + ecap) "
+                                                      "and 12 bytes x ecap)");
+    }
+    for (int i = 0; i < 4; i++) f.gp_m[i] = f.gp_fix + fixw + (uint64_t)i * c;
+    for (int i = 0; i < 3; i++) f.gp_c[i] = f.gp_fix + fixw + 4 * c + (uint64_t)i * e;
+    f.gp_cap = c;
+    f.gp_ecap = e;
+    return TM_OK;
+}
+
+// the index's member -> local subscriber table (tm_set_member_subs) on group g
+int msub_upload(tm_index *ix, int g, hipStream_t s, const uint32_t *&d, uint64_t &len) {
+    return table_upload(ix, ix->msub_h, ix->msub[g], g, s, d, len);
+}
+
 // the passes the live lanes' grouping calls ran (which 0) / skipped (1) so far
 // (caller holds ix->mu; waits for nothing: a call still in flight is not counted)
 int group_passes(tm_index *ix, int which, uint64_t &out) {
@@ -2951,6 +2987,14 @@ int tm_set_dests(tm_index *ix, uint64_t n, const uint32_t *values, const uint32_
                      "tm_set_dests: out of host memory (the table has one entry per value up to the largest)");
 }
 
+int tm_set_member_subs(tm_index *ix, uint64_t n, const uint32_t *members, const uint32_t *sub_ids) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_set_member_subs: null handle");
+    if (n && (!members || !sub_ids)) return fail(ix, TM_EINVAL, "tm_set_member_subs: null buffer");
+    if (!n) return TM_OK;
+    return table_set(ix, ix->msub_h, ix->msub, n, members, sub_ids,
+                     "tm_set_member_subs: out of host memory (the table has one entry per member id up to the largest)");
+}
+
 int tm_set_route_filters(tm_index *ix, uint64_t n, const uint32_t *values, const uint32_t *filter_ids) {
     if (!ix) return fail(nullptr, TM_EINVAL, "tm_set_route_filters: null handle");
     if (n && (!values || !filter_ids)) return fail(ix, TM_EINVAL, "tm_set_route_filters: null buffer");
@@ -3041,6 +3085,39 @@ int tm_group_subs_dev(tm_index *ix, const uint64_t *head, const uint32_t *topic,
     if ((rc = ensure_group(ix, *b.ln, cap, "tm_group_subs_dev"))) return rc;
     HIPCHK(ix, launch_group_subs(b.ln->f, head, topic, value, sub, cap, out_ghead, out_gsub, out_goff, gcap, out_topic,
                                  out_value, out_sub, out_perm, b.s));
+    return b.done();
+}
+
+int tm_group_picks_dev(tm_index *ix, const uint64_t *head, const uint32_t *topic, const uint32_t *value,
+                       const uint32_t *sub, uint64_t cap, uint32_t n_dests, const uint64_t *dest_offs,
+                       const uint32_t *etopic, const uint32_t *evalue, const uint32_t *member, uint64_t ecap,
+                       const uint32_t *sub_of, uint64_t sub_of_len, uint64_t *out_ghead, uint32_t *out_gsub,
+                       uint64_t *out_goff, uint64_t gcap, uint32_t *out_topic, uint32_t *out_value, uint32_t *out_sub,
+                       uint32_t *out_src, uint64_t out_cap, void *stream) {
+    if (!ix) return fail(nullptr, TM_EINVAL, "tm_group_picks_dev: null handle");
+    if (!n_dests || n_dests > FO_MAX_DESTS) return fail(ix, TM_EINVAL, "tm_group_picks_dev: n_dests must be 1 .. 65536");
+    if (cap > 0xFFFFFFFFull) cap = 0xFFFFFFFFull;   // (32-bit positions)
+    if (ecap > 0xFFFFFFFFull) ecap = 0xFFFFFFFFull;
+    if (out_cap > 0xFFFFFFFFull) out_cap = 0xFFFFFFFFull;
+    if (!head || !dest_offs || !out_ghead || !out_goff || (gcap && !out_gsub) || (cap && (!topic || !value || !sub)) ||
+        (ecap && (!etopic || !evalue || !member)) || (out_cap && (!out_topic || !out_value || !out_sub)))
+        return fail(ix, TM_EINVAL, "tm_group_picks_dev: null buffer");
+    if ((uintptr_t)head & 7) return fail(ix, TM_EINVAL, "tm_group_picks_dev: d_head must be 8-byte aligned");
+    if ((uintptr_t)dest_offs & 7) return fail(ix, TM_EINVAL, "tm_group_picks_dev: d_dest_offsets must be 8-byte aligned");
+    if ((uintptr_t)out_ghead & 7) return fail(ix, TM_EINVAL, "tm_group_picks_dev: d_out_ghead must be 8-byte aligned");
+    if ((uintptr_t)out_goff & 7) return fail(ix, TM_EINVAL, "tm_group_picks_dev: d_out_goff must be 8-byte aligned");
+    if (sub_of && sub_of_len > 0xFFFFFFFFull) return fail(ix, TM_EINVAL, "tm_group_picks_dev: more than 2^32 - 1 members");
+    if (cap + ecap > 0xFFFFFFFFull)
+        return fail(ix, TM_EINVAL, "tm_group_picks_dev: cap + ecap must be at most 2^32 - 1 (32-bit positions)");
+    DevBatch b(ix, stream);
+    int rc;
+    if ((rc = b.open_fanout())) return rc;
+    if ((rc = ensure_group(ix, *b.ln, cap + ecap, "tm_group_picks_dev"))) return rc;
+    if ((rc = ensure_group_picks(ix, *b.ln, cap + ecap, ecap, "tm_group_picks_dev"))) return rc;
+    if (!sub_of && (rc = msub_upload(ix, b.grp, b.s, sub_of, sub_of_len))) return rc;
+    HIPCHK(ix, launch_group_picks(b.ln->f, head, topic, value, sub, cap, n_dests, dest_offs, etopic, evalue, member, ecap,
+                                  sub_of, sub_of_len, out_ghead, out_gsub, out_goff, gcap, out_topic, out_value, out_sub,
+                                  out_src, out_cap, GS_PASSES, b.s));
     return b.done();
 }
 
@@ -3962,7 +4039,8 @@ static int copy_route_out(tm_index *ix, Lane &ln, uint32_t n_dests, uint64_t tot
 // One request of the route family (tm_route_batch, tm_dispatch_batch,
 // tm_publish_batch and their 32-bit forms): everything the six entry points
 // share.  dp / pk / gp: the dispatch, the pick and the grouping of the
-// deliveries (tm_deliver_batch; with dp only), null when the call has none.
+// deliveries (tm_deliver_batch; with dp only), null when the call has none;
+// pk and gp together: tm_publish_deliver_batch, the local picks merged in.
 // who: the entry point the caller called -- every refusal and failure names
 // it.  Only the topic offsets and out_dest_offsets differ in width; they travel
 // beside the request.
@@ -3997,7 +4075,8 @@ static int copy_group_out(tm_index *ix, Lane &ln, const RouteReq &rq, const uint
     const RouteDispatch *dp = rq.dp;
     const RouteGroup *gp = rq.gp;
     const uint64_t dcap = std::min<uint64_t>(dp->dcap, 0xFFFFFFFFull);
-    const uint64_t keep = std::min(head[1], dcap), gkeep = std::min(head[2], gp->gcap);
+    // (behind a pick the grouped arrays hold the N = head[3] merged deliveries)
+    const uint64_t keep = std::min(rq.pk ? head[3] : head[1], dcap), gkeep = std::min(head[2], gp->gcap);
     static thread_local std::vector<uint64_t> wide;
     uint64_t *goff = gp->out_goff;
     if (!goff) {
@@ -4056,11 +4135,40 @@ static int route_check(tm_index *ix, const RouteReq &rq, bool offsets, bool narr
 // whose caller has the `kept` entries: queued now, ONCE, over the arrays still
 // in the lane -- the state words move once, and only for entries the caller
 // gets.  Only the copy of its own output can fail after it.
-static int pick_after_run(tm_index *ix, HostBatch &hb, const RouteReq &rq, uint64_t vcap, uint64_t kept) {
+// gm (tm_publish_deliver_batch): behind the pick, in the same hold of the lock
+// and on the same lane, the picks are merged with the lane's gm->T deliveries
+// (d_head = [M, T] on the device) and grouped into the lane's group arrays,
+// d_head[2..3] = [G, N]; gm->fetch: d_head is not mapped host memory, its four
+// words are copied to gm->pin.  Every scratch is had BEFORE the pick is queued:
+// a call that runs out of memory has moved no state.
+struct PickMerge {
+    uint64_t *d_head, T, gcap;
+    uint8_t *pin;
+    bool fetch;
+};
+
+static int pick_after_run(tm_index *ix, HostBatch &hb, const RouteReq &rq, uint64_t vcap, uint64_t kept,
+                          const PickMerge *gm = nullptr) {
     int rc;
     Lane &ln = *hb.ln;
     if ((rc = hb.relock())) return rc;
+    const uint32_t *sub_of = nullptr;
+    uint64_t sub_of_len = 0;
+    // (a topic index is below n: the digits the picks' sort by message can need)
+    const uint32_t msg_passes = rq.n <= 0x100 ? 1 : rq.n <= 0x10000 ? 2 : rq.n <= 0x1000000 ? 3 : GS_PASSES;
+    if (gm) {
+        if ((rc = group_scratch(ix, ln, gm->T + kept, gm->gcap, rq.who))) return rc;
+        if ((rc = ensure_group_picks(ix, ln, gm->T + kept, kept, rq.who))) return rc;
+        if ((rc = msub_upload(ix, ix->rep[ln.r].group, ln.s, sub_of, sub_of_len))) return rc;
+    }
     if ((rc = queue_pick(ix, ln, rq.n, rq.n_dests, vcap, *rq.pk))) return rc;
+    if (gm) {
+        HIPCHK(ix, launch_group_picks(ln.f, gm->d_head, ln.d_dt, ln.d_dv, ln.d_ds, gm->T, rq.n_dests, ln.d_ao, ln.d_at,
+                                      ln.d_av, ln.d_sm, kept, sub_of, sub_of_len, gm->d_head + 2, ln.d_gsub, ln.d_goff,
+                                      std::min(gm->gcap, gm->T + kept), ln.d_gt, ln.d_gv, ln.d_gs, nullptr,
+                                      gm->T + kept, msg_passes, ln.s));
+        if (gm->fetch) HIPCHK(ix, hipMemcpyAsync(gm->pin, gm->d_head, 32, hipMemcpyDeviceToHost, ln.s));
+    }
     if ((rc = batch_done(ix, ln))) return rc;
     hb.g.unlock();
     // (the copy may wait for the stream: never under the lock.  out_member is
@@ -4087,12 +4195,18 @@ static int pick_after_run(tm_index *ix, HostBatch &hb, const RouteReq &rq, uint6
 // lane's group arrays hold min(gcap, deliveries) groups, so nothing but the
 // dispatch's own retry ever queues it again.
 // pk (tm_publish_batch): pick_after_run, when the kept entries fit.
+// pk and gp (tm_publish_deliver_batch): the run queues no grouping; when the
+// kept entries fit and T + K <= dcap (both known here, K bounds the local
+// picks), pick_after_run queues the pick and behind it the merge of the local
+// picks with the lane's deliveries and their grouping, and the copies out read
+// the merged arrays.  Otherwise TM_ECAP with no pick made and no state moved.
 static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to, uint64_t *out_dest_offsets) {
     const uint64_t n = rq.n, cap = rq.cap;
     const uint32_t n_dests = rq.n_dests;
     const bool aggre = rq.aggre();
     const RouteDispatch *dp = rq.dp;
     const RouteGroup *gp = rq.gp;
+    const bool merge = gp && rq.pk;   // tm_publish_deliver_batch: the grouping waits for the pick
     HostBatch hb(ix, rq.who);
     int rc;
     if ((rc = hb.open(n))) return rc;
@@ -4120,7 +4234,7 @@ static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to
         if ((rc = grow_dev(ix, s, ln.d_vals, ln.d_vals_cap, vcap))) return rc;
         if ((rc = route_scratch(ix, ln, n_dests, vcap, aggre, false, 0))) return rc;
         if (dp && (rc = dispatch_scratch(ix, ln, vcap, dwant))) return rc;
-        if (gp && (rc = group_scratch(ix, ln, dwant, gcap, rq.who))) return rc;
+        if (gp && !merge && (rc = group_scratch(ix, ln, dwant, gcap, rq.who))) return rc;
         rc = hb.run([&](const DevIndex &d, uint32_t tag) -> int {
             int path = PATH_PHASES;
             HIPCHK(ix, launch_match(d, ln.w, n, dbytes, doffs, dhit, derr, ln.d_vals, vcap, tag, next_lb(ix),
@@ -4131,7 +4245,7 @@ static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to
             if (dp)
                 if (int rc = queue_dispatch(ix, ln, n_dests, dp->local_dest, aggre, vcap, std::min(dwant, dcap), dhead))
                     return rc;
-            if (gp)
+            if (gp && !merge)
                 if (int rc = queue_group(ix, ln, dhead, std::min(dwant, dcap), gcap, dhead + 2)) return rc;
             return fetch_out(ix, ln, n, rbytes);
         });
@@ -4152,9 +4266,9 @@ static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to
             dwant = std::min(head[1] + head[1] / 4, dcap);
             if ((rc = hb.relock())) return rc;
             if ((rc = dispatch_scratch(ix, ln, vcap, dwant))) return rc;
-            if (gp && (rc = group_scratch(ix, ln, dwant, gcap, rq.who))) return rc;
+            if (gp && !merge && (rc = group_scratch(ix, ln, dwant, gcap, rq.who))) return rc;
             if ((rc = queue_dispatch(ix, ln, n_dests, dp->local_dest, aggre, vcap, dwant, dhead))) return rc;
-            if (gp && (rc = queue_group(ix, ln, dhead, dwant, gcap, dhead + 2))) return rc;
+            if (gp && !merge && (rc = queue_group(ix, ln, dhead, dwant, gcap, dhead + 2))) return rc;
             if (n > ZC_TOPICS) HIPCHK(ix, hipMemcpyAsync(ln.pin_out + hoff, dhead, hbytes, hipMemcpyDeviceToHost, s));
             if ((rc = batch_done(ix, ln))) return rc;
             hb.g.unlock();
@@ -4166,6 +4280,19 @@ static int route_batch_impl(tm_index *ix, const RouteReq &rq, const uint64_t *to
                         rq.out_values);
     if (rc != TM_OK && rc != TM_ECAP) return rc;
     if (rq.out_err && n) std::memcpy(rq.out_err, ln.pin_out + (n + 1) * 8, n);
+    if (merge) {
+        // no pick unless the caller gets every entry and every merged delivery: K bounds the local picks
+        const uint64_t kept = rc == TM_OK ? std::min(out_dest_offsets[n_dests + 1], cap) : 0;
+        dp->out_head[0] = head[0];
+        dp->out_head[1] = head[1];
+        gp->out_ghead[0] = gp->out_ghead[1] = 0;
+        if (rc != TM_OK || head[1] + kept > dp->dcap || head[1] + kept > 0xFFFFFFFFull) return TM_ECAP;
+        const PickMerge gm{dhead, head[1], gcap, ln.pin_out + hoff, n > ZC_TOPICS};
+        if (int prc = pick_after_run(ix, hb, rq, vcap, kept, &gm)) return prc;
+        std::memcpy(head, ln.pin_out + hoff, hbytes);
+        if (int grc = copy_group_out(ix, ln, rq, head)) return grc;
+        return head[2] > gcap ? TM_ECAP : TM_OK;
+    }
     if (rq.pk && aggre && total <= cap)
         if (int prc = pick_after_run(ix, hb, rq, vcap, std::min(out_dest_offsets[n_dests + 1], cap))) return prc;
     if (gp) {
@@ -4235,6 +4362,19 @@ int tm_publish_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t
     const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
     const RoutePick pk{key_clientid, key_topic, seed, out_member};
     const RouteReq rq{"tm_publish_batch", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, &dp, &pk};
+    return route_batch64(ix, rq, to, out_dest_offsets);
+}
+
+int tm_publish_deliver_batch(tm_index *ix, uint64_t n, const uint8_t *tb, const uint64_t *to, uint32_t n_dests,
+                             uint32_t local_dest, uint32_t flags, uint64_t *out_dest_offsets, uint32_t *out_topic,
+                             uint32_t *out_values, uint64_t cap, uint64_t *out_head, uint32_t *out_dtopic,
+                             uint32_t *out_dvalue, uint32_t *out_dsub, uint64_t dcap, const uint32_t *key_clientid,
+                             const uint32_t *key_topic, uint32_t seed, uint32_t *out_member, uint64_t *out_ghead,
+                             uint32_t *out_gsub, uint64_t *out_goff, uint64_t gcap, uint8_t *out_err) {
+    const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
+    const RoutePick pk{key_clientid, key_topic, seed, out_member};
+    const RouteGroup gp{out_ghead, out_gsub, out_goff, gcap};
+    const RouteReq rq{"tm_publish_deliver_batch", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, &dp, &pk, &gp};
     return route_batch64(ix, rq, to, out_dest_offsets);
 }
 

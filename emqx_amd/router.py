@@ -275,6 +275,9 @@ class Router:
             mirror.filter_release = self.filter_release
         if hasattr(mirror, "sub_fn") and self.local_subs is not None:
             mirror.sub_fn = self._key_subs
+        if hasattr(mirror, "member_subs_fn") and self.shared_subs is not None and self.local_subs is not None:
+            # (ahead of the member lists below: the mirror asks for every member id it is given)
+            mirror.member_subs_fn = self._member_sub
         if hasattr(mirror, "share_fn") and self.shared_subs is not None:
             mirror.share_fn = self._key_slot
             mirror.share_release = self._key_slot_release
@@ -385,6 +388,85 @@ class Router:
         kc = None if key_clientid is None else np.ascontiguousarray(key_clientid, dtype=np.uint32)
         kt = None if key_topic is None else np.ascontiguousarray(key_topic, dtype=np.uint32)
         return self._routes_by_dest(topics, errors, True, True, publish=(kc, kt, seed))
+
+    def member_is_local(self, pid) -> bool:
+        """a group member that is a connection of this node: its picks arrive in by_sub"""
+        return self.shared_subs.node_of(pid) == self.node
+
+    def _member_sub(self, member_id):
+        """The mirror's member_subs_fn: the local subscriber id of a share member
+        (SharedSubs' interned pid) whose node_of is this node, None for any other."""
+        ss = self.shared_subs
+        if member_id >= len(ss.pids) or not self.member_is_local(ss.pids[member_id]):
+            return None
+        return self.local_subs.sub_id(ss.pids[member_id])
+
+    def match_routes_publish_deliver(self, topics, key_clientid=None, key_topic=None, seed: int = 0,
+                                     errors: str = "raise"):
+        """match_routes_publish with the local picks grouped with the deliveries
+        on the device (tm_publish_deliver_batch; route_in_place takes the same
+        staged call for now) -> (ByDest, deliveries, picks, by_sub): the first
+        three are exactly match_routes_publish's; by_sub = {pid: [(message
+        index, To)]} holds a connection's direct deliveries and the picks that
+        fell on it (member_is_local) together, in publish order -- inside a
+        message the direct deliveries first, in match_routes_deliver's order,
+        then the picks in the order `picks` lists them.  The bag's exact-topic
+        rows and their host picks are merged in here.  Needs local_subs and
+        shared_subs."""
+        if self.local_subs is None or self.shared_subs is None:
+            raise ValueError("match_routes_publish_deliver: the router needs local_subs and shared_subs")
+        kc = None if key_clientid is None else np.ascontiguousarray(key_clientid, dtype=np.uint32)
+        kt = None if key_topic is None else np.ascontiguousarray(key_topic, dtype=np.uint32)
+        return self._routes_by_dest(topics, errors, True, True, publish=(kc, kt, seed), merged=True)
+
+    def _split_merged(self, mirror, grouped, groups):
+        """tm_publish_deliver_batch's merged groups taken apart by the entry's key:
+        a {Filter, {Group, Node}} key is a pick, any other a direct delivery ->
+        (the direct deliveries still grouped, their (subscribers, offsets), the
+        picks as {sub id: [(message index, group, To)]} in device order)."""
+        gt, gk = grouped[0].tolist(), grouped[1].tolist()
+        gsub, goff = groups[0].tolist(), groups[1].tolist()
+        mk = mirror._keys
+        keep, d_gsub, d_goff, pick_groups = [], [], [0], {}
+        for g, sub in enumerate(gsub):
+            n0 = len(keep)
+            for j in range(goff[g], goff[g + 1]):
+                key = mk[gk[j]] if gk[j] < len(mk) else None
+                dest = ti.get_id(key) if key is not None else None
+                if isinstance(dest, tuple) and len(dest) == 2 and dest[0] != "external":
+                    pick_groups.setdefault(sub, []).append((gt[j], dest[0], ti.get_topic(key)))
+                else:
+                    keep.append(j)
+            if len(keep) > n0:
+                d_gsub.append(sub)
+                d_goff.append(len(keep))
+        at = np.asarray(keep, dtype=np.int64)
+        return (tuple(np.asarray(a, dtype=np.uint32)[at] for a in grouped),
+                (np.asarray(d_gsub, dtype=np.uint32), np.asarray(d_goff, dtype=np.uint64)), pick_groups)
+
+    def _merge_picks(self, by_sub, picks, host_picks, pick_groups, errors) -> dict:
+        """by_sub with the local picks: the device's (pick_groups) and the bag's
+        (host_picks), per pid and message behind the direct deliveries, in the
+        order `picks` lists them."""
+        rank = {}
+        for g, rows in picks.items():
+            for i, to, _ in rows:
+                rank.setdefault((g, i, to), len(rank))
+        extra: dict = {}   # pid -> [(message index, rank, To)]
+        for sub, rows in pick_groups.items():
+            pid = self.local_subs.pid_of(sub)
+            for i, g, to in rows:
+                if i not in errors and (g, i, to) in rank:   # (a key deleted since the batch began: dropped in picks too)
+                    extra.setdefault(pid, []).append((i, rank[(g, i, to)], to))
+        for g, rows in host_picks.items():
+            for i, to, pid in rows:
+                if pid is not None and self.member_is_local(pid):
+                    extra.setdefault(pid, []).append((i, rank[(g, i, to)], to))
+        out = dict(by_sub)
+        for pid, rows in extra.items():
+            both = [(i, 0, n, to) for n, (i, to) in enumerate(by_sub.get(pid, ()))] + [(i, 1, r, to) for i, r, to in rows]
+            out[pid] = [(i, to) for i, _, _, to in sorted(both, key=lambda e: e[:3])]
+        return out
 
     # ------------------------------------------------------ local subscribers
     def _key_subs(self, key):
@@ -738,10 +820,10 @@ class Router:
         order = [j for _, _, _, j in keyed]
         return tuple(np.asarray(a, dtype=np.uint32)[order] for a in grouped), dev_groups
 
-    def _routes_by_dest(self, topics, errors, aggre, dispatch, publish=None, grouped=False):
+    def _routes_by_dest(self, topics, errors, aggre, dispatch, publish=None, grouped=False, merged=False):
         topics = [bytes(t) for t in topics]
         member = None
-        dev_groups = None
+        dev_groups = pick_groups = None
         mirror = self._live_mirror()
         out = ByDest()
         deliveries: list = []
@@ -756,7 +838,12 @@ class Router:
             if dispatch:
                 if local == UNROUTED:
                     raise ValueError("match_routes_dispatch: this node has no destination id")
-                if publish is not None:
+                if publish is not None and merged:
+                    (doff, tidx, kids, err), mdel, member, mgrp, _ = mirror.publish_deliver_kids(topics, n_dests, local,
+                                                                                                 *publish)
+                    gdel, ggrp, pick_groups = self._split_merged(mirror, mdel, mgrp)
+                    (dt, dk, ds), dev_groups = self._ungroup(mirror, doff, tidx, kids, local, gdel, ggrp)
+                elif publish is not None:
                     pub = mirror.publish_kids32 if self._route_in_place else mirror.publish_kids
                     (doff, tidx, kids, err), (dt, dk, ds), member = pub(topics, n_dests, local, *publish)
                 elif grouped:
@@ -883,10 +970,14 @@ class Router:
         if publish is None:
             return out, deliveries
         picks = self._host_picks(topics, out.errors, *publish)
+        host_picks = {g: list(rows) for g, rows in picks.items()} if merged else None
         for g, rows in dev_picks.items():
             picks.setdefault(g, []).extend(rows)
         for g in picks:
             picks[g].sort(key=lambda e: e[0])   # (stable: a message's bag row stays first)
+        if merged:
+            by_sub = self._by_sub(mirror, topics, out.errors, dev_groups)
+            return out, deliveries, picks, self._merge_picks(by_sub, picks, host_picks, pick_groups, out.errors)
         return out, deliveries, picks
 
     def _by_sub(self, mirror, topics, errors, dev_groups) -> dict:

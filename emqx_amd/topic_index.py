@@ -95,6 +95,13 @@ class Tab:
         self._with_share: set = set()   # kids whose device slot is not "none"
         self._share_members: list = []  # pending (slot, [member ids], n_local, meta)
         self._share_states: list = []   # pending (slot, state word)
+        # picks grouped with the deliveries: member_subs_fn(member id) -> the local subscriber
+        # id of a share member (None: not a connection of this node), asked for every member
+        # id set_share_members queues whose answer differs from what was shipped, and shipped
+        # with tm_set_member_subs in the same flush, ahead of the members
+        self.member_subs_fn = None
+        self._member_subs: list = []    # pending (member id, subscriber id)
+        self._member_sub_of: dict = {}  # member id -> subscriber id as shipped or queued
         self._route_pool: list = []     # route_kids32: idle sets of pinned batch buffers (host_array)
 
     # -- key <-> device encoding
@@ -148,6 +155,10 @@ class Tab:
         if self._subs:
             subs, self._subs = self._subs, []
             self._index.set_subscribers([k for k, _ in subs], [ids for _, ids in subs])
+        if self._member_subs:
+            ms = np.array(self._member_subs, dtype=np.uint32).reshape(-1, 2)
+            self._member_subs = []
+            self._index.set_member_subs(ms[:, 0], ms[:, 1])
         if self._share_members:
             mem, self._share_members = self._share_members, []
             self._index.set_share_members([m[0] for m in mem], [m[1] for m in mem], [m[2] for m in mem],
@@ -259,7 +270,23 @@ class Tab:
         tm_set_share_members at the next flush -- ahead of the slots and the
         inserts of that flush.  A slot queued twice ships its last list."""
         with self._lock:
-            self._share_members.append((int(slot), [int(x) for x in member_ids], int(n_local), int(meta)))
+            ids = [int(x) for x in member_ids]
+            if self.member_subs_fn is not None:
+                for m in ids:
+                    sub = self.member_subs_fn(m)
+                    sub = _native.TM_SHARE_NONE if sub is None else int(sub)
+                    if self._member_sub_of.get(m, _native.TM_SHARE_NONE) != sub:
+                        self._member_sub_of[m] = sub
+                        self._member_subs.append((m, sub))
+            self._share_members.append((int(slot), ids, int(n_local), int(meta)))
+
+    def set_member_sub(self, member_id: int, sub_id):
+        """Share member `member_id` is local subscriber `sub_id` (None: not a
+        connection of this node), shipped with tm_set_member_subs at the next flush."""
+        with self._lock:
+            sub = _native.TM_SHARE_NONE if sub_id is None else int(sub_id)
+            self._member_sub_of[int(member_id)] = sub
+            self._member_subs.append((int(member_id), sub))
 
     def set_share_state(self, slot: int, state: int):
         """Slot `slot`'s state word becomes `state` on every device entry
@@ -281,6 +308,19 @@ class Tab:
         blob, offs = _native.pack_strings(topics)
         return self._index.publish_batch(blob, offs, n_dests, local_dest, key_clientid=key_clientid,
                                          key_topic=key_topic, seed=seed)
+
+    def publish_deliver_kids(self, topics, n_dests: int, local_dest: int, key_clientid=None, key_topic=None,
+                             seed: int = 0):
+        """tm_publish_deliver_batch -> (route_kids' result, (topic index, kid,
+        subscriber id) u32[N] -- the direct deliveries and the picks whose
+        member is a local subscriber (member_subs_fn / set_member_sub), merged
+        by message and GROUPED by subscriber id --, member id u32[K] as
+        publish_kids, (subscriber id u32[G], offsets u64[G + 1]), T the number
+        of direct deliveries among the N)."""
+        self.flush()
+        blob, offs = _native.pack_strings(topics)
+        return self._index.publish_deliver_batch(blob, offs, n_dests, local_dest, key_clientid=key_clientid,
+                                                 key_topic=key_topic, seed=seed)
 
     def attach(self, rows, batch_size: int = 1000) -> int:
         """Boot the device mirror from an existing table (emqx_topic_index_gpu:

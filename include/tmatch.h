@@ -989,6 +989,116 @@ int tm_deliver_batch32(tm_index *h, uint64_t n, const uint8_t *topic_bytes, cons
                        uint64_t dcap, uint64_t *out_ghead, uint32_t *out_gsub, uint32_t *out_goff, uint64_t gcap,
                        uint8_t *out_err);
 
+/* Shared-subscription picks grouped with the deliveries (ABI minor 22).  One
+ * connection process receives both kinds of delivery in one mailbox: {deliver,
+ * To, Msg} from do_dispatch2/2 (emqx_broker.erl:726-760) and from the shared
+ * dispatch/3 (emqx_shared_sub.erl:146-163).  tm_publish_batch leaves its
+ * deliveries in message order and makes the picks; tm_deliver_batch groups by
+ * subscriber and makes no pick.  The calls below close the chain: one list per
+ * local subscriber, direct and picked deliveries together, in publish order.
+ *
+ * tm_set_member_subs: the index's share member id -> local subscriber id table,
+ * a twin of tm_set_dests (same thread safety, upload discipline and errors).
+ * Member ids are tm_set_share_members', subscriber ids tm_set_subscribers'.
+ * TM_SHARE_NONE (0xFFFFFFFF): not a connection of this node, and so is a member
+ * never set -- such a pick stays a pick in out_member for the host to forward
+ * and is never a local delivery.  A local subscriber whose id is 0xFFFFFFFF can
+ * therefore not be the target of a merged pick; direct deliveries may still
+ * carry that id, as in tm_group_subs_dev.
+ *
+ * tm_group_picks_dev: device buffers, asynchronous on `stream`.  d_head,
+ * d_topic, d_value, d_sub and cap are what tm_dispatch_dev wrote (the
+ * deliveries in ascending message order, as it writes them: the merge searches
+ * them); n_dests, d_dest_offsets, d_etopic, d_evalue and ecap what tm_aggre_dev
+ * wrote; d_member what tm_share_pick_dev wrote.  d_head and the offsets are
+ * read on the device, so the call chains behind tm_dispatch_dev and
+ * tm_share_pick_dev with no host synchronisation.  d_sub_of == NULL: the
+ * index's own tm_set_member_subs table (sub_of_len is then ignored).  cap, ecap
+ * and out_cap are clamped to 2^32 - 1.  In numpy:
+ *   W = min(head[1], cap);  E = min(doff[n_dests + 1], ecap)
+ *   m  = member[:E]
+ *   ls = where(m < sub_of_len, sub_of[m], NONE)          # NONE = 0xFFFFFFFF: no pick, or not local
+ *   pq = nonzero(ls != NONE)[0];  P = len(pq);  N = W + P
+ *   t = concatenate(topic[:W], etopic[pq]);  v = concatenate(value[:W], evalue[pq]);  s = concatenate(sub[:W], ls[pq])
+ *   p = lexsort((t, s))            # by subscriber, then by message, then by place in the concatenation: stable
+ *   out_topic, out_value, out_sub, out_src = t[p], v[p], s[p], p      -- the first min(N, out_cap); out_src when given
+ *   gs, cnt = unique(s, return_counts=True);  G = len(gs);  Gw = min(G, gcap)
+ *   out_gsub[:Gw] = gs[:Gw];  out_goff[0..Gw] = concatenate([0], cumsum(cnt))[:Gw + 1];  ghead = [G, N]
+ * Inside a subscriber's list the messages ascend; inside one message the direct
+ * deliveries come first in their input order, then that message's picks in
+ * ascending entry position.  out_src[j] < W names a direct delivery, out_src[j]
+ * >= W is W + the pick's rank among the local picks.  (The order of several
+ * deliveries of one message to one subscriber has no meaning in MQTT; the rule
+ * only has to be fixed.)  With P = 0 every output equals tm_group_subs_dev's
+ * for the same deliveries.  Nothing at or past min(N, out_cap) is written in
+ * the four per-delivery outputs, nothing at or past Gw in d_out_gsub and
+ * nothing past d_out_goff[Gw] (entry 0 is written whatever gcap is); ghead is
+ * exact whatever the caps are; the inputs are not modified; no delivery
+ * position >= W, no entry position >= E and no d_sub_of word >= sub_of_len is
+ * read.  The outputs MUST NOT overlap the inputs.  Steps, each a launch of its
+ * own over a fixed grid, no block waiting for another: the local picks are
+ * flagged (member, then sub_of), counted per block (ballot, popcount), the
+ * counts scanned, and (topic, value, subscriber) compacted in ascending entry
+ * position; the P picks are sorted stably by message with tm_group_subs_dev's
+ * 8-bit digit passes (a digit all agree on skipped: a batch of at most 256
+ * messages costs one pass); picks and deliveries are merged by message through
+ * two binary searches on sorted arrays; tm_group_subs_dev's passes then sort
+ * the merged deliveries by subscriber.  TM_DEBUG_GROUP_PASSES_RUN / _SKIPPED
+ * count both sorts' passes.  The stream's scratch (kept with the fan-out's,
+ * tm_stream_release) holds 32 bytes x (cap + ecap), 12 bytes x ecap and 1.1
+ * MiB (TM_ENOMEM if that cannot be had).  It is sized from cap + ecap, never
+ * from counts only the device knows: pass the sizes of the buffers.  TM_EINVAL
+ * before any device work: a null handle, a null required pointer (d_head,
+ * d_dest_offsets, d_out_ghead, d_out_goff; the three delivery arrays when cap >
+ * 0; d_etopic, d_evalue and d_member when ecap > 0; the three outputs when
+ * out_cap > 0; d_out_gsub when gcap > 0), n_dests == 0 or n_dests > 65536,
+ * d_head, d_dest_offsets, d_out_ghead or d_out_goff not 8-byte aligned, a given
+ * d_sub_of with sub_of_len > 2^32 - 1, min(cap, 2^32 - 1) + min(ecap, 2^32 - 1)
+ * > 2^32 - 1 (positions are u32).
+ *
+ * tm_publish_deliver_batch: the host product path.  It is tm_publish_batch to
+ * the letter for the route outputs, out_head = [M, T] (the direct deliveries
+ * alone), out_member[0 .. K), the state words, lanes, read-your-writes, the
+ * device-failure retry and the required TM_ROUTE_AGGRE.  The three delivery
+ * arrays come back merged and grouped: tm_group_picks_dev's outputs over the
+ * lane's deliveries and the lane's picks with the index's own
+ * tm_set_member_subs table (as of the moment the pick is queued); out_ghead =
+ * [G, N], out_gsub and out_goff as in tm_deliver_batch.  The pick and, in the
+ * same hold of the index lock and on the same lane, the merge and the grouping
+ * are queued once, after the run that stands and after every scratch they need
+ * has been had.  The state moves exactly once per successful call and never
+ * for a call the caller has to repeat:
+ *   total > cap     TM_ECAP, no pick, no state (tm_publish_batch's rule).
+ *   T + K > dcap    TM_ECAP, no pick, no state: T and K are known on the host
+ *                   before the pick is queued, and K bounds the local picks.
+ *                   out_head[1] and out_dest_offsets[n_dests + 1] size the
+ *                   retry: dcap >= T + K.  Deliberately stricter than
+ *                   tm_publish_batch's dcap rule, under which the picks stand.
+ *   under either of these the delivery arrays and the group outputs are not
+ *   written and out_ghead = [0, 0].
+ *   G > gcap alone  TM_ECAP with the picks made and the state moved once; the
+ *                   grouped per-delivery arrays are complete and out_ghead is
+ *                   exact: the caller reads the group bounds off the sorted
+ *                   out_dsub and does NOT resubmit.
+ * TM_EINVAL: whatever tm_publish_batch refuses, a null out_ghead or out_goff,
+ * a null out_gsub with gcap > 0. */
+int tm_set_member_subs(tm_index *h, uint64_t n, const uint32_t *members, const uint32_t *sub_ids);
+int tm_group_picks_dev(tm_index *h, const uint64_t *d_head,
+                       const uint32_t *d_topic, const uint32_t *d_value, const uint32_t *d_sub, uint64_t cap,
+                       uint32_t n_dests, const uint64_t *d_dest_offsets, const uint32_t *d_etopic,
+                       const uint32_t *d_evalue, const uint32_t *d_member, uint64_t ecap,
+                       const uint32_t *d_sub_of, uint64_t sub_of_len,
+                       uint64_t *d_out_ghead, uint32_t *d_out_gsub, uint64_t *d_out_goff, uint64_t gcap,
+                       uint32_t *d_out_topic, uint32_t *d_out_value, uint32_t *d_out_sub, uint32_t *d_out_src,
+                       uint64_t out_cap, void *stream);
+int tm_publish_deliver_batch(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint64_t *topic_offsets,
+                             uint32_t n_dests, uint32_t local_dest, uint32_t flags,
+                             uint64_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                             uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
+                             uint64_t dcap, const uint32_t *key_clientid, const uint32_t *key_topic, uint32_t seed,
+                             uint32_t *out_member, uint64_t *out_ghead, uint32_t *out_gsub, uint64_t *out_goff,
+                             uint64_t gcap, uint8_t *out_err);
+
 /* Release the batch scratch kept for `stream` (after its batches finish);
  * a caller that retires a stream calls this.  No reference counterpart. */
 int tm_stream_release(tm_index *h, void *stream);

@@ -139,6 +139,22 @@ the staged path); the route outputs, the head and which entries have a pick
 are compared with tm_publish_batch's first.  Under TM_LIB naming a library
 without tm_publish_batch only tm_dispatch_batch runs (the yardstick of an A/B);
 --dispatch-leg-only times this library the same way, the other side of that A/B.
+
+--group --share: the picks grouped with the deliveries (no index): 1M synthetic
+deliveries (100,000 pids, 250,000 messages) and 1M aggregated entries of which
+0 / 65,536 / 1M carry a member that is a local subscriber; tm_group_picks_dev
+against (a) the torch composition on the same tensors -- the local picks
+compacted, cat, a stable sort by message and one by subscriber,
+unique_consecutive, gathers -- outputs compared first (identical), and (b)
+tm_group_subs_dev on the deliveries alone: the floor, so the line with no local
+pick shows what the merge's front end costs over it; the three interleaved
+under HIP events.  --small --group --share: the --small index with --small
+--share's groups (member ids below 200,000, half of them local subscribers
+through tm_set_member_subs); tm_publish_deliver_batch beside tm_publish_batch
+and tm_deliver_batch, host to host and interleaved, at 64 / 1,024 / 4,096
+topics (--sizes); its grouped arrays are checked against the definition applied
+to tm_publish_batch's deliveries and its own entries and picks; pair_p50_ms is
+the two calls' sum, merged_over_pair the new call over it.
 """
 import argparse
 import json
@@ -727,6 +743,9 @@ def small_batches(a, sizes=(64, 1024, 4096, 16384), n_dests=16, warmup=20, reps=
     ix.sync(None)
     P = _native._ptr
     lib, h = ix._lib, ix._h
+    if a.group and a.share:
+        small_group_share(a, ix, len(fs), nvals, sizes if a.sizes else (64, 1024, 4096), n_dests, warmup, reps)
+        return
     if a.group:
         small_group(a, ix, len(fs), nvals, sizes if a.sizes else (64, 1024, 4096), n_dests, warmup, reps)
         return
@@ -970,6 +989,196 @@ def group_legs(torch, a, T=1_000_000):
                               "identical": True}), flush=True)
 
 
+def torch_group_picks(torch, t, v, s, et, ev, member, sub_of):
+    """the merge and the grouping as a torch composition on the same device tensors (ids below 2^31): the local
+    picks compacted, cat, two stable sorts (by message, then by subscriber), unique_consecutive, gathers"""
+    ok = (member >= 0) & (member < len(sub_of))
+    ls = torch.where(ok, sub_of[member.clamp(0, len(sub_of) - 1).long()], torch.full_like(member, -1))
+    pq = torch.nonzero(ls != -1).squeeze(1)
+    ct, cv, cs = torch.cat([t, et[pq]]), torch.cat([v, ev[pq]]), torch.cat([s, ls[pq]])
+    _, p1 = torch.sort(ct, stable=True)
+    ss, p2 = torch.sort(cs[p1], stable=True)
+    perm = p1[p2]
+    gs, cnt = torch.unique_consecutive(ss, return_counts=True)
+    goff = torch.zeros(len(gs) + 1, dtype=torch.int64, device=s.device)
+    goff[1:] = torch.cumsum(cnt, 0)
+    return ct[perm], cv[perm], ss, gs, goff
+
+
+def group_share_legs(torch, a, T=1_000_000, E=1_000_000):
+    """--group --share: tm_group_picks_dev at T deliveries with P = 0 / 64k / 1M local picks among E entries, against
+    (a) the torch composition and (b) tm_group_subs_dev on the same deliveries alone (the floor: what the parent offers
+    without the picks), the three interleaved"""
+    dev = torch.device("cuda")
+    ix = _native.Index()
+    s = torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(7)
+    pids, n_msgs, n_members, n_dests = 100_000, T // 4, 200_000, 4
+    d_s = torch.from_numpy(rng.integers(0, pids, T).astype(np.int32)).to(dev)
+    d_t = torch.from_numpy(np.sort(rng.integers(0, n_msgs, T)).astype(np.int32)).to(dev)
+    d_v = torch.from_numpy(rng.integers(0, 1 << 20, T).astype(np.int32)).to(dev)
+    d_head = torch.tensor([T, T], dtype=torch.int64, device=dev)
+    cuts = np.sort(rng.integers(0, E + 1, n_dests))
+    doff = np.concatenate([[0], cuts, [E]]).astype(np.int64)
+    et = np.concatenate([np.sort(rng.integers(0, n_msgs, int(doff[b + 1] - doff[b]))) for b in range(n_dests + 1)])
+    d_doff = torch.from_numpy(doff).to(dev)
+    d_et = torch.from_numpy(et.astype(np.int32)).to(dev)
+    d_ev = torch.from_numpy(rng.integers(0, 1 << 20, E).astype(np.int32)).to(dev)
+    sub_of = np.full(n_members, -1, np.int32)
+    sub_of[:n_members // 2] = rng.integers(0, pids, n_members // 2)       # the lower half of the members is local
+    d_sub_of = torch.from_numpy(sub_of).to(dev)
+    C = T + E
+    o_t, o_v, o_s = (torch.zeros(C, dtype=torch.int32, device=dev) for _ in range(3))
+    o_gsub = torch.zeros(C, dtype=torch.int32, device=dev)
+    o_goff = torch.zeros(C + 1, dtype=torch.int64, device=dev)
+    o_ghead = torch.zeros(2, dtype=torch.int64, device=dev)
+    f_t, f_v, f_s, f_gsub = (torch.zeros(T, dtype=torch.int32, device=dev) for _ in range(4))
+    f_goff = torch.zeros(T + 1, dtype=torch.int64, device=dev)
+    f_ghead = torch.zeros(2, dtype=torch.int64, device=dev)
+    for want in (0, 65_536, E):
+        member = rng.integers(n_members // 2, n_members, E)              # remote
+        member[rng.random(E) < 0.2] = -1                                  # no pick
+        member[rng.permutation(E)[:want]] = rng.integers(0, n_members // 2, want)
+        d_m = torch.from_numpy(member.astype(np.int32)).to(dev)
+
+        def hip():
+            ix.group_picks_dev(d_head.data_ptr(), d_t.data_ptr(), d_v.data_ptr(), d_s.data_ptr(), T, n_dests,
+                               d_doff.data_ptr(), d_et.data_ptr(), d_ev.data_ptr(), d_m.data_ptr(), E, o_ghead.data_ptr(),
+                               o_gsub.data_ptr(), o_goff.data_ptr(), C, o_t.data_ptr(), o_v.data_ptr(), o_s.data_ptr(), C,
+                               d_sub_of=d_sub_of.data_ptr(), sub_of_len=n_members, stream=s)
+
+        def tor():
+            return torch_group_picks(torch, d_t, d_v, d_s, d_et, d_ev, d_m, d_sub_of)
+
+        def floor():
+            ix.group_subs_dev(d_head.data_ptr(), d_t.data_ptr(), d_v.data_ptr(), d_s.data_ptr(), T, f_ghead.data_ptr(),
+                              f_gsub.data_ptr(), f_goff.data_ptr(), T, f_t.data_ptr(), f_v.data_ptr(), f_s.data_ptr(),
+                              stream=s)
+
+        hip()
+        r_t, r_v, r_s, r_gs, r_goff = tor()
+        floor()
+        torch.cuda.synchronize()
+        G, N = int(o_ghead[0]), int(o_ghead[1])
+        assert N == T + want == len(r_t) and G == len(r_gs) and torch.equal(o_t[:N], r_t) and torch.equal(o_s[:N], r_s) and \
+            torch.equal(o_v[:N], r_v) and torch.equal(o_gsub[:G], r_gs) and torch.equal(o_goff[:G + 1], r_goff), \
+            f"P {want}: the two paths differ"
+        if want == 0:
+            assert torch.equal(o_t[:T], f_t) and torch.equal(o_v[:T], f_v) and torch.equal(o_s[:T], f_s)
+        del r_t, r_v, r_s, r_gs, r_goff
+        for _ in range(a.warmup):
+            hip(), tor(), floor()
+        torch.cuda.synchronize()
+        ms = ([], [], [])
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        for _ in range(a.reps):   # interleaved: hip, torch, floor, hip, ...
+            ev[0].record()
+            hip()
+            ev[1].record()
+            tor()
+            ev[2].record()
+            floor()
+            ev[3].record()
+            torch.cuda.synchronize()
+            for k in range(3):
+                ms[k].append(ev[k].elapsed_time(ev[k + 1]))
+        h, t, f = stats(ms[0]), stats(ms[1]), stats(ms[2])
+        print(json.dumps({"tool": "fanout_bench", "kind": "group_share", "deliveries": T, "entries": E, "local_picks": want,
+                          "merged": N, "groups": G, "pids": pids, "messages": n_msgs, "reps": a.reps,
+                          "group_picks": h, "torch": t, "group_subs_floor": f,
+                          "torch_over_hip": round(t["median_ms"] / h["median_ms"], 2),
+                          "hip_over_floor": round(h["median_ms"] / f["median_ms"], 2),
+                          "hip_minus_floor_ms": round(h["median_ms"] - f["median_ms"], 4), "identical": True}), flush=True)
+
+
+def small_group_share(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=0, n_groups=4):
+    """--small --group --share: tm_publish_deliver_batch host to host beside tm_publish_batch followed by
+    tm_deliver_batch (what gives the same lists without it, minus the host merge), all under TM_ROUTE_AGGRE,
+    interleaved; small_share's groups with members below 200,000, half of them local subscribers"""
+    import time
+    P = _native._ptr
+    lib, h = ix._lib, ix._h
+    rng = np.random.default_rng(7)
+    cnt = rng.integers(a.subs[0], a.subs[1] + 1, nvals)
+    loffs = np.zeros(nvals + 1, np.uint64)
+    loffs[1:] = np.cumsum(cnt)
+    n_pids, n_members = 100_000, 200_000
+    subs = rng.integers(0, n_pids, int(loffs[-1]), dtype=np.int64).astype(np.uint32)
+    assert lib.tm_set_subscribers(h, nvals, P(np.arange(nvals, dtype=np.uint32)), P(loffs), P(subs)) == 0
+    dest = np.random.default_rng(7).integers(0, n_dests, nvals)   # (small_batches' destination table)
+    grp = np.nonzero((dest >= 1) & (dest <= n_groups))[0].astype(np.uint32)
+    ix.set_share_slots(grp, np.arange(len(grp), dtype=np.uint32))
+    mc = rng.integers(2, 9, len(grp))
+    moffs = np.zeros(len(grp) + 1, np.uint64)
+    moffs[1:] = np.cumsum(mc)
+    mem = rng.integers(0, n_members, int(moffs[-1]), dtype=np.int64).astype(np.uint32)
+    zero, meta = np.zeros(len(grp), np.uint32), np.full(len(grp), _native.TM_SHARE_ROUND_ROBIN, np.uint32)
+    assert lib.tm_set_share_members(h, len(grp), P(np.arange(len(grp), dtype=np.uint32)), P(moffs), P(mem), P(zero),
+                                    P(meta)) == 0
+    sub_of = np.where(rng.random(n_members) < 0.5, rng.integers(0, n_pids, n_members), 0xFFFFFFFF).astype(np.uint32)
+    ix.set_member_subs(np.arange(n_members, dtype=np.uint32), sub_of)
+    for n in sizes:
+        tp = wl.topics(3, a.filters, n)
+        blob, offs = np.ascontiguousarray(tp.blob), np.ascontiguousarray(tp.offs, dtype=np.uint64)
+        cap = 16 * n + 1024
+        d64, head, ghead, err = np.zeros(n_dests + 2, np.uint64), np.zeros(2, np.uint64), np.zeros(2, np.uint64), \
+            np.zeros(n, np.uint8)
+        rc = lib.tm_dispatch_batch(h, n, P(blob), P(offs), n_dests, local, 1, P(d64), None, None, 0, P(head), None, None,
+                                   None, 0, P(err))
+        assert rc in (0, _native.TM_ECAP)
+        T = int(head[1])
+        dcap = T + cap
+        t_, v_, m_ = (np.zeros(cap, np.uint32) for _ in range(3))
+        t2, v2, m2 = (np.zeros(cap, np.uint32) for _ in range(3))
+        dd, dg, dm = (tuple(np.zeros(dcap, np.uint32) for _ in range(3)) for _ in range(3))
+        gsub, goff = np.zeros(dcap, np.uint32), np.zeros(dcap + 1, np.uint64)
+        kc = rng.integers(0, 1 << 32, n, dtype=np.uint32)
+
+        def leg_p():
+            return lib.tm_publish_batch(h, n, P(blob), P(offs), n_dests, local, 1, P(d64), P(t_), P(v_), cap, P(head),
+                                        P(dd[0]), P(dd[1]), P(dd[2]), dcap, P(kc), P(kc), 1, P(m_), P(err))
+
+        def leg_g():
+            return lib.tm_deliver_batch(h, n, P(blob), P(offs), n_dests, local, 1, P(d64), P(t_), P(v_), cap, P(head),
+                                        P(dg[0]), P(dg[1]), P(dg[2]), dcap, P(ghead), P(gsub), P(goff), dcap, P(err))
+
+        def leg_m():
+            return lib.tm_publish_deliver_batch(h, n, P(blob), P(offs), n_dests, local, 1, P(d64), P(t2), P(v2), cap, P(head),
+                                                P(dm[0]), P(dm[1]), P(dm[2]), dcap, P(kc), P(kc), 1, P(m2), P(ghead), P(gsub),
+                                                P(goff), dcap, P(err))
+
+        # the merged call against the definition over its own entries and picks and the dispatch's deliveries
+        assert leg_p() == 0 and leg_m() == 0
+        K, N, G = int(d64[n_dests + 1]), int(ghead[1]), int(ghead[0])
+        ls = np.where(m2[:K] < n_members, sub_of[np.minimum(m2[:K], n_members - 1)], 0xFFFFFFFF)
+        pq = np.nonzero(ls != 0xFFFFFFFF)[0]
+        ct, cv, cs = (np.concatenate([x[:T], y[pq]]) for x, y in ((dd[0], t2[:K]), (dd[1], v2[:K]), (dd[2], ls)))
+        perm = np.lexsort((ct, cs))
+        assert N == T + len(pq) and np.array_equal(dm[0][:N], ct[perm]) and np.array_equal(dm[1][:N], cv[perm]) and \
+            np.array_equal(dm[2][:N], cs[perm]) and np.array_equal(gsub[:G], np.unique(cs)), \
+            f"n {n}: tm_publish_deliver_batch differs from the definition"
+        legs = [("publish_batch", leg_p), ("deliver_batch", leg_g), ("publish_deliver_batch", leg_m)]
+        ms = {k: [] for k, _ in legs}
+        for r in range(warmup + reps):
+            for k, f in legs:
+                t0 = time.perf_counter_ns()
+                assert f() == 0
+                t1 = time.perf_counter_ns()
+                if r >= warmup:
+                    ms[k].append((t1 - t0) * 1e-6)
+        st = {k: dict(stats(v), p50_ms=round(float(np.median(v)), 4), p99_ms=round(float(np.percentile(v, 99)), 4))
+              for k, v in ms.items()}
+        pair = st["publish_batch"]["p50_ms"] + st["deliver_batch"]["p50_ms"]
+        print(json.dumps({"tool": "fanout_bench", "kind": "small_group_share", "filters": fs_len, "topics": n,
+                          "kept_entries": K, "n_dests": n_dests, "groups_shared": n_groups, "deliveries": T,
+                          "local_picks": len(pq), "merged": N, "subscribers": G, "warmup": warmup, "reps": reps, **st,
+                          "pair_p50_ms": round(pair, 4),
+                          "merged_over_pair": round(st["publish_deliver_batch"]["p50_ms"] / pair, 3),
+                          "merged_minus_publish_ms": round(st["publish_deliver_batch"]["p50_ms"] -
+                                                           st["publish_batch"]["p50_ms"], 4),
+                          "identical": True}), flush=True)
+
+
 def small_group(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=0):
     """--small --group: tm_deliver_batch beside tm_dispatch_batch, host to host, interleaved"""
     import time
@@ -1099,7 +1308,9 @@ def main():
                         "tm_publish_batch beside tm_dispatch_batch, host to host")
     p.add_argument("--group", action="store_true",
                    help="deliveries grouped by subscriber: tm_group_subs_dev vs the torch composition at 1M deliveries; "
-                        "with --small: tm_deliver_batch beside tm_dispatch_batch, host to host")
+                        "with --small: tm_deliver_batch beside tm_dispatch_batch, host to host; with --share: "
+                        "tm_group_picks_dev vs the torch composition and the tm_group_subs_dev floor; with --small "
+                        "--share: tm_publish_deliver_batch beside tm_publish_batch followed by tm_deliver_batch")
     p.add_argument("--dispatch-leg-only", action="store_true",
                    help="--small --share: time tm_dispatch_batch alone, as a library without tm_publish_batch is timed")
     p.add_argument("--no-deliver32-leg", action="store_true",
@@ -1117,7 +1328,7 @@ def main():
         small_batches(a, **({"sizes": tuple(a.sizes)} if a.sizes else {}))
         return
     if a.group:
-        group_legs(torch, a)
+        (group_share_legs if a.share else group_legs)(torch, a)
         return
     dev = torch.device("cuda")
     fs = wl.filters(3, a.filters)
