@@ -38,7 +38,8 @@ typedef struct tmn_set {         /* one caller's batch buffers (tm_host_alloc: t
     uint64_t deliveries;                         /* T of the set's last tmn_dispatch */
     uint32_t dispatched;                         /* that call succeeded: tmn_deliveries has something to read
                                                     (2: it was a tmn_publish, tmn_picks has too; 3: a tmn_deliver,
-                                                    the deliveries are grouped and tmn_groups has something) */
+                                                    the deliveries are grouped and tmn_groups has something; 4: a
+                                                    tmn_publish_deliver, merged and grouped: both have) */
     tmn_buf skc, skt, smember;                   /* tmn_publish (tmatch_nif_share.h): the key words per topic, the picked
                                                     members (u32); allocated by tmn_share_keys / its first call only */
     uint32_t key_n, key_mask;                    /* tmn_share_keys: for how many topics, which arrays (1 clientid, 2 topic) */

@@ -75,7 +75,7 @@ int tmn_deliver(tmn_set *s, tm_index *h, uint32_t n, uint32_t n_dests, uint32_t 
 int tmn_groups(const tmn_set *s, const uint32_t **subs, const uint32_t **offs, uint64_t *count) {
     *subs = *offs = 0;
     *count = 0;
-    if (s->dispatched != 3) return TM_EINVAL;
+    if (s->dispatched != 3 && s->dispatched != 4) return TM_EINVAL;
     *subs = s->gsub.p;
     *offs = s->goff.p;
     *count = s->groups;

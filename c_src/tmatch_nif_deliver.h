@@ -36,7 +36,8 @@ int tmn_deliver(tmn_set *s, tm_index *h, uint32_t n, uint32_t n_dests, uint32_t 
 /* The groups of the last tmn_deliver: 0, *count subscriber ids in *subs
  * (ascending) and *count + 1 offsets in *offs -- subscriber g owns the
  * deliveries [offs[g], offs[g + 1]) of tmn_deliveries' arrays; TM_EINVAL and
- * none when the set's last call was not a tmn_deliver that succeeded. */
+ * none when the set's last call was not a tmn_deliver (or a
+ * tmn_publish_deliver, tmatch_nif_publish_deliver.h) that succeeded. */
 int tmn_groups(const tmn_set *s, const uint32_t **subs, const uint32_t **offs, uint64_t *count);
 
 #ifdef __cplusplus

@@ -85,7 +85,7 @@ int tmn_publish(tmn_set *s, tm_index *h, uint32_t n, uint32_t n_dests, uint32_t 
 int tmn_picks(const tmn_set *s, const uint32_t **members, uint64_t *count) {
     *members = 0;
     *count = 0;
-    if (s->dispatched != 2) return TM_EINVAL;
+    if (s->dispatched != 2 && s->dispatched != 4) return TM_EINVAL;
     *members = s->smember.p;
     *count = s->picks;
     return 0;

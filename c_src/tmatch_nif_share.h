@@ -54,7 +54,8 @@ int tmn_publish(tmn_set *s, tm_index *h, uint32_t n, uint32_t n_dests, uint32_t 
 
 /* The picks of the set's last tmn_publish: 0 and *count members, members[q]
  * for entry q of the slices (tmn_route_dest's positions); TM_EINVAL and none
- * when the set's last dispatching call was no successful tmn_publish. */
+ * when the set's last dispatching call was no successful tmn_publish (or
+ * tmn_publish_deliver, tmatch_nif_publish_deliver.h). */
 int tmn_picks(const tmn_set *s, const uint32_t **members, uint64_t *count);
 
 #ifdef __cplusplus

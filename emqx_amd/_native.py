@@ -33,7 +33,7 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_dispatch_batch32", "tm_set_share_slots", "tm_set_share_members", "tm_share_state_set",
            "tm_share_state_get", "tm_share_pick_dev", "tm_publish_batch", "tm_publish_batch32",
            "tm_group_subs_dev", "tm_deliver_batch", "tm_deliver_batch32", "tm_set_member_subs",
-           "tm_group_picks_dev", "tm_publish_deliver_batch")
+           "tm_group_picks_dev", "tm_publish_deliver_batch", "tm_publish_deliver_batch32")
 TM_ALLOC_VRAM = 1
 TM_ROUTE_AGGRE = 1          # tm_route_batch_ex / tm_route_batch32_ex: aggre/1 applied to the buckets
 NO_FILTER = 0xFFFFFFFF      # tm_set_route_filters: no filter known (equal to nothing)
@@ -67,7 +67,11 @@ TM_DEBUG_GROUP_TILE, TM_DEBUG_GROUP_PASSES_RUN, TM_DEBUG_GROUP_PASSES_SKIPPED = 
 TM_DEBUG_GROUP_GRID = 40    # (get only) the blocks of group_subs_dev's fixed grid
 TM_DEBUG_DELIVER_ONE, TM_DEBUG_DELIVER_GRID = 41, 42   # (get only) deliver_batch32 calls per grouping leg
 TM_DEBUG_GS1_MAX = 43       # deliveries the one-workgroup grouping takes itself (clamped to GS1_DELIVERIES)
+TM_DEBUG_GP1_MAX = 44       # merged deliveries (T + K) the one-workgroup merge takes itself (clamped to GP1_DELIVERIES)
+# (get only) publish_deliver_batch32 calls per ending: one workgroup / the grid kernels or the staged path
+TM_DEBUG_PUBLISH_DELIVER_ONE, TM_DEBUG_PUBLISH_DELIVER_GRID = 45, 46
 GS1_DELIVERIES = 16384
+GP1_DELIVERIES = 8192        # (emqx_amd/csrc/tm_dev.h) merged deliveries, T + K, of tm_publish_deliver_batch32's one workgroup
 MAX_DESTS = 65536           # tm_fanout_dev / tm_route_batch: n_dests is 1 .. MAX_DESTS
 
 
@@ -179,6 +183,8 @@ def load_library(path: Path | None = None):
                                      vp, u64, vp]),
         "tm_publish_deliver_batch": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u32,
                                            vp, vp, vp, vp, u64, vp]),
+        "tm_publish_deliver_batch32": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u32,
+                                             vp, vp, vp, vp, u64, vp]),
         "tm_debug_set": (i32, [vp, u32, u64]),
         "tm_debug_get": (i32, [vp, u32, C.POINTER(u64)]),
     }
@@ -922,6 +928,55 @@ class Index:
                                                  _ptr(err)))
         total, T = int(doff[n_dests + 1]), int(head[1])
         return (doff[: n_dests + 2], topic[:total], vals[:total], err[:n]), (dt[:T], dv[:T], ds[:T]), member[:total]
+
+    def publish_deliver_batch32(self, blob: np.ndarray, offs: np.ndarray, n_dests: int, local_dest: int, out, member,
+                                key_clientid=None, key_topic=None, seed: int = 0, cap: int | None = None,
+                                dcap: int | None = None, gcap: int | None = None):
+        """tm_publish_deliver_batch32: publish_deliver_batch with u32 topic offsets
+        in and u32 bucket and group offsets out, over caller-owned buffers.
+        out: deliver_batch32's eleven arrays; member u32[>= cap]; key_clientid /
+        key_topic: u32[>= n] or None -> (the route tuple, (dtopic, dvalue,
+        dsub)[:N] -- the direct deliveries and the local picks merged and
+        GROUPED by subscriber --, member[:K], (gsub[:G], goff[:G + 1]), T) as
+        views.  In place (no staging, one synchronisation) when every array
+        comes from host_array() and the batch is a micro-batch
+        (include/tmatch.h).  Raises TmError(TM_ECAP) when cap or dcap is short
+        (dest_offsets[n_dests+1] > cap or head[1] + dest_offsets[n_dests+1] >
+        dcap): no pick was made and no state moved, the same sizes size the
+        retry.  A gcap that proves too small raises nothing: the picks of the
+        call stand, the grouped arrays are complete, and the group bounds are
+        read off the sorted dsub (fresh arrays instead of views)."""
+        n = len(offs) - 1
+        if len(out) != 11:
+            raise ValueError("publish_deliver_batch32: out is dispatch_batch32's eight arrays, then ghead, gsub and goff")
+        doff, topic, vals, err, head, dt, dv, ds, ghead, gsub, goff = out
+        cap, dcap = self._out32("publish_deliver_batch32", offs, n_dests, out[:8], member, (key_clientid, key_topic), cap,
+                                dcap)
+        if ghead.dtype != np.uint64 or len(ghead) < 2 or gsub.dtype != np.uint32 or goff.dtype != np.uint32 or len(goff) < 1:
+            raise ValueError("publish_deliver_batch32: ghead u64[2], gsub u32[gcap] and goff u32[gcap + 1] expected")
+        groom = min(len(gsub), len(goff) - 1)
+        gcap = groom if gcap is None else gcap
+        if gcap < 0 or gcap > groom:
+            raise ValueError("publish_deliver_batch32: gcap exceeds the group arrays")
+        rc = self._lib.tm_publish_deliver_batch32(self._h, n, _ptr(blob), _ptr(offs), n_dests, local_dest, TM_ROUTE_AGGRE,
+                                                  _ptr(doff), _ptr(topic), _ptr(vals), cap, _ptr(head), _ptr(dt), _ptr(dv),
+                                                  _ptr(ds), dcap, _ptr(key_clientid), _ptr(key_topic), seed, _ptr(member),
+                                                  _ptr(ghead), _ptr(gsub), _ptr(goff), gcap, _ptr(err))
+        if rc not in (TM_OK, TM_ECAP):
+            self._check(rc)
+        total, T = int(doff[n_dests + 1]), int(head[1])
+        G, N = int(ghead[0]), int(ghead[1])
+        if rc == TM_ECAP and not (total <= cap and T + total <= dcap and G > gcap):
+            self._check(rc)   # cap or dcap: nothing moved
+        if rc == TM_ECAP:
+            # the picks stand and the grouped arrays are complete: the groups from the sorted subscribers
+            s = ds[:N]
+            starts = np.flatnonzero(np.concatenate(([True], s[1:] != s[:-1]))) if N else np.zeros(0, np.int64)
+            groups = (s[starts].copy(), np.concatenate((starts, [N])).astype(np.uint32))
+        else:
+            groups = (gsub[:G], goff[: G + 1])
+        return (doff[: n_dests + 2], topic[:total], vals[:total], err[:n]), (dt[:N], dv[:N], ds[:N]), member[:total], \
+            groups, T
 
     def release_stream(self, stream: int | None):
         """Drop the batch scratch the library keeps for `stream`."""

@@ -511,6 +511,55 @@ hipError_t launch_group_one(const uint32_t *status_in, const uint64_t *head, con
                             uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
                             uint64_t *out_ghead, uint32_t *out_gsub, uint32_t *out_goff, uint64_t gcap, uint32_t *status,
                             hipStream_t s);
+// A micro-batch's picks merged with its deliveries and grouped in ONE launch
+// of ONE workgroup (k_gp_one; tm_publish_deliver_batch32), queued behind
+// launch_dispatch_one (given the lane's delivery arrays and `head`, as under
+// launch_group_one), launch_pd_gate and launch_share_one.
+// launch_pd_gate (k_pd_gate, one wave) decides ONCE, on the device, whether the
+// run that queued the three stands and fits one workgroup, and writes that into
+// `gate` (one device word: 0 go, else skip), which launch_share_one is given as
+// its fail word and launch_group_picks_one reads: the pick is made and the state
+// moves exactly when the merge and the grouping run.  status_in: the block
+// launch_dispatch_one itself was given; head: the [M, T] it left on the lane;
+// dest_offsets: the aggre pass's u32 offsets (K = dest_offsets[n_dests + 1]);
+// fail: the lane's look-back fail word (may be null).  With FO1_DONE in
+// status_in out_head = head (mapped host memory).  Go needs launch_share_one's
+// own conditions (FO1_DONE, total <= vcap, total <= cap, *fail == 0, n_dests <=
+// FO1_MAX_DESTS) and T <= tmax, T + K <= min(dcap, nmax); tmax and nmax are
+// clamped to GP1_DELIVERIES.  status (may be mapped host memory):
+// [PD1_ST_STATE] = PD1_GO or PD1_SKIP, [PD1_ST_REASON] = the first condition
+// in the order of PD1_R_* that failed, [PD1_ST_T] / [PD1_ST_K] = T (saturated)
+// and K where status_in was FO1_DONE.
+// launch_group_picks_one: a non-zero gate word gives status[GP1_ST_STATE] =
+// GP1_SKIPPED and nothing else.  Otherwise member[0 .. K) (what
+// launch_share_one wrote on the lane) goes to out_member, and
+// launch_group_picks' results over the T deliveries and the K entries with
+// sub_of (sub_of_len words) go to the caller's buffers: the N = T + P merged
+// and grouped deliveries below dcap, out_ghead = [G, N], the first min(G, gcap)
+// subscribers and offsets with the end entry -- out_goff as u32.  Every output
+// may be mapped host memory, none is read.  status: [GP1_ST_STATE] =
+// GP1_GROUPED with the digit passes run and skipped (of GS_PASSES for each of
+// the two sorts), G, P and N beside it.  head and out_ghead must be 8-byte
+// aligned.  No scratch: both sorts run over 16-bit codes inside LDS; a pick's
+// message and entry position are staged there too, which is why one workgroup
+// stops at 8192 merged deliveries where k_gs_one takes 16384.
+constexpr uint32_t GP1_DELIVERIES = 8192;
+enum { PD1_ST_STATE = 0, PD1_ST_REASON = 1, PD1_ST_T = 2, PD1_ST_K = 3, PD1_ST_WORDS = 4 };
+enum : uint32_t { PD1_GO = 1, PD1_SKIP = 2 };
+enum : uint32_t { PD1_R_NONE = 0, PD1_R_STATE = 1, PD1_R_VCAP = 2, PD1_R_FAIL = 3, PD1_R_CAP = 4, PD1_R_DCAP = 5,
+                  PD1_R_LARGE = 6 };
+enum { GP1_ST_STATE = 0, GP1_ST_RUN = 1, GP1_ST_SKIPPED = 2, GP1_ST_G = 3, GP1_ST_P = 4, GP1_ST_N = 5, GP1_ST_WORDS = 6 };
+enum : uint32_t { GP1_GROUPED = 1, GP1_SKIPPED = 2 };
+hipError_t launch_pd_gate(const uint32_t *status_in, const uint64_t *head, const uint32_t *dest_offsets, uint32_t n_dests,
+                          const uint32_t *fail, uint64_t vcap, uint64_t cap, uint64_t dcap, uint64_t tmax, uint64_t nmax,
+                          uint64_t *out_head, uint32_t *gate, uint32_t *status, hipStream_t s);
+hipError_t launch_group_picks_one(const uint32_t *gate, const uint64_t *head, const uint32_t *in_topic,
+                                  const uint32_t *in_value, const uint32_t *in_sub, const uint32_t *dest_offsets,
+                                  uint32_t n_dests, const uint32_t *e_topic, const uint32_t *e_value, const uint32_t *member,
+                                  const uint32_t *sub_of, uint64_t sub_of_len, uint64_t cap, uint64_t dcap,
+                                  uint32_t *out_member, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
+                                  uint64_t *out_ghead, uint32_t *out_gsub, uint32_t *out_goff, uint64_t gcap,
+                                  uint32_t *status, hipStream_t s);
 // delta upload: run i copies runs[i].n u32 words from data + runs[i].src to
 // word (dst & PATCH_OFF) of table (dst >> 48), whose device address on the
 // replica being patched is bases.b[table] (the same runs patch every replica)

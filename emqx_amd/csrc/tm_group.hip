@@ -805,7 +805,355 @@ __global__ __launch_bounds__(FO1_BLOCK) void k_gs_one(const uint32_t *__restrict
     }
 }
 
+// ---- a micro-batch's picks merged with its deliveries and grouped in ONE
+// workgroup (tm_publish_deliver_batch32), queued behind k_dp_one (deliveries
+// and head on the lane, as under k_gs_one), k_pd_gate and k_sh_one.
+//   k_pd_gate  one wave, one thread at work.  The run that queued the kernels
+//          may be run again (a value scratch that grew, a look-back retry) and
+//          the pick moves state, so whether the run stands is decided once, on
+//          the device, and written to one device word: k_sh_one is given that
+//          word as its fail word and k_gp_one reads it, so the pick is made
+//          exactly when the merge runs.  Go: k_sh_one's own conditions and T <=
+//          tmax, T + K <= min(dcap, nmax).  With FO1_DONE in st_in the lane's
+//          head = [M, T] goes on to the caller's out_head whatever follows.
+//   k_gp_one
+//   copy   member[0 .. K) from the lane to the caller's out_member.
+//   stage  source code c names delivery c (c < T) or T + the compact rank of a
+//          local pick: s_key[c] its subscriber id, s_msg[c] its message (16
+//          bits: a message index is below FO1_TOPICS), s_pq[r] the entry
+//          position of rank r.  The local picks (sub_of[member[q]] != NONE) are
+//          counted per wave, the counts scanned over the waves, and compacted
+//          in ascending entry position (a ballot and popcount per step).
+//   picks  the P ranks sorted stably by message: the digit pass below over the
+//          two low digits, one all picks agree on skipped.
+//   merge  delivery p goes to p + the picks with a message < t_p, the pick of
+//          sorted rank r to r + the deliveries with a message <= t_r: binary
+//          searches over s_msg.  Only codes move: the merged order is one of the
+//          two index arrays, the sort below looks keys up through the code.
+//   sort   the N = T + P codes stably by s_key: k_gs_one's pass, a copy for
+//          the reason given above k_gs_one (gp1_pass; k_gs_one keeps its own).
+//   out    heads, groups and the payload as k_gs_one; topic from s_msg, value
+//          gathered from the lane's deliveries or the entries through s_pq.
+// LDS: 32 KiB keys + 2 x 16 KiB codes + 16 KiB messages + 16 KiB entry
+// positions + 16 KiB bins + 96 B.  With 16384 codes the same layout takes 208
+// KiB of the CU's 160: the limit is 8192 (the assertions below).
+constexpr uint32_t GP1_WAVES = FO1_BLOCK / 64;
+constexpr uint64_t GP1_LDS_MAX = 160 * 1024;
+constexpr uint64_t gp1_lds(uint64_t codes) {
+    return codes * 4 + 2 * codes * 2 + codes * 2 + codes * 2 + GP1_WAVES * GS_BINS * 4 + GP1_WAVES * 4 + GS_BINS / 64 * 4 + 4 * 4;
+}
+static_assert(gp1_lds(GP1_DELIVERIES) <= GP1_LDS_MAX, "k_gp_one: the staged codes must fit the CU's LDS");
+static_assert(gp1_lds(2 * GP1_DELIVERIES) > GP1_LDS_MAX, "k_gp_one: twice the codes would fit: raise GP1_DELIVERIES");
+static_assert(GP1_DELIVERIES <= 0x10000u && FO1_ENTRIES <= 0x10000u && FO1_TOPICS <= 0x10000u,
+              "k_gp_one: codes, entry positions and messages are staged as 16 bits");
+static_assert(GP1_DELIVERIES <= GS1_DELIVERIES, "k_gp_one reads the lane arrays k_gs_one's request sizes");
+
+__global__ __launch_bounds__(64) void k_pd_gate(const uint32_t *__restrict__ st_in, const uint64_t *__restrict__ head,
+                                                const uint32_t *__restrict__ doff, uint32_t n_dests,
+                                                const uint32_t *fail, uint64_t vcap, uint64_t cap, uint64_t dcap,
+                                                uint64_t tmax, uint64_t nmax, uint64_t *__restrict__ out_head,
+                                                uint32_t *__restrict__ gate, uint32_t *__restrict__ status) {
+    if (threadIdx.x) return;
+    const uint32_t state = st_in[FO1_ST_STATE], total = st_in[FO1_ST_TOTAL];
+    uint32_t reason = PD1_R_NONE, t32 = 0, k32 = 0;
+    if (state != FO1_DONE || n_dests > FO1_MAX_DESTS) {
+        reason = PD1_R_STATE;   // k_dp_one wrote nothing: the head is an older run's
+    } else {
+        const uint64_t M = head[0], T = head[1];
+        const uint64_t K = doff[n_dests + 1];
+        const uint32_t failed = fail ? __hip_atomic_load(fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
+        out_head[0] = M;
+        out_head[1] = T;
+        t32 = T > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)T;
+        k32 = (uint32_t)K;
+        if (total > vcap) reason = PD1_R_VCAP;
+        else if (failed) reason = PD1_R_FAIL;
+        else if (total > cap) reason = PD1_R_CAP;
+        else if (T + K > dcap) reason = PD1_R_DCAP;
+        else if (T > tmax || T + K > nmax || K > FO1_ENTRIES) reason = PD1_R_LARGE;
+    }
+    *gate = reason;
+    status[PD1_ST_REASON] = reason;
+    status[PD1_ST_T] = t32;
+    status[PD1_ST_K] = k32;
+    status[PD1_ST_STATE] = reason == PD1_R_NONE ? PD1_GO : PD1_SKIP;
+}
+
+// One stable 8-bit LSD pass of the codes src[0 .. n) into dst by (keys[code] >> shift) & 255: wave w owns
+// the positions [w * D, (w + 1) * D); a row of bins per wave, scanned over the waves and then the bins; in
+// the scatter the lanes of a step with the same digit rank themselves by a peer mask (k_gs_one's pass)
+template <class Key>
+__device__ __forceinline__ void gp1_pass(const Key *keys, const uint16_t *src, uint16_t *dst, uint32_t n, uint32_t shift,
+                                         uint32_t *s_h, uint32_t *s_bw, uint32_t tid, uint32_t lane, uint32_t wv) {
+    const uint32_t D = ((n + GP1_WAVES - 1) / GP1_WAVES + 63) & ~63u;
+    const uint32_t d0 = wv * D < n ? wv * D : n, d1 = d0 + D < n ? d0 + D : n;
+    uint32_t *my_h = s_h + wv * GS_BINS;
+    for (uint32_t i = tid; i < GP1_WAVES * GS_BINS; i += FO1_BLOCK) s_h[i] = 0;
+    __syncthreads();
+    for (uint32_t p0 = d0; p0 < d1; p0 += 64) {
+        const uint32_t p = p0 + lane;
+        if (p < d1) atomicAdd(&my_h[((uint32_t)keys[src[p]] >> shift) & (GS_BINS - 1)], 1u);
+    }
+    __syncthreads();
+    uint32_t tot = 0;
+    if (tid < GS_BINS)
+        for (uint32_t q = 0; q < GP1_WAVES; q++) {
+            const uint32_t x = s_h[q * GS_BINS + tid];
+            s_h[q * GS_BINS + tid] = tot;
+            tot += x;
+        }
+    const uint32_t binc = gs_incl_scan32(tot, lane);
+    if (tid < GS_BINS && lane == 63) s_bw[wv] = binc;
+    __syncthreads();
+    if (tid < GS_BINS) {
+        uint32_t exc = binc - tot;
+        for (uint32_t q = 0; q < wv; q++) exc += s_bw[q];
+        for (uint32_t q = 0; q < GP1_WAVES; q++) s_h[q * GS_BINS + tid] += exc;
+    }
+    __syncthreads();
+    for (uint32_t p0 = d0; p0 < d1; p0 += 64) {   // (wave-uniform)
+        const uint32_t p = p0 + lane;
+        const bool ok = p < d1;
+        const uint32_t ix = ok ? src[p] : 0u;
+        const uint32_t d = ok ? ((uint32_t)keys[ix] >> shift) & (GS_BINS - 1) : 0u;
+        const uint64_t peers = gs_match(d, ok);
+        uint32_t at = 0;
+        if (ok) at = my_h[d] + gs_below(peers, lane);
+        gs1_wave_sync();
+        if (ok && (peers >> lane) == 1ull) my_h[d] += (uint32_t)__popcll(peers);   // (the run's last lane)
+        gs1_wave_sync();
+        if (ok && at < n) dst[at] = (uint16_t)ix;   // (at < n always: the histogram saw these keys)
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(FO1_BLOCK) void k_gp_one(
+    const uint32_t *__restrict__ gate, const uint64_t *__restrict__ head, const uint32_t *__restrict__ in_t,
+    const uint32_t *__restrict__ in_v, const uint32_t *__restrict__ in_s, const uint32_t *__restrict__ doff,
+    uint32_t n_dests, const uint32_t *__restrict__ e_t, const uint32_t *__restrict__ e_v,
+    const uint32_t *__restrict__ member, const uint32_t *__restrict__ sub_of, uint64_t sub_of_len, uint64_t cap,
+    uint64_t dcap, uint32_t *__restrict__ out_member, uint32_t *__restrict__ out_dt, uint32_t *__restrict__ out_dv,
+    uint32_t *__restrict__ out_ds, uint64_t *__restrict__ out_ghead, uint32_t *__restrict__ out_gsub,
+    uint32_t *__restrict__ out_goff, uint64_t gcap, uint32_t *__restrict__ status) {
+    __shared__ uint32_t s_key[GP1_DELIVERIES];
+    __shared__ __attribute__((aligned(4))) uint16_t s_ix[2][GP1_DELIVERIES];
+    __shared__ __attribute__((aligned(4))) uint16_t s_msg[GP1_DELIVERIES];
+    __shared__ __attribute__((aligned(4))) uint16_t s_pq[GP1_DELIVERIES];
+    __shared__ uint32_t s_h[GP1_WAVES * GS_BINS];
+    __shared__ uint32_t s_wt[GP1_WAVES];
+    __shared__ uint32_t s_bw[GS_BINS / 64];
+    __shared__ uint32_t s_red[4];   // the AND and the OR of the picks' messages, of all keys
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (*gate != 0) {   // (block-uniform) the run does not stand, or not in one workgroup: no pick was made
+        if (tid == 0) status[GP1_ST_STATE] = GP1_SKIPPED;
+        return;
+    }
+    uint32_t T = head[1] < GP1_DELIVERIES ? (uint32_t)head[1] : GP1_DELIVERIES;   // (the gate: T + K <= GP1_DELIVERIES)
+    uint32_t K = doff[n_dests + 1];
+    if (K > cap) K = (uint32_t)cap;                      // (never: K <= total <= cap)
+    if (K > GP1_DELIVERIES - T) K = GP1_DELIVERIES - T;   // (never)
+    if (tid == 0) {
+        s_red[0] = s_red[2] = 0xFFFFFFFFu;
+        s_red[1] = s_red[3] = 0;
+    }
+    // ---- the picks to the caller
+    for (uint32_t i = tid; i < K; i += FO1_BLOCK) out_member[i] = member[i];
+    // ---- the deliveries' keys and messages
+    uint32_t k_and = 0xFFFFFFFFu, k_or = 0, m_and = 0xFFFFFFFFu, m_or = 0;
+    for (uint32_t i = tid; i < T; i += FO1_BLOCK) {
+        const uint32_t key = in_s[i];
+        s_key[i] = key;
+        s_msg[i] = (uint16_t)in_t[i];
+        k_and &= key;
+        k_or |= key;
+    }
+    // ---- the local picks, counted and compacted in ascending entry position
+    const uint32_t C = ((K + GP1_WAVES - 1) / GP1_WAVES + 63) & ~63u;
+    const uint32_t c0 = wv * C < K ? wv * C : K, c1 = c0 + C < K ? c0 + C : K;
+    uint32_t n_loc = 0;
+    for (uint32_t q0 = c0; q0 < c1; q0 += 64) {   // (wave-uniform)
+        const uint32_t q = q0 + lane;
+        const bool f = q < c1 && gp_local(member, sub_of, sub_of_len, q) != GP_NONE;
+        n_loc += (uint32_t)__popcll(__ballot(f));
+    }
+    if (lane == 0) s_wt[wv] = n_loc;
+    __syncthreads();
+    uint32_t base = 0, P = 0;
+    for (uint32_t q = 0; q < GP1_WAVES; q++) {
+        if (q < wv) base += s_wt[q];
+        P += s_wt[q];
+    }
+    const uint32_t N = T + P;   // (<= GP1_DELIVERIES: P <= K)
+    for (uint32_t q0 = c0; q0 < c1; q0 += 64) {   // (wave-uniform)
+        const uint32_t q = q0 + lane;
+        const uint32_t ls = q < c1 ? gp_local(member, sub_of, sub_of_len, q) : GP_NONE;
+        const bool f = ls != GP_NONE;
+        const uint64_t m = __ballot(f);
+        const uint32_t r = base + gs_below(m, lane);
+        if (f && r < P) {   // (r < P always: the count above saw these entries)
+            const uint32_t t = e_t[q];
+            s_key[T + r] = ls;
+            s_msg[T + r] = (uint16_t)t;
+            s_pq[r] = (uint16_t)q;
+            s_ix[0][r] = (uint16_t)r;
+            k_and &= ls;
+            k_or |= ls;
+            m_and &= t;
+            m_or |= t;
+        }
+        base += (uint32_t)__popcll(m);
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {
+        k_and &= __shfl_xor(k_and, d, 64);
+        k_or |= __shfl_xor(k_or, d, 64);
+        m_and &= __shfl_xor(m_and, d, 64);
+        m_or |= __shfl_xor(m_or, d, 64);
+    }
+    if (lane == 0) {
+        atomicAnd(&s_red[0], m_and);
+        atomicOr(&s_red[1], m_or);
+        atomicAnd(&s_red[2], k_and);
+        atomicOr(&s_red[3], k_or);
+    }
+    __syncthreads();
+    const uint32_t mdiff = P ? (s_red[0] ^ s_red[1]) & 0xFFFFu : 0u;   // bits on which two picks' messages differ
+    const uint32_t diff = N ? s_red[2] ^ s_red[3] : 0u;                // on which two keys differ
+    // ---- the picks by message
+    uint32_t cur = 0, run = 0;
+    for (uint32_t shift = 0; shift < 16; shift += 8) {   // (block-uniform)
+        if (!((mdiff >> shift) & (GS_BINS - 1))) continue;
+        run++;
+        gp1_pass(s_msg + T, s_ix[cur], s_ix[cur ^ 1], P, shift, s_h, s_bw, tid, lane, wv);
+        cur ^= 1;
+    }
+    // ---- merged by message into the other index array
+    {
+        const uint16_t *R = s_ix[cur];
+        uint16_t *Mg = s_ix[cur ^ 1];
+        for (uint32_t i = tid; i < N; i += FO1_BLOCK) {
+            uint32_t lo = 0, code;
+            if (i < T) {   // the picks with a message below mine
+                const uint32_t t = s_msg[i];
+                uint32_t hi = P;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (s_msg[T + R[mid]] < t) lo = mid + 1;
+                    else hi = mid;
+                }
+                code = i;
+                lo += i;
+            } else {       // the deliveries with a message at or below mine
+                const uint32_t r = i - T, c = R[r];
+                const uint32_t t = s_msg[T + c];
+                uint32_t hi = T;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (s_msg[mid] <= t) lo = mid + 1;
+                    else hi = mid;
+                }
+                code = T + c;
+                lo += r;
+            }
+            if (lo < N) Mg[lo] = (uint16_t)code;   // (always: a permutation of [0, N))
+        }
+        cur ^= 1;
+    }
+    __syncthreads();
+    // ---- the merged codes by subscriber
+    for (uint32_t pass = 0, shift = 0; pass < GS_PASSES; pass++, shift += 8) {   // (block-uniform)
+        if (!((diff >> shift) & (GS_BINS - 1))) continue;
+        run++;
+        gp1_pass(s_key, s_ix[cur], s_ix[cur ^ 1], N, shift, s_h, s_bw, tid, lane, wv);
+        cur ^= 1;
+    }
+    // ---- heads, groups and the payload
+    const uint16_t *I = s_ix[cur];
+    const uint32_t D = ((N + GP1_WAVES - 1) / GP1_WAVES + 63) & ~63u;
+    const uint32_t d0 = wv * D < N ? wv * D : N, d1 = d0 + D < N ? d0 + D : N;
+    uint32_t n_heads = 0;
+    for (uint32_t p0 = d0; p0 < d1; p0 += 64) {   // (wave-uniform)
+        const uint32_t p = p0 + lane;
+        const bool h = p < d1 && (p == 0 || s_key[I[p - 1]] != s_key[I[p]]);
+        n_heads += (uint32_t)__popcll(__ballot(h));
+    }
+    if (lane == 0) s_wt[wv] = n_heads;   // (the compaction's counts were read before the barriers above)
+    __syncthreads();
+    uint32_t g0 = 0, G = 0;
+    for (uint32_t q = 0; q < GP1_WAVES; q++) {
+        if (q < wv) g0 += s_wt[q];
+        G += s_wt[q];
+    }
+    for (uint32_t p0 = d0; p0 < d1; p0 += 64) {   // (wave-uniform)
+        const uint32_t p = p0 + lane;
+        const bool ok = p < d1;
+        uint32_t code = ok ? I[p] : 0u;
+        if (code >= N) code = 0;   // (never: I is a permutation of [0, N))
+        const uint32_t key = ok ? s_key[code] : 0u;
+        const bool h = ok && (p == 0 || s_key[I[p - 1]] != key);
+        const uint64_t hm = __ballot(h);
+        if (h) {
+            const uint64_t g = (uint64_t)g0 + gs_below(hm, lane);
+            if (g < gcap) out_gsub[g] = key;
+            if (g <= gcap) out_goff[g] = p;   // (g == gcap < G: where the first group left out starts)
+        }
+        g0 += (uint32_t)__popcll(hm);
+        if (ok && p < dcap) {   // (p < dcap always: the gate)
+            out_dt[p] = s_msg[code];
+            out_dv[p] = code < T ? in_v[code] : e_v[s_pq[code - T]];
+            out_ds[p] = key;
+        }
+    }
+    if (tid == 0) {
+        if (G <= gcap) out_goff[G] = N;
+        out_ghead[0] = G;
+        out_ghead[1] = N;
+        status[GP1_ST_RUN] = run;
+        status[GP1_ST_SKIPPED] = 2 * GS_PASSES - run;
+        status[GP1_ST_G] = G;
+        status[GP1_ST_P] = P;
+        status[GP1_ST_N] = N;
+        status[GP1_ST_STATE] = GP1_GROUPED;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_pd_gate(const uint32_t *status_in, const uint64_t *head, const uint32_t *dest_offsets, uint32_t n_dests,
+                          const uint32_t *fail, uint64_t vcap, uint64_t cap, uint64_t dcap, uint64_t tmax, uint64_t nmax,
+                          uint64_t *out_head, uint32_t *gate, uint32_t *status, hipStream_t s) {
+    if (!status_in || !head || !dest_offsets || !out_head || !gate || !status || !n_dests || n_dests > FO1_MAX_DESTS ||
+        (((uintptr_t)head | (uintptr_t)out_head) & 7))
+        return hipErrorInvalidValue;
+    if (tmax > GP1_DELIVERIES) tmax = GP1_DELIVERIES;
+    if (nmax > GP1_DELIVERIES) nmax = GP1_DELIVERIES;
+    hipLaunchKernelGGL(k_pd_gate, dim3(1), dim3(64), 0, s, status_in, head, dest_offsets, n_dests, fail, vcap, cap, dcap,
+                       tmax, nmax, out_head, gate, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_picks_one(const uint32_t *gate, const uint64_t *head, const uint32_t *in_topic,
+                                  const uint32_t *in_value, const uint32_t *in_sub, const uint32_t *dest_offsets,
+                                  uint32_t n_dests, const uint32_t *e_topic, const uint32_t *e_value, const uint32_t *member,
+                                  const uint32_t *sub_of, uint64_t sub_of_len, uint64_t cap, uint64_t dcap,
+                                  uint32_t *out_member, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
+                                  uint64_t *out_ghead, uint32_t *out_gsub, uint32_t *out_goff, uint64_t gcap,
+                                  uint32_t *status, hipStream_t s) {
+    if (!gate || !head || !dest_offsets || !out_ghead || !out_goff || !status || !n_dests || n_dests > FO1_MAX_DESTS ||
+        (((uintptr_t)head | (uintptr_t)out_ghead) & 7))
+        return hipErrorInvalidValue;
+    if (!sub_of) sub_of_len = 0;
+    if (sub_of_len > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (cap > FO1_ENTRIES) cap = FO1_ENTRIES;
+    if (dcap > GP1_DELIVERIES) dcap = GP1_DELIVERIES;
+    if (!in_topic || !in_value || !in_sub || !e_topic || !e_value || !member ||
+        (cap && !out_member) || (dcap && (!out_dtopic || !out_dvalue || !out_dsub)) || (gcap && !out_gsub))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_gp_one, dim3(1), dim3(FO1_BLOCK), 0, s, gate, head, in_topic, in_value, in_sub, dest_offsets,
+                       n_dests, e_topic, e_value, member, sub_of, sub_of_len, cap, dcap, out_member, out_dtopic,
+                       out_dvalue, out_dsub, out_ghead, out_gsub, out_goff, gcap, status);
+    return hipGetLastError();
+}
 
 hipError_t launch_group_one(const uint32_t *status_in, const uint64_t *head, const uint32_t *in_topic,
                             const uint32_t *in_value, const uint32_t *in_sub, uint64_t dcap, uint64_t dp1_max,

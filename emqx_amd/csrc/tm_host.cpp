@@ -370,6 +370,10 @@ struct tm_index {
     // digit passes k_gs_one ran / skipped (TM_DEBUG_GROUP_PASSES_*: added to the grid form's)
     std::atomic<uint64_t> deliver_one{0}, deliver_grid{0}, gs1_passes[2] = {};
     uint64_t gs1_max = GS1_DELIVERIES;   // TM_DEBUG_GS1_MAX: deliveries k_gs_one groups itself
+    // tm_publish_deliver_batch32 calls the one-workgroup ending finished (k_gp_one merged and grouped, or the
+    // gate found a capacity short and nothing moved) / that the grid kernels or the staged path finished
+    std::atomic<uint64_t> publish_deliver_one{0}, publish_deliver_grid{0};
+    uint64_t gp1_max = GP1_DELIVERIES;   // TM_DEBUG_GP1_MAX: merged deliveries k_gp_one takes itself
     // The host-batch combiner (small_combined): small in-place 32-bit batches
     // of concurrent callers queue here; up to cmb_leaders callers at a time
     // each take what is queued and run it as ONE k_walk_small launch
@@ -2181,7 +2185,7 @@ struct HostBatch {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 22u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 23u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 
@@ -3975,7 +3979,8 @@ struct RoutePick {
 // / d_at / d_av) with the index's own tables and state into d_sm (caller
 // holds ix->mu).  Queued ONCE per call, after the run that stands: the state
 // words move once, and only for entries the caller gets.
-static int queue_pick(tm_index *ix, Lane &ln, uint64_t n, uint32_t n_dests, uint64_t vcap, const RoutePick &pk) {
+static int queue_pick(tm_index *ix, Lane &ln, uint64_t n, uint32_t n_dests, uint64_t vcap, const RoutePick &pk,
+                      const uint64_t *doff = nullptr) {
     int rc;
     const hipStream_t s = ln.s;
     const uint64_t hoff = (vcap + 1) & ~1ull;   // the two head words, 8-byte aligned
@@ -3997,7 +4002,7 @@ static int queue_pick(tm_index *ix, Lane &ln, uint64_t n, uint32_t n_dests, uint
     uint64_t slot_len = 0, n_slots = 0, pool_len = 0;
     uint32_t *state = nullptr;
     if ((rc = share_upload(ix, ix->rep[ln.r].group, s, slot_of, slot_len, rec, n_slots, pool, pool_len, state))) return rc;
-    HIPCHK(ix, launch_share_pick(ln.f, n_dests, ln.d_ao, ln.d_at, ln.d_av, vcap, kc, kt, n, pk.seed, slot_of, slot_len, rec,
+    HIPCHK(ix, launch_share_pick(ln.f, n_dests, doff ? doff : ln.d_ao, ln.d_at, ln.d_av, vcap, kc, kt, n, pk.seed, slot_of, slot_len, rec,
                                  n_slots, pool, pool_len, state, reinterpret_cast<uint64_t *>(ln.d_sm + hoff), ln.d_sm, s));
     return TM_OK;
 }
@@ -4145,13 +4150,15 @@ struct PickMerge {
     uint64_t *d_head, T, gcap;
     uint8_t *pin;
     bool fetch;
+    const uint64_t *doff = nullptr;   // the aggre pass's offsets where they are not ln.d_ao (u32 there, widened here)
+    bool locked = false;              // the caller holds the lock and has queued on the lane in this hold
 };
 
 static int pick_after_run(tm_index *ix, HostBatch &hb, const RouteReq &rq, uint64_t vcap, uint64_t kept,
                           const PickMerge *gm = nullptr) {
     int rc;
     Lane &ln = *hb.ln;
-    if ((rc = hb.relock())) return rc;
+    if (!(gm && gm->locked) && (rc = hb.relock())) return rc;
     const uint32_t *sub_of = nullptr;
     uint64_t sub_of_len = 0;
     // (a topic index is below n: the digits the picks' sort by message can need)
@@ -4161,9 +4168,10 @@ static int pick_after_run(tm_index *ix, HostBatch &hb, const RouteReq &rq, uint6
         if ((rc = ensure_group_picks(ix, ln, gm->T + kept, kept, rq.who))) return rc;
         if ((rc = msub_upload(ix, ix->rep[ln.r].group, ln.s, sub_of, sub_of_len))) return rc;
     }
-    if ((rc = queue_pick(ix, ln, rq.n, rq.n_dests, vcap, *rq.pk))) return rc;
+    if ((rc = queue_pick(ix, ln, rq.n, rq.n_dests, vcap, *rq.pk, gm ? gm->doff : nullptr))) return rc;
     if (gm) {
-        HIPCHK(ix, launch_group_picks(ln.f, gm->d_head, ln.d_dt, ln.d_dv, ln.d_ds, gm->T, rq.n_dests, ln.d_ao, ln.d_at,
+        HIPCHK(ix, launch_group_picks(ln.f, gm->d_head, ln.d_dt, ln.d_dv, ln.d_ds, gm->T, rq.n_dests,
+                                      gm->doff ? gm->doff : ln.d_ao, ln.d_at,
                                       ln.d_av, ln.d_sm, kept, sub_of, sub_of_len, gm->d_head + 2, ln.d_gsub, ln.d_goff,
                                       std::min(gm->gcap, gm->T + kept), ln.d_gt, ln.d_gv, ln.d_gs, nullptr,
                                       gm->T + kept, msg_passes, ln.s));
@@ -4512,11 +4520,14 @@ constexpr int DP1_GRID_HEAD = DP1_ST_WORDS;   // status word of the [M, T] a gri
 constexpr int SH1_HOST = DP1_GRID_HEAD + 4;   // k_sh_one's status words (its head 8-byte aligned)
 constexpr int GS1_HOST = SH1_HOST + SH1_ST_WORDS;        // k_gs_one's status words
 constexpr int GS1_GRID_HEAD = GS1_HOST + GS1_ST_WORDS;   // the [M, T, G, W] a grid dispatch and grouping leave
-constexpr int DP1_HOST_WORDS = GS1_GRID_HEAD + 8;
+constexpr int PD1_HOST = GS1_GRID_HEAD + 8;              // k_pd_gate's status words
+constexpr int GP1_HOST = PD1_HOST + PD1_ST_WORDS;        // k_gp_one's status words
+constexpr int DP1_HOST_WORDS = GP1_HOST + GP1_ST_WORDS;
 // the lane's device words (Lane::fo1_s): the two status pairs, then k_dp_one's head under a grouping
 // request and the grid grouping's [G, W] behind it
 constexpr int FO1S_HEAD = 2 * FO1_ST_WORDS;
-constexpr int FO1S_WORDS = FO1S_HEAD + 8;
+constexpr int FO1S_GATE = FO1S_HEAD + 8;   // k_pd_gate's word: 0 go, else skip (k_sh_one's fail word, k_gp_one's gate)
+constexpr int FO1S_WORDS = FO1S_GATE + 2;
 static_assert(DP1_GRID_HEAD % 2 == 0, "the grid dispatch's head is two u64");
 static_assert((SH1_HOST + SH1_ST_HEAD) % 2 == 0, "the pick's head is two u64");
 static_assert(GS1_GRID_HEAD % 2 == 0 && FO1S_HEAD % 2 == 0, "the grouping's heads are u64");
@@ -4590,6 +4601,8 @@ static int route32_scratch(tm_index *ix, Lane &ln, const RouteReq &rq, uint64_t 
         if ((rc = grow_dev(ix, s, ln.d_dv, ln.d_dv_cap, GS1_DELIVERIES))) return rc;
         if ((rc = grow_dev(ix, s, ln.d_ds, ln.d_ds_cap, GS1_DELIVERIES))) return rc;
     }
+    // k_sh_one's picks stay on the lane too: k_gp_one copies them out and merges them
+    if (rq.gp && rq.pk && (rc = grow_dev(ix, s, ln.d_sm, ln.d_sm_cap, FO1_ENTRIES))) return rc;
     return TM_OK;
 }
 
@@ -4607,7 +4620,13 @@ static int route32_scratch(tm_index *ix, Lane &ln, const RouteReq &rq, uint64_t 
 // pointers -- its deliveries and its head go to the lane, it expands up to
 // min(dp1_max, gs1_max) deliveries -- and ONE more workgroup, k_gs_one, groups
 // them into the caller's buffers (tm_dev.h launch_group_one); it moves no
-// state, so a run queued again just writes again.
+// state, so a run queued again just writes again.  pk and gp
+// (tm_publish_deliver_batch32): k_dp_one as under gp, then k_pd_gate, which
+// decides once on the device whether the run stands and fits, k_sh_one with
+// the gate's word for its fail word and the lane's d_sm for its out_member,
+// and k_gp_one, which copies the picks out, merges the local ones with the
+// deliveries and groups them into the caller's buffers (tm_dev.h
+// launch_group_picks_one) -- the pick is made exactly when the merge runs.
 static int route32_queue(tm_index *ix, Lane &ln, const RouteReq &rq, const Route32Dev &v, const DevIndex &d,
                          uint32_t tag, uint64_t vcap) {
     int rc;
@@ -4633,6 +4652,8 @@ static int route32_queue(tm_index *ix, Lane &ln, const RouteReq &rq, const Route
     st[FO1_ST_STATE] = 0;   // (the lane's stream is idle: nothing else writes the words)
     st[SH1_HOST + SH1_ST_STATE] = 0;
     st[GS1_HOST + GS1_ST_STATE] = 0;
+    st[PD1_HOST + PD1_ST_STATE] = 0;
+    st[GP1_HOST + GP1_ST_STATE] = 0;
     if (!aggre && !dp) {
         HIPCHK(ix, launch_fanout_one(n, ln.d_pr, ln.d_vals, vcap, dtab, dlen, n_dests, v.fo, v.topic, v.value, cap,
                                      ln.fo1_d, s));
@@ -4659,13 +4680,32 @@ static int route32_queue(tm_index *ix, Lane &ln, const RouteReq &rq, const Route
     if ((rc = subs_upload(ix, grp, s, span, span_len, pool, pool_len))) return rc;
     if (const RouteGroup *gp = rq.gp) {
         uint64_t *lhead = reinterpret_cast<uint64_t *>(ln.fo1_s + FO1S_HEAD);
-        const uint64_t ldcap = std::min<uint64_t>(v.dcap, GS1_DELIVERIES), lmax = std::min(ix->dp1_max, ix->gs1_max);
+        const uint64_t ldcap = std::min<uint64_t>(v.dcap, GS1_DELIVERIES);
+        const uint64_t lmax = std::min({ix->dp1_max, ix->gs1_max, rq.pk ? ix->gp1_max : ix->gs1_max});
         HIPCHK(ix, launch_dispatch_one(st_dev, lfo, ln.d_ft, ln.d_fv, lao, ln.d_at, ln.d_av, n_dests, dp->local_dest, span,
                                        span_len, pool, pool_len, v.fo, v.topic, v.value, cap, lhead, ln.d_dt, ln.d_dv,
                                        ln.d_ds, ldcap, lmax, ln.fo1_d, s));
+        if (const RoutePick *pk = rq.pk) {
+            // tm_publish_deliver_batch32 (pk requires aggre: lao is k_ag_one's).  The share tables and the
+            // member-subs table of this very run's snapshot; the gate decides once for the pick and the merge
+            const uint32_t *slot_of = nullptr, *rec = nullptr, *spool = nullptr, *sub_of = nullptr;
+            uint64_t slot_len = 0, n_slots = 0, spool_len = 0, sub_of_len = 0;
+            uint32_t *state = nullptr, *gate = ln.fo1_s + FO1S_GATE;
+            if ((rc = share_upload(ix, grp, s, slot_of, slot_len, rec, n_slots, spool, spool_len, state))) return rc;
+            if ((rc = msub_upload(ix, grp, s, sub_of, sub_of_len))) return rc;
+            HIPCHK(ix, launch_pd_gate(st_dev, lhead, lao, n_dests, n ? ln.w.hint_d + HINT_FAIL : nullptr, vcap, cap, v.dcap,
+                                      lmax, ix->gp1_max, v.head, gate, ln.fo1_d + PD1_HOST, s));
+            HIPCHK(ix, launch_share_one(st_dev, gate, lao, n_dests, ln.d_at, ln.d_av, vcap, cap, v.kc, v.kt, n, pk->seed,
+                                        slot_of, slot_len, rec, n_slots, spool, spool_len, state, ln.d_sm,
+                                        ln.fo1_d + SH1_HOST, s));
+            HIPCHK(ix, launch_group_picks_one(gate, lhead, ln.d_dt, ln.d_dv, ln.d_ds, lao, n_dests, ln.d_at, ln.d_av,
+                                              ln.d_sm, sub_of, sub_of_len, cap, v.dcap, v.member, v.dtopic, v.dvalue,
+                                              v.dsub, v.ghead, v.gsub, v.goff, gp->gcap, ln.fo1_d + GP1_HOST, s));
+            return TM_OK;
+        }
         HIPCHK(ix, launch_group_one(st_dev, lhead, ln.d_dt, ln.d_dv, ln.d_ds, ldcap, lmax, v.head, v.dtopic, v.dvalue,
                                     v.dsub, v.ghead, v.gsub, v.goff, gp->gcap, ln.fo1_d + GS1_HOST, s));
-        return TM_OK;   // (no pick under a grouping: route_check)
+        return TM_OK;
     }
     HIPCHK(ix, launch_dispatch_one(st_dev, lfo, ln.d_ft, ln.d_fv, lao, ln.d_at, ln.d_av, n_dests, dp->local_dest, span,
                                    span_len, pool, pool_len, v.fo, v.topic, v.value, cap, v.head, v.dtopic, v.dvalue,
@@ -4850,6 +4890,125 @@ static int route32_end_grid(tm_index *ix, HostBatch &hb, const RouteReq &rq, con
     return rc;
 }
 
+// tm_publish_deliver_batch32's grid endings, their common tail (the lock is
+// held when gm.locked; the lane holds the deliveries and d_head = [M, T]): the
+// pick, the merge and the grouping exactly once (pick_after_run), then the
+// grouped arrays copied out and narrowed
+static int route32_pd_tail(tm_index *ix, HostBatch &hb, const RouteReq &rq, uint64_t vcap, uint64_t kept, PickMerge gm) {
+    Lane &ln = *hb.ln;
+    gm.pin = reinterpret_cast<uint8_t *>(ln.fo1_h + GS1_GRID_HEAD);
+    gm.fetch = true;
+    if (int rc = pick_after_run(ix, hb, rq, vcap, kept, &gm)) return rc;
+    uint64_t head[4];
+    std::memcpy(head, ln.fo1_h + GS1_GRID_HEAD, 32);
+    if (int rc = copy_group_out(ix, ln, rq, head)) return rc;
+    ix->publish_deliver_grid++;
+    return head[2] > rq.gp->gcap ? TM_ECAP : TM_OK;
+}
+
+// The endings of tm_publish_deliver_batch32 in place.  The host's own view of
+// the run that stands (the loop is over: total <= vcap, no look-back failure)
+// against the three kernels' status words: the gate said go, k_sh_one picked
+// and k_gp_one grouped exactly when the run hands over its entries (total <=
+// cap), T + K fits dcap and one workgroup takes them.
+//   one workgroup   everything is in the caller's buffers; or a capacity is
+//                   short (total > cap, T + K > dcap): TM_ECAP, nothing moved.
+//   the lane's grid T or T + K past one workgroup's limit: the aggre pass's u32
+//                   offsets are widened beside the arrays, the grid dispatch
+//                   runs into the lane where k_dp_one did not expand, then
+//                   route32_pd_tail.
+//   the pairs' grid FO1_TOO_LARGE: the grid fan-out, aggre and dispatch on the
+//                   same pairs (no second walk) as route32_end_grid, the route
+//                   outputs copied out and narrowed, tm_publish_deliver_batch's
+//                   capacity rules, then route32_pd_tail.
+static int route32_end_publish_deliver(tm_index *ix, HostBatch &hb, const RouteReq &rq, uint32_t *out_dest_offsets,
+                                       uint64_t total, uint64_t vcap, uint32_t state) {
+    int rc;
+    Lane &ln = *hb.ln;
+    const hipStream_t s = ln.s;
+    const RouteDispatch *dp = rq.dp;
+    const RouteGroup *gp = rq.gp;
+    const uint32_t n_dests = rq.n_dests;
+    const volatile uint32_t *st = ln.fo1_h;
+    const uint64_t dcap = std::min<uint64_t>(dp->dcap, 0xFFFFFFFFull);
+    uint64_t *lhead = reinterpret_cast<uint64_t *>(ln.fo1_s + FO1S_HEAD);
+    if (state != FO1_DONE && state != (uint32_t)DP1_TOO_LARGE && state != FO1_TOO_LARGE)
+        return route_fail(ix, rq, TM_EDEVICE, "the fan-out kernel left no status");
+    const bool done = state != FO1_TOO_LARGE;   // k_fo_one and k_ag_one completed: T and K are known
+    const uint64_t T = (uint64_t)st[DP1_ST_T_HI] << 32 | st[DP1_ST_T_LO], K = st[PD1_HOST + PD1_ST_K];
+    const uint32_t pd = st[PD1_HOST + PD1_ST_STATE], ps = st[SH1_HOST + SH1_ST_STATE], gs = st[GP1_HOST + GP1_ST_STATE];
+    const bool fits = done && total <= rq.cap && T + K <= dcap;
+    const bool want = fits && state == FO1_DONE && T + K <= std::min<uint64_t>(ix->gp1_max, GP1_DELIVERIES);
+    if ((pd != PD1_GO && pd != PD1_SKIP) || (ps != SH1_PICKED && ps != SH1_SKIPPED) ||
+        (gs != GP1_GROUPED && gs != GP1_SKIPPED) || (pd == PD1_GO) != want || (ps == SH1_PICKED) != want ||
+        (gs == GP1_GROUPED) != want)
+        return route_fail(ix, rq, TM_EDEVICE, "the gate, the pick and the merge kernels and the host disagree on whether "
+                                              "the run stands");
+    if (want) {
+        ix->publish_deliver_one++;
+        ix->gs1_passes[0] += st[GP1_HOST + GP1_ST_RUN];
+        ix->gs1_passes[1] += st[GP1_HOST + GP1_ST_SKIPPED];
+        return st[GP1_HOST + GP1_ST_G] > gp->gcap ? TM_ECAP : TM_OK;
+    }
+    if (done && !fits) {   // nothing moved; out_head and the bucket offsets size the retry
+        gp->out_ghead[0] = gp->out_ghead[1] = 0;
+        ix->publish_deliver_one++;
+        return TM_ECAP;
+    }
+    const uint64_t nfo = (uint64_t)n_dests + 2;
+    if ((rc = hb.relock())) return rc;
+    if (done) {
+        if ((rc = ensure_dispatch(ix, ln, FO1_ENTRIES, true))) return rc;
+        if ((rc = grow_dev(ix, s, ln.d_o64, ln.d_o64_cap, nfo))) return rc;
+        HIPCHK(ix, launch_offs_widen(reinterpret_cast<const uint32_t *>(ln.d_ao), ln.d_o64, nfo, s));
+        if (state == (uint32_t)DP1_TOO_LARGE) {   // (T <= dcap: the lane takes every delivery, no retry)
+            if ((rc = dispatch_scratch(ix, ln, FO1_ENTRIES, T))) return rc;
+            if ((rc = queue_dispatch_to(ix, ln, n_dests, dp->local_dest, ln.d_o64, true, FO1_ENTRIES, T, lhead, ln.d_dt,
+                                        ln.d_dv, ln.d_ds)))
+                return rc;
+        }
+        PickMerge gm{lhead, T, gp->gcap, nullptr, true, ln.d_o64, true};
+        return route32_pd_tail(ix, hb, rq, FO1_ENTRIES, K, gm);
+    }
+    std::vector<uint64_t> fo;
+    try {
+        fo.resize(nfo);
+    } catch (const std::bad_alloc &) {
+        return route_fail(ix, rq, TM_ENOMEM, "out of host memory");
+    }
+    if ((rc = route_scratch(ix, ln, n_dests, vcap, true, true, rq.n))) return rc;
+    if ((rc = queue_grid_fanout(ix, ln, rq.n, nullptr, ln.d_pr, vcap, n_dests, true))) return rc;
+    uint64_t head[2] = {0, 0}, dwant = std::min(std::max<uint64_t>(ln.d_ds_cap, 1 << 16), dcap);
+    for (int attempt = 0;; attempt++) {
+        if ((rc = dispatch_scratch(ix, ln, vcap, dwant))) return rc;
+        if ((rc = queue_dispatch_to(ix, ln, n_dests, dp->local_dest, ln.d_ao, true, vcap, dwant, lhead, ln.d_dt, ln.d_dv,
+                                    ln.d_ds)))
+            return rc;
+        HIPCHK(ix, hipMemcpyAsync(ln.fo1_h + GS1_GRID_HEAD, lhead, 16, hipMemcpyDeviceToHost, s));
+        if ((rc = batch_done(ix, ln))) return rc;
+        hb.g.unlock();
+        HIPCHK(ix, hipStreamSynchronize(s));
+        std::memcpy(head, ln.fo1_h + GS1_GRID_HEAD, 16);
+        if (std::min(head[1], dcap) <= dwant) break;
+        if (attempt >= 2) return route_fail(ix, rq, TM_EDEVICE, "the delivery total kept growing past the scratch");
+        dwant = std::min(head[1] + head[1] / 4, dcap);
+        if ((rc = hb.relock())) return rc;
+    }
+    rc = copy_route_out(ix, ln, n_dests, total, rq.cap, true, total <= rq.cap, fo.data(), out_dest_offsets, rq.out_topic,
+                        rq.out_values);
+    if (rc != TM_OK && rc != TM_ECAP) return rc;
+    const uint64_t kept = rc == TM_OK ? std::min(fo[n_dests + 1], rq.cap) : 0;
+    dp->out_head[0] = head[0];
+    dp->out_head[1] = head[1];
+    gp->out_ghead[0] = gp->out_ghead[1] = 0;
+    if (rc != TM_OK || head[1] + kept > dp->dcap || head[1] + kept > 0xFFFFFFFFull) {
+        ix->publish_deliver_grid++;
+        return TM_ECAP;
+    }
+    PickMerge gm{lhead, head[1], gp->gcap, nullptr, true};
+    return route32_pd_tail(ix, hb, rq, vcap, kept, gm);
+}
+
 // the in-place attempt of route_batch32: the stages above, in order
 static int route32_in_place(tm_index *ix, const RouteReq &rq, const uint32_t *to, uint64_t nbytes,
                             uint32_t *out_dest_offsets) {
@@ -4881,6 +5040,7 @@ static int route32_in_place(tm_index *ix, const RouteReq &rq, const uint32_t *to
         if ((rc = hb.relock())) return rc;
     }
     const uint32_t state = st[FO1_ST_STATE];
+    if (rq.pk && rq.gp) return route32_end_publish_deliver(ix, hb, rq, out_dest_offsets, total, vcap, state);
     if (rq.pk && (rc = route32_pick_status(ix, ln, rq, total, state))) return rc;
     if (rq.gp && (rc = route32_group_status(ix, ln, rq, state))) return rc;
     if (state == FO1_DONE) return route32_end_in_place(ix, ln, rq, total);
@@ -4914,7 +5074,8 @@ static int route_batch32(tm_index *ix, RouteReq rq, const uint32_t *to, uint32_t
     if (rc != TM_OK && rc != TM_ECAP) return rc;
     for (size_t i = 0; i < fo.size(); i++) out_dest_offsets[i] = (uint32_t)fo[i];
     // (rq.gp: copy_group_out narrowed the groups' offsets into out_goff32)
-    (rq.gp ? ix->deliver_grid : rq.pk ? ix->publish_grid : rq.dp ? ix->dispatch_grid : ix->route_grid)++;
+    (rq.gp && rq.pk ? ix->publish_deliver_grid : rq.gp ? ix->deliver_grid : rq.pk ? ix->publish_grid :
+     rq.dp ? ix->dispatch_grid : ix->route_grid)++;
     return rc;
 }
 
@@ -4961,6 +5122,20 @@ int tm_deliver_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32
     // (G <= W < 2^32: a larger gcap asks for nothing more)
     const RouteGroup gp{out_ghead, out_gsub, nullptr, std::min<uint64_t>(gcap, 0xFFFFFFFFull), out_goff};
     return route_batch32(ix, {"tm_deliver_batch32", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, &dp, nullptr, &gp},
+                         to, out_dest_offsets);
+}
+
+int tm_publish_deliver_batch32(tm_index *ix, uint64_t n, const uint8_t *tb, const uint32_t *to, uint32_t n_dests,
+                               uint32_t local_dest, uint32_t flags, uint32_t *out_dest_offsets, uint32_t *out_topic,
+                               uint32_t *out_values, uint64_t cap, uint64_t *out_head, uint32_t *out_dtopic,
+                               uint32_t *out_dvalue, uint32_t *out_dsub, uint64_t dcap, const uint32_t *key_clientid,
+                               const uint32_t *key_topic, uint32_t seed, uint32_t *out_member, uint64_t *out_ghead,
+                               uint32_t *out_gsub, uint32_t *out_goff, uint64_t gcap, uint8_t *out_err) {
+    const RouteDispatch dp{local_dest, out_head, out_dtopic, out_dvalue, out_dsub, dcap};
+    const RoutePick pk{key_clientid, key_topic, seed, out_member};
+    const RouteGroup gp{out_ghead, out_gsub, nullptr, std::min<uint64_t>(gcap, 0xFFFFFFFFull), out_goff};
+    return route_batch32(ix, {"tm_publish_deliver_batch32", n, tb, n_dests, flags, out_topic, out_values, cap, out_err, &dp, &pk,
+                              &gp},
                          to, out_dest_offsets);
 }
 
@@ -5100,6 +5275,7 @@ int tm_debug_set(tm_index *ix, uint32_t key, uint64_t value) {
     case TM_DEBUG_PATCH_ZC: ix->patch_zc = value != 0; break;
     case TM_DEBUG_DP1_MAX: ix->dp1_max = std::min<uint64_t>(value, DP1_DELIVERIES); break;
     case TM_DEBUG_GS1_MAX: ix->gs1_max = std::min<uint64_t>(value, GS1_DELIVERIES); break;
+    case TM_DEBUG_GP1_MAX: ix->gp1_max = std::min<uint64_t>(value, GP1_DELIVERIES); break;
     case TM_DEBUG_SMALL_KERNEL:
         if (value != SMALL_AUTO && value != SMALL_WAVE && value != SMALL_WAVE8)
             return fail(ix, TM_EINVAL, "tm_debug_set: TM_DEBUG_SMALL_KERNEL is 0, 1 or 3 (2, the lane kernel, was removed)");
@@ -5148,6 +5324,13 @@ int tm_debug_get(tm_index *ix, uint32_t key, uint64_t *value) {
         *value = ix->gs1_max;
         break;
     }
+    case TM_DEBUG_GP1_MAX: {
+        std::lock_guard<std::mutex> g(ix->mu);
+        *value = ix->gp1_max;
+        break;
+    }
+    case TM_DEBUG_PUBLISH_DELIVER_ONE: *value = ix->publish_deliver_one.load(); break;
+    case TM_DEBUG_PUBLISH_DELIVER_GRID: *value = ix->publish_deliver_grid.load(); break;
     case TM_DEBUG_DP1_MAX: {
         std::lock_guard<std::mutex> g(ix->mu);
         *value = ix->dp1_max;

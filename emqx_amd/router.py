@@ -153,7 +153,9 @@ class Router:
         match_routes_dispatch through dispatch_kids32 (tm_dispatch_batch32)
         instead of dispatch_kids, match_routes_publish through publish_kids32
         (tm_publish_batch32) instead of publish_kids, match_routes_deliver
-        through deliver_kids32 (tm_deliver_batch32) instead of deliver_kids.
+        through deliver_kids32 (tm_deliver_batch32) instead of deliver_kids,
+        match_routes_publish_deliver through publish_deliver_kids32
+        (tm_publish_deliver_batch32) instead of publish_deliver_kids.
         local_subs: this node's subscribers.LocalSubs; the device list of every
         route key {Filter, node()} then follows it (tm_set_subscribers), for
         match_routes_dispatch.
@@ -404,8 +406,8 @@ class Router:
     def match_routes_publish_deliver(self, topics, key_clientid=None, key_topic=None, seed: int = 0,
                                      errors: str = "raise"):
         """match_routes_publish with the local picks grouped with the deliveries
-        on the device (tm_publish_deliver_batch; route_in_place takes the same
-        staged call for now) -> (ByDest, deliveries, picks, by_sub): the first
+        on the device (tm_publish_deliver_batch; tm_publish_deliver_batch32 with
+        route_in_place) -> (ByDest, deliveries, picks, by_sub): the first
         three are exactly match_routes_publish's; by_sub = {pid: [(message
         index, To)]} holds a connection's direct deliveries and the picks that
         fell on it (member_is_local) together, in publish order -- inside a
@@ -839,8 +841,10 @@ class Router:
                 if local == UNROUTED:
                     raise ValueError("match_routes_dispatch: this node has no destination id")
                 if publish is not None and merged:
-                    (doff, tidx, kids, err), mdel, member, mgrp, _ = mirror.publish_deliver_kids(topics, n_dests, local,
-                                                                                                 *publish)
+                    # (a mirror written before tm_publish_deliver_batch32 has no in-place call: the staged one)
+                    pdl = getattr(mirror, "publish_deliver_kids32", None) if self._route_in_place else None
+                    pdl = pdl or mirror.publish_deliver_kids
+                    (doff, tidx, kids, err), mdel, member, mgrp, _ = pdl(topics, n_dests, local, *publish)
                     gdel, ggrp, pick_groups = self._split_merged(mirror, mdel, mgrp)
                     (dt, dk, ds), dev_groups = self._ungroup(mirror, doff, tidx, kids, local, gdel, ggrp)
                 elif publish is not None:

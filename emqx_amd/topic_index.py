@@ -559,6 +559,66 @@ class Tab:
         buffers go back to the pool)."""
         return self._kids32(topics, n_dests, local_dest, True, (key_clientid, key_topic, seed))
 
+    def publish_deliver_kids32(self, topics, n_dests: int, local_dest: int, key_clientid=None, key_topic=None,
+                               seed: int = 0):
+        """publish_deliver_kids through tm_publish_deliver_batch32 on pooled pinned
+        buffers: a micro-batch is matched, fanned out, dispatched, picked for,
+        merged and grouped by subscriber in place (one synchronisation, no
+        staging copy).  The member-subs table is shipped ahead by the flush, as
+        in publish_deliver_kids.  The delivery arrays have room for T + K of the
+        previous sizes and the group arrays for a group per delivery, so a short
+        gcap cannot occur.  TM_ECAP from the entries or the deliveries: no pick
+        was made and no state moved, so the call is made once more, sized from
+        the bucket offsets and the head.  Returns what publish_deliver_kids
+        returns (copies: the buffers go back to the pool)."""
+        self.flush()
+        ix = self._index
+        blob, offs = _native.pack_strings(topics)
+        n, nbytes = len(offs) - 1, int(offs[-1])
+        if nbytes >= 1 << 32:   # no 32-bit offsets for them: the staged call
+            return ix.publish_deliver_batch(blob, offs, n_dests, local_dest, key_clientid=key_clientid,
+                                            key_topic=key_topic, seed=seed)
+        first = max(4 * n, 1024)
+        s = self._route_set(n, nbytes, n_dests, first, 2 * first, True, True)
+        try:
+            s["blob"][:nbytes] = blob[:nbytes]
+            s["offs"][: n + 1] = offs
+            keys = []
+            for name, k in (("kc", key_clientid), ("kt", key_topic)):
+                if k is None:
+                    keys.append(None)
+                    continue
+                k = np.asarray(k, dtype=np.uint32)
+                if len(k) < n:
+                    raise ValueError("publish_deliver_kids32: one key word per topic")
+                s[name][:n] = k[:n]
+                keys.append(s[name][:max(n, 1)])
+            for attempt in (0, 1):
+                if len(s["gsub"]) < len(s["dsubs"]) or len(s["goff"]) < len(s["dsubs"]) + 1:   # a group per delivery
+                    self._route_grow(s, "gsub", len(s["dsubs"]))
+                    self._route_grow(s, "goff", len(s["dsubs"]) + 1)
+                out = (s["doff"], s["topic"], s["vals"], s["err"], s["head"], s["dtopic"], s["dvals"], s["dsubs"], s["ghead"],
+                       s["gsub"], s["goff"])
+                try:
+                    route, deliveries, member, groups, T = ix.publish_deliver_batch32(
+                        s["blob"], s["offs"][: n + 1], n_dests, local_dest, out, s["member"], keys[0], keys[1], seed)
+                    break
+                except _native.TmError as e:
+                    if e.code != _native.TM_ECAP or attempt:
+                        raise
+                # nothing moved: the entry arrays grow from the bucket offsets (under total > cap the
+                # un-aggregated total, an upper bound of K), the delivery arrays to T + that
+                total, T = int(s["doff"][n_dests + 1]), int(s["head"][1])
+                for names, need in ((("topic", "vals", "member"), total), (("dtopic", "dvals", "dsubs"), T + total)):
+                    if need > min(len(s[name]) for name in names):
+                        for name in names:
+                            self._route_grow(s, name, need)
+            doff, tidx, kids, err = route
+            return (doff.astype(np.uint64), tidx.copy(), kids.copy(), err.copy()), tuple(a.copy() for a in deliveries), \
+                member.copy(), (groups[0].copy(), groups[1].astype(np.uint64)), T
+        finally:
+            self._route_put(s)
+
     def read_begin(self) -> int:
         return self._index.read_begin()
 

@@ -1099,6 +1099,60 @@ int tm_publish_deliver_batch(tm_index *h, uint64_t n, const uint8_t *topic_bytes
                              uint32_t *out_member, uint64_t *out_ghead, uint32_t *out_gsub, uint64_t *out_goff,
                              uint64_t gcap, uint8_t *out_err);
 
+/* tm_publish_deliver_batch32 (ABI minor 23): tm_publish_deliver_batch with
+ * 32-bit offsets in and out, for the NIF's micro-batches: the last link of the
+ * publish chain in place.  For the same index state, arguments and start state
+ * of the slots the return code, every route output, out_head = [M, T],
+ * out_member[0 .. K), the merged and grouped delivery arrays, out_ghead = [G,
+ * N], out_gsub, out_goff and the state words afterwards are
+ * tm_publish_deliver_batch's: out_dest_offsets narrowed to u32 as in
+ * tm_publish_batch32, out_goff narrowed to u32 (gcap + 1 words; entry 0 is
+ * written whatever gcap is); out_head and out_ghead stay u64[2] and must be
+ * 8-byte aligned.  Nothing is written at or past min(total, cap) in out_topic /
+ * out_values, K in out_member, min(N, dcap) in the three delivery arrays,
+ * min(G, gcap) in out_gsub, nor past out_goff[min(G, gcap)].  TM_ECAP:
+ * tm_publish_deliver_batch's three rules, to the letter:
+ *   total > cap     no pick, no state.
+ *   T + K > dcap    no pick, no state; nothing is written to the delivery
+ *                   arrays, the group outputs or out_member, out_ghead = [0,
+ *                   0]; out_head and the bucket offsets size the retry.
+ *   G > gcap alone  the picks stand and the state has moved once; the grouped
+ *                   arrays are complete and out_ghead is exact.
+ * TM_EINVAL: whatever tm_publish_batch32 refuses, a null out_ghead or
+ * out_goff, a null out_gsub with gcap > 0, a misaligned out_ghead.
+ * In place -- no staging copy, no copy out, one synchronisation, everything
+ * queued in one hold of the index lock on the lane's stream -- when
+ * tm_publish_batch32's conditions hold and out_ghead, out_gsub and out_goff lie
+ * in this index's tm_host_alloc memory too; the device never reads a caller's
+ * buffer.  Behind the walk, the fan-out and the aggre pass the one-workgroup
+ * dispatch leaves its deliveries on the device; one wave (the gate) then
+ * decides, on the device and once, whether the run stands (tm_publish_batch32's
+ * own conditions), T + K <= dcap and one workgroup takes them, and writes
+ * out_head; the one-workgroup pick of tm_publish_batch32 picks and moves the
+ * state exactly when the gate says so; and ONE more workgroup copies the picks
+ * to out_member, flags the local ones against the tm_set_member_subs table,
+ * compacts them, sorts them by message, merges them with the deliveries by
+ * binary searches and sorts the merged deliveries by subscriber, all inside
+ * LDS, and writes the grouped arrays, the groups and out_ghead into the
+ * caller's buffers.  The member-subs table is uploaded in the same hold of the
+ * lock as the walk is queued in: it is the run's own snapshot, which is
+ * stricter than tm_publish_deliver_batch's "as of the moment the pick is
+ * queued", never looser.  That workgroup takes at most 8192 merged deliveries
+ * (T + K; TM_DEBUG_GP1_MAX lowers that, TM_DEBUG_GS1_MAX and TM_DEBUG_DP1_MAX
+ * too: the smallest wins).  More than that, or more than 16384 route entries:
+ * no pick has been made, and the grid dispatch (where needed), the grid pick,
+ * merge and grouping run once on the arrays still on the device and the
+ * results are copied out -- never a second walk.  The one-workgroup ending
+ * does everything or moves nothing.  Every other batch is widened, run by
+ * tm_publish_deliver_batch, and narrowed. */
+int tm_publish_deliver_batch32(tm_index *h, uint64_t n, const uint8_t *topic_bytes, const uint32_t *topic_offsets,
+                               uint32_t n_dests, uint32_t local_dest, uint32_t flags,
+                               uint32_t *out_dest_offsets, uint32_t *out_topic, uint32_t *out_values, uint64_t cap,
+                               uint64_t *out_head, uint32_t *out_dtopic, uint32_t *out_dvalue, uint32_t *out_dsub,
+                               uint64_t dcap, const uint32_t *key_clientid, const uint32_t *key_topic, uint32_t seed,
+                               uint32_t *out_member, uint64_t *out_ghead, uint32_t *out_gsub, uint32_t *out_goff,
+                               uint64_t gcap, uint8_t *out_err);
+
 /* Release the batch scratch kept for `stream` (after its batches finish);
  * a caller that retires a stream calls this.  No reference counterpart. */
 int tm_stream_release(tm_index *h, void *stream);
@@ -1216,7 +1270,16 @@ int tm_profile_read(tm_index *h, double *walk_ms, double *batch_ms, uint64_t *ba
  * TM_DEBUG_DELIVER_GRID (get only): tm_deliver_batch32 calls the one-workgroup
  * grouping completed / that the grid kernels or the staged path finished.
  * TM_DEBUG_GS1_MAX (set / get): the deliveries up to which that workgroup
- * groups them itself, clamped to the compiled bound (16384). */
+ * groups them itself, clamped to the compiled bound (16384).
+ * TM_DEBUG_GP1_MAX (set / get): the merged deliveries (T + K) up to which
+ * tm_publish_deliver_batch32's one workgroup merges and groups them itself,
+ * clamped to the compiled bound (8192).  TM_DEBUG_PUBLISH_DELIVER_ONE /
+ * TM_DEBUG_PUBLISH_DELIVER_GRID (get only): tm_publish_deliver_batch32 calls
+ * the one-workgroup ending finished (merged and grouped, or TM_ECAP with
+ * nothing moved) / that the grid kernels or the staged path finished.  The
+ * one workgroup's digit passes are counted in TM_DEBUG_GROUP_PASSES_RUN /
+ * _SKIPPED: four per sort, the picks' by message and the merged deliveries' by
+ * subscriber. */
 enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES = 3, TM_DEBUG_PHASES = 4,
        TM_DEBUG_FAILED_BATCHES = 5, TM_DEBUG_RETRIED_BATCHES = 6, TM_DEBUG_PATH_PHASES = 7,
        TM_DEBUG_PATH_SMALL = 8, TM_DEBUG_PATH_LANE = 9, TM_DEBUG_SMALL_KERNEL = 10,
@@ -1228,7 +1291,8 @@ enum { TM_DEBUG_LB_SPINS = 1, TM_DEBUG_LB_FAIL_BLOCK = 2, TM_DEBUG_LB_LAUNCHES =
        TM_DEBUG_HINT_AUDIT = 30, TM_DEBUG_SUB_COMPACTIONS = 31, TM_DEBUG_DISPATCH_ONE = 32,
        TM_DEBUG_DISPATCH_GRID = 33, TM_DEBUG_DP1_MAX = 34, TM_DEBUG_PUBLISH_ONE = 35, TM_DEBUG_PUBLISH_GRID = 36,
        TM_DEBUG_GROUP_TILE = 37, TM_DEBUG_GROUP_PASSES_RUN = 38, TM_DEBUG_GROUP_PASSES_SKIPPED = 39,
-       TM_DEBUG_GROUP_GRID = 40, TM_DEBUG_DELIVER_ONE = 41, TM_DEBUG_DELIVER_GRID = 42, TM_DEBUG_GS1_MAX = 43 };
+       TM_DEBUG_GROUP_GRID = 40, TM_DEBUG_DELIVER_ONE = 41, TM_DEBUG_DELIVER_GRID = 42, TM_DEBUG_GS1_MAX = 43,
+       TM_DEBUG_GP1_MAX = 44, TM_DEBUG_PUBLISH_DELIVER_ONE = 45, TM_DEBUG_PUBLISH_DELIVER_GRID = 46 };
 int tm_debug_set(tm_index *h, uint32_t key, uint64_t value);
 int tm_debug_get(tm_index *h, uint32_t key, uint64_t *value);
 

@@ -154,7 +154,13 @@ through tm_set_member_subs); tm_publish_deliver_batch beside tm_publish_batch
 and tm_deliver_batch, host to host and interleaved, at 64 / 1,024 / 4,096
 topics (--sizes); its grouped arrays are checked against the definition applied
 to tm_publish_batch's deliveries and its own entries and picks; pair_p50_ms is
-the two calls' sum, merged_over_pair the new call over it.
+the two calls' sum, merged_over_pair the new call over it.  The in-place legs run
+beside them on tm_host_alloc buffers: tm_publish_batch32, tm_deliver_batch32 and
+tm_publish_deliver_batch32, whose outputs and state words are compared with the
+staged call's from the same start state first (--no-pd32-leg leaves the last one
+out, so that a library from before it, given through TM_LIB, runs the same
+rounds); staged_over_in_place is the staged call's p50 over the new leg's,
+merged32_minus_publish32_ms what the merge adds over tm_publish_batch32.
 """
 import argparse
 import json
@@ -1158,6 +1164,58 @@ def small_group_share(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=
             np.array_equal(dm[2][:N], cs[perm]) and np.array_equal(gsub[:G], np.unique(cs)), \
             f"n {n}: tm_publish_deliver_batch differs from the definition"
         legs = [("publish_batch", leg_p), ("deliver_batch", leg_g), ("publish_deliver_batch", leg_m)]
+        # the in-place forms on tm_host_alloc buffers: tm_publish_batch32, tm_deliver_batch32 and, merged and
+        # grouped, tm_publish_deliver_batch32 (a library from before it, or --no-pd32-leg: the first two alone)
+        pinned, took = [], None
+        has_pd32 = hasattr(lib, "tm_publish_deliver_batch32") and not a.no_pd32_leg
+        if hasattr(lib, "tm_publish_batch32") and hasattr(lib, "tm_deliver_batch32"):
+            def pin(k, dt):
+                pinned.append(ix.host_array(k, dt))
+                return pinned[-1]
+            nb = int(offs[-1])
+            b32, o32, e32, k32 = pin(nb + 16, np.uint8), pin(n + 1, np.uint32), pin(n, np.uint8), pin(n, np.uint32)
+            b32[:nb], o32[:], k32[:] = blob[:nb], offs.astype(np.uint32), kc
+            d32, h32, gh32 = pin(n_dests + 2, np.uint32), pin(2, np.uint64), pin(2, np.uint64)
+            t32, v32, m32 = (pin(cap, np.uint32) for _ in range(3))
+            dd32 = tuple(pin(dcap, np.uint32) for _ in range(3))
+            gs32, go32 = pin(dcap, np.uint32), pin(dcap + 1, np.uint32)
+
+            def leg_p32():
+                return lib.tm_publish_batch32(h, n, P(b32), P(o32), n_dests, local, 1, P(d32), P(t32), P(v32), cap, P(h32),
+                                              P(dd32[0]), P(dd32[1]), P(dd32[2]), dcap, P(k32), P(k32), 1, P(m32), P(e32))
+
+            def leg_g32():
+                return lib.tm_deliver_batch32(h, n, P(b32), P(o32), n_dests, local, 1, P(d32), P(t32), P(v32), cap, P(h32),
+                                              P(dd32[0]), P(dd32[1]), P(dd32[2]), dcap, P(gh32), P(gs32), P(go32), dcap,
+                                              P(e32))
+
+            def leg_m32():
+                return lib.tm_publish_deliver_batch32(h, n, P(b32), P(o32), n_dests, local, 1, P(d32), P(t32), P(v32), cap,
+                                                      P(h32), P(dd32[0]), P(dd32[1]), P(dd32[2]), dcap, P(k32), P(k32), 1,
+                                                      P(m32), P(gh32), P(gs32), P(go32), dcap, P(e32))
+
+            assert leg_p32() == 0 and leg_g32() == 0, "an in-place leg failed"
+            legs += [("publish_batch32", leg_p32), ("deliver_batch32", leg_g32)]
+            if has_pd32:
+                # outputs equal first: both from the same start state of the slots
+                slots = np.arange(len(grp), dtype=np.uint32)
+                start = ix.share_state_get(slots)
+                assert leg_m() == 0
+                after = ix.share_state_get(slots)
+                ix.share_state_set(slots, start)
+                ONE = _native.TM_DEBUG_PUBLISH_DELIVER_ONE
+                c0 = ix.debug_get(ONE)
+                assert leg_m32() == 0
+                took = "one_workgroup" if ix.debug_get(ONE) > c0 else "grid_or_staged"
+                K2, N2, G2 = int(d64[n_dests + 1]), int(ghead[1]), int(ghead[0])
+                assert gh32.tolist() == ghead.tolist() and h32.tolist() == head.tolist() and \
+                    np.array_equal(d32[: n_dests + 2].astype(np.uint64), d64) and np.array_equal(m32[:K2], m2[:K2]) and \
+                    np.array_equal(t32[:K2], t2[:K2]) and np.array_equal(v32[:K2], v2[:K2]) and \
+                    all(np.array_equal(x[:N2], y[:N2]) for x, y in zip(dd32, dm)) and \
+                    np.array_equal(gs32[:G2], gsub[:G2]) and np.array_equal(go32[:G2 + 1].astype(np.uint64), goff[:G2 + 1]) and \
+                    np.array_equal(ix.share_state_get(slots), after), \
+                    f"n {n}: tm_publish_deliver_batch32 differs from tm_publish_deliver_batch"
+                legs.append(("publish_deliver_batch32", leg_m32))
         ms = {k: [] for k, _ in legs}
         for r in range(warmup + reps):
             for k, f in legs:
@@ -1169,14 +1227,22 @@ def small_group_share(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=
         st = {k: dict(stats(v), p50_ms=round(float(np.median(v)), 4), p99_ms=round(float(np.percentile(v, 99)), 4))
               for k, v in ms.items()}
         pair = st["publish_batch"]["p50_ms"] + st["deliver_batch"]["p50_ms"]
-        print(json.dumps({"tool": "fanout_bench", "kind": "small_group_share", "filters": fs_len, "topics": n,
-                          "kept_entries": K, "n_dests": n_dests, "groups_shared": n_groups, "deliveries": T,
-                          "local_picks": len(pq), "merged": N, "subscribers": G, "warmup": warmup, "reps": reps, **st,
-                          "pair_p50_ms": round(pair, 4),
-                          "merged_over_pair": round(st["publish_deliver_batch"]["p50_ms"] / pair, 3),
-                          "merged_minus_publish_ms": round(st["publish_deliver_batch"]["p50_ms"] -
-                                                           st["publish_batch"]["p50_ms"], 4),
-                          "identical": True}), flush=True)
+        line = {"tool": "fanout_bench", "kind": "small_group_share", "filters": fs_len, "topics": n,
+                "kept_entries": K, "n_dests": n_dests, "groups_shared": n_groups, "deliveries": T,
+                "local_picks": len(pq), "merged": N, "subscribers": G, "warmup": warmup, "reps": reps, **st,
+                "pair_p50_ms": round(pair, 4),
+                "merged_over_pair": round(st["publish_deliver_batch"]["p50_ms"] / pair, 3),
+                "merged_minus_publish_ms": round(st["publish_deliver_batch"]["p50_ms"] - st["publish_batch"]["p50_ms"], 4),
+                "identical": True}
+        if took is not None:
+            line["merged32_by"] = took
+            line["staged_over_in_place"] = round(st["publish_deliver_batch"]["p50_ms"] /
+                                                 st["publish_deliver_batch32"]["p50_ms"], 2)
+            line["merged32_minus_publish32_ms"] = round(st["publish_deliver_batch32"]["p50_ms"] -
+                                                        st["publish_batch32"]["p50_ms"], 4)
+        print(json.dumps(line), flush=True)
+        for x in pinned:
+            ix.host_free(x)
 
 
 def small_group(a, ix, fs_len, nvals, sizes, n_dests, warmup, reps, local=0):
@@ -1315,6 +1381,9 @@ def main():
                    help="--small --share: time tm_dispatch_batch alone, as a library without tm_publish_batch is timed")
     p.add_argument("--no-deliver32-leg", action="store_true",
                    help="--small --group: leave the tm_deliver_batch32 leg out, as a library without it is timed")
+    p.add_argument("--no-pd32-leg", action="store_true",
+                   help="--small --group --share: leave the tm_publish_deliver_batch32 leg out, as a library without it "
+                        "is timed (the two in-place legs beside it stay)")
     p.add_argument("--sizes", type=int, nargs="+", default=None, help="--small: the batch sizes")
     p.add_argument("--dp1-max", type=int, default=None,
                    help="--small --dispatch: TM_DEBUG_DP1_MAX for the dispatch_batch32 leg (default: the compiled bound)")
