@@ -1450,7 +1450,9 @@ int upload_full(tm_index *ix, Mirror<T> &m) {
     for (int r = 0; r < ix->nrep; r++)
         if (int rc = bring_up(ix, r, ix->patch_seq, ix->rep[r].ps)) return rc;
     uint64_t need = std::max<uint64_t>(m.h.size(), 1);
-    const bool grow = need > m.dcap;
+    // (collect's condition: a table within DEV_GUARD of its allocation grows, or every collect from
+    // then on would ship it whole again, the guard shrinking to nothing, until it outgrew the allocation)
+    const bool grow = need + DEV_GUARD > m.dcap;
     const uint64_t cap = grow ? need + need / 2 + DEV_GUARD : m.dcap;
     // a failure part way leaves the device copies in doubt: dcap 0 makes the
     // next collect reallocate and ship the whole table again (its dirty set
