@@ -8,9 +8,11 @@
  * run as a subprocess by tests/test_publish_deliver32_cpu.py: slices, picks,
  * merged and grouped deliveries, one rerun per kind of TM_ECAP (entries,
  * deliveries, one after the other) with the stand-in's state moved once each
- * time, err 4 -> TM_EDEVICE, tmn_give and the pool's destruction (every buffer
- * freed).  Prints "ok" and exits 0, or the line of the first failed check and
- * exits 1.
+ * time, err 4 -> TM_EDEVICE, one set through every entry point in turn with the
+ * readers refusing the wrong kind and the calls refused before any library call
+ * (the CPU twin of tests/test_gpu_nif_chain.py), tmn_give and the pool's
+ * destruction (every buffer freed).  Prints "ok" and exits 0, or the line of the
+ * first failed check and exits 1.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -29,6 +31,10 @@ long fake_pd_moves(void);
 uint64_t fake_pd_cap(long call);
 uint64_t fake_pd_dcap(long call);
 uint64_t fake_pd_gcap(long call);
+long fake_publish_count(void);
+long fake_deliver_count(void);
+long fake_dispatch_count(void);
+long fake_route_count(void);
 
 #define CHECK(c) do { if (!(c)) { printf("line %d: %s\n", __LINE__, #c); exit(1); } } while (0)
 
@@ -202,6 +208,82 @@ int main(void) {
     pack(s, 2, fine);
     CHECK(tmn_publish_deliver(s, H, 2, 2, 1, 0) == TM_OK);
     verify(s, 2, fine, 2, 1, 0, 0, 0);
+    tmn_give(&pool, s);
+
+    /* 5b. the CPU twin of tests/test_gpu_nif_chain.py's "one set through every entry point" and "refusals":
+       tmn_route, tmn_dispatch, tmn_publish, tmn_deliver, tmn_publish_deliver, tmn_match, tmn_first and back on
+       ONE set; after each, every reader either reads that call's kind or refuses (TM_EINVAL, nothing handed
+       out); a refused call leaves nothing to read, makes no library call, and the set works afterwards */
+    s = tmn_take(&pool);
+    CHECK(s);
+    {
+        const uint32_t *a, *b, *c;
+        uint64_t cnt, b0, e0;
+        const char *five[] = {"abcde", "+x", "", "xyz", "0123456789"};
+        const uint64_t r0 = s->reruns;                                 /* (a pooled set: it has rerun above) */
+#define REFUSES_PICKS (cnt = 7, a = five_marker, tmn_picks(s, &a, &cnt) == TM_EINVAL && cnt == 0 && a == 0)
+#define REFUSES_GROUPS (cnt = 7, a = b = five_marker, tmn_groups(s, &a, &b, &cnt) == TM_EINVAL && cnt == 0 && a == 0 && b == 0)
+#define REFUSES_DELIVERIES \
+    (cnt = 7, a = b = c = five_marker, tmn_deliveries(s, &a, &b, &c, &cnt) == TM_EINVAL && cnt == 0 && !a && !b && !c)
+        const uint32_t marker_word = 0, *const five_marker = &marker_word;
+        pack(s, 5, five);
+        CHECK(tmn_share_keys(s, H, 5, kc, kt) == TM_OK);
+        CHECK(tmn_route(s, H, 5, 3) == TM_OK && tmn_route_dest(s, 3, &b0, &e0) == 0 && e0 == 5 + 3 + 10);
+        CHECK(tmn_route_dest(s, 4, &b0, &e0) == TM_EINVAL && b0 == 0 && e0 == 0);
+        CHECK(tmn_dispatch(s, H, 5, 3, 1, 0) == TM_OK && tmn_deliveries(s, &a, &b, &c, &cnt) == 0 && cnt > 0);
+        CHECK(REFUSES_PICKS && REFUSES_GROUPS && tmn_direct(s) == 0);
+        CHECK(tmn_publish(s, H, 5, 3, 1, 4) == TM_OK && tmn_picks(s, &a, &cnt) == 0 && cnt == s->picks && cnt > 0);
+        CHECK(tmn_deliveries(s, &a, &b, &c, &cnt) == 0 && REFUSES_GROUPS && tmn_direct(s) == 0);
+        CHECK(tmn_deliver(s, H, 5, 3, 1, 0) == TM_OK && tmn_groups(s, &a, &b, &cnt) == 0 && cnt == s->groups && cnt > 0);
+        CHECK(tmn_deliveries(s, &a, &b, &c, &cnt) == 0 && REFUSES_PICKS && tmn_direct(s) == 0);
+        CHECK(tmn_publish_deliver(s, H, 5, 3, 1, 4) == TM_OK && s->reruns == r0);
+        verify(s, 5, five, 3, 1, kc, kt, 4);
+        CHECK(tmn_direct(s) > 0 && tmn_direct(s) < s->deliveries);
+        /* the match half on the same buffers: unique rows end at the distinct count, not at the next offset */
+        for (uint32_t order = TM_ORDER_TRAVERSAL; order <= TM_ORDER_UNIQUE; order++) {
+            CHECK(tmn_match(s, H, 5, order) == TM_OK);
+            for (uint32_t i = 0; i < 5; i++) {
+                const uint64_t len = i == 1 ? 0 : strlen(five[i]), want = order == TM_ORDER_UNIQUE ? (len + 1) / 2 : len;
+                CHECK(tmn_row(s, 5, order, i, &b0, &e0) == (i == 1 ? TMN_ERR_BADARG : 0) && e0 - b0 == want);
+                for (uint64_t k = 0; k < want; k++) CHECK(tmn_vals(s)[b0 + k] == 1000 * i + k);
+            }
+        }
+        /* tmn_first twice, the second batch with other lengths: the u64 offsets are copied for each */
+        const char *other[] = {"", "q", "+y", "zz"};
+        uint32_t v;
+        CHECK(tmn_first(s, H, 5) == TM_OK && tmn_first_row(s, 0, &v) == 1 && tmn_first_row(s, 1, &v) == 2);
+        CHECK(tmn_first_row(s, 2, &v) == 0 && tmn_first_row(s, 4, &v) == 1 && v == 4000);
+        pack(s, 4, other);
+        CHECK(tmn_first(s, H, 4) == TM_OK && tmn_first_row(s, 0, &v) == 0 && tmn_first_row(s, 1, &v) == 1 && v == 1000);
+        CHECK(tmn_first_row(s, 2, &v) == 2 && tmn_first_row(s, 3, &v) == 1 && v == 3000);
+        /* and back */
+        pack(s, 5, five);
+        CHECK(tmn_publish_deliver(s, H, 5, 3, 1, 4) == TM_OK);
+        verify(s, 5, five, 3, 1, kc, kt, 4);
+        /* refusals: no library call, nothing left to read, whichever of the three was asked */
+        c0 = fake_pd_count(), m0 = fake_pd_moves();
+        const long alloc0 = fake_count(0);
+        for (int k = 0; k < 15; k++) {
+            const uint32_t n = k % 5 == 3 ? 4 : k % 5 == 4 ? 6 : 5;                    /* the keys are for five */
+            const uint32_t nd = k % 5 == 0 ? 0 : k % 5 == 1 ? 65537 : 3, ld = k % 5 == 2 ? 3 : 1;
+            if (k / 5 == 1 && n != 5) continue;                                        /* (tmn_deliver has no keys) */
+            CHECK(tmn_publish_deliver(s, H, 5, 3, 1, 4) == TM_OK);                     /* something to take away */
+            const long before = fake_pd_count() + fake_publish_count() + fake_deliver_count() + fake_dispatch_count() + fake_route_count();
+            const int rc = k / 5 == 0 ? tmn_publish(s, H, n, nd, ld, 4) : k / 5 == 1 ? tmn_deliver(s, H, n, nd, ld, 0)
+                                                                                     : tmn_publish_deliver(s, H, n, nd, ld, 4);
+            CHECK(rc == TM_EINVAL);
+            CHECK(fake_pd_count() + fake_publish_count() + fake_deliver_count() + fake_dispatch_count() + fake_route_count() == before);
+            CHECK(REFUSES_PICKS && REFUSES_GROUPS && REFUSES_DELIVERIES && tmn_direct(s) == 0);
+            CHECK(tmn_route_dest(s, 0, &b0, &e0) == TM_EINVAL && b0 == 0 && e0 == 0);
+        }
+        CHECK(fake_count(0) == alloc0 && s->reruns == r0);
+        CHECK(tmn_publish_deliver(s, H, 5, 3, 1, 4) == TM_OK);
+        verify(s, 5, five, 3, 1, kc, kt, 4);
+        CHECK(tmn_share_keys(s, H, 0, 0, 0) == TM_OK);
+#undef REFUSES_PICKS
+#undef REFUSES_GROUPS
+#undef REFUSES_DELIVERIES
+    }
     tmn_give(&pool, s);
 
     /* 6. every buffer goes with the pool: the members, the group head and the two group buffers too */
