@@ -33,7 +33,10 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_dispatch_batch32", "tm_set_share_slots", "tm_set_share_members", "tm_share_state_set",
            "tm_share_state_get", "tm_share_pick_dev", "tm_publish_batch", "tm_publish_batch32",
            "tm_group_subs_dev", "tm_deliver_batch", "tm_deliver_batch32", "tm_set_member_subs",
-           "tm_group_picks_dev", "tm_publish_deliver_batch", "tm_publish_deliver_batch32")
+           "tm_group_picks_dev", "tm_publish_deliver_batch", "tm_publish_deliver_batch32",
+           "tm_retained_create", "tm_retained_destroy", "tm_retained_put", "tm_retained_delete", "tm_retained_get",
+           "tm_retained_match", "tm_retained_expire", "tm_retained_compact", "tm_retained_stats",
+           "tm_retained_last_error")
 TM_ALLOC_VRAM = 1
 TM_ROUTE_AGGRE = 1          # tm_route_batch_ex / tm_route_batch32_ex: aggre/1 applied to the buckets
 NO_FILTER = 0xFFFFFFFF      # tm_set_route_filters: no filter known (equal to nothing)
@@ -73,6 +76,9 @@ TM_DEBUG_PUBLISH_DELIVER_ONE, TM_DEBUG_PUBLISH_DELIVER_GRID = 45, 46
 GS1_DELIVERIES = 16384
 GP1_DELIVERIES = 8192        # (emqx_amd/csrc/tm_dev.h) merged deliveries, T + K, of tm_publish_deliver_batch32's one workgroup
 MAX_DESTS = 65536           # tm_fanout_dev / tm_route_batch: n_dests is 1 .. MAX_DESTS
+# the retained-message store (emqx_amd/csrc/tm_retain.h): levels kept in columns, rows a block scans
+RT_COLS, RT_TILE = 8, 256
+RT_PUT_REPLACED, RT_PUT_NEW, RT_PUT_INVALID = 0, 1, 2   # tm_retained_put's out_code
 
 
 class NativeUnavailable(RuntimeError):
@@ -100,6 +106,16 @@ class tm_stats_t(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("n_keys", "n_wild_keys", "n_exact_keys", "n_dead_keys",
                                           "n_nodes", "n_edges", "n_words", "device_bytes",
                                           "uploads", "patch_bytes")]
+
+
+class tm_retained_opts(C.Structure):
+    _fields_ = [("initial_rows", C.c_uint32), ("tail_max", C.c_uint32)]
+
+
+class tm_retained_stats_t(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("live_rows", "base_rows", "tail_rows", "dead_rows", "words", "compactions",
+                                          "growths", "match_launches", "no_launch_filters", "device_bytes",
+                                          "rt_cols", "rt_tile")]
 
 
 _lib = None
@@ -185,6 +201,16 @@ def load_library(path: Path | None = None):
                                            vp, vp, vp, vp, u64, vp]),
         "tm_publish_deliver_batch32": (i32, [vp, u64, vp, vp, u32, u32, u32, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u32,
                                              vp, vp, vp, vp, u64, vp]),
+        "tm_retained_create": (i32, [i32, C.POINTER(tm_retained_opts), C.POINTER(vp)]),
+        "tm_retained_destroy": (i32, [vp]),
+        "tm_retained_put": (i32, [vp, u64, vp, vp, vp, vp, vp]),
+        "tm_retained_delete": (i32, [vp, u64, vp, vp, vp]),
+        "tm_retained_get": (i32, [vp, u64, vp, vp, u64, vp, vp]),
+        "tm_retained_match": (i32, [vp, u64, vp, vp, u64, vp, vp, u64, vp]),
+        "tm_retained_expire": (i32, [vp, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(i32)]),
+        "tm_retained_compact": (i32, [vp]),
+        "tm_retained_stats": (i32, [vp, C.POINTER(tm_retained_stats_t)]),
+        "tm_retained_last_error": (C.c_char_p, [vp]),
         "tm_debug_set": (i32, [vp, u32, u64]),
         "tm_debug_get": (i32, [vp, u32, C.POINTER(u64)]),
     }
@@ -1010,3 +1036,108 @@ class Index:
         s = tm_stats_t()
         self._check(self._lib.tm_stats(self._h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in tm_stats_t._fields_}
+
+
+class Retained:
+    """Owning handle of one device-resident retained-message store (tm_retained*,
+    include/tmatch.h "The retained-message store"): stored topic names with a
+    caller-chosen u32 value and an expiry each, looked up by subscription
+    filters (emqx_retainer_mnesia:match_messages/3) on the GPU."""
+
+    def __init__(self, device: int = -1, initial_rows: int = 0, tail_max: int = 0):
+        if not _gpu_present():
+            raise NativeUnavailable("no HIP device visible: the retained store runs on the GPU only")
+        self._lib = load_library()
+        opts = tm_retained_opts(initial_rows, tail_max)
+        h = C.c_void_p()
+        rc = self._lib.tm_retained_create(device, C.byref(opts), C.byref(h))
+        if rc != TM_OK:
+            raise TmError(rc, self._lib.tm_retained_last_error(None).decode())
+        self._h = h
+
+    def _check(self, rc):
+        if rc != TM_OK:
+            cls = DeviceError if rc == TM_EDEVICE else TmError
+            raise cls(rc, self._lib.tm_retained_last_error(self._h).decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.tm_retained_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def put(self, topics, values, expiry_ms=None) -> np.ndarray:
+        """store_retained for a batch -> codes (0 replaced, 1 new, 2 invalid topic: nothing stored)"""
+        blob, offs = pack_strings(topics)
+        return self.put_packed(blob, offs, values, expiry_ms)
+
+    def put_packed(self, blob, offs, values, expiry_ms=None) -> np.ndarray:
+        """put() over topics already packed (pack_strings' form)"""
+        n = len(offs) - 1
+        blob, offs = np.ascontiguousarray(blob, dtype=np.uint8), np.ascontiguousarray(offs, dtype=np.uint64)
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        exp = None if expiry_ms is None else np.ascontiguousarray(expiry_ms, dtype=np.uint64)
+        if len(values) != n or (exp is not None and len(exp) != n):
+            raise ValueError("a value (and an expiry) per topic")
+        code = np.zeros(n, np.uint8)
+        self._check(self._lib.tm_retained_put(self._h, n, _ptr(blob), _ptr(offs), _ptr(values), _ptr(exp), _ptr(code)))
+        return code
+
+    def delete(self, topics) -> np.ndarray:
+        """delete_message for exact topics -> found flags"""
+        blob, offs = pack_strings(topics)
+        found = np.zeros(len(offs) - 1, np.uint8)
+        self._check(self._lib.tm_retained_delete(self._h, len(found), _ptr(blob), _ptr(offs), _ptr(found)))
+        return found.astype(bool)
+
+    def get(self, topics, now_ms: int = 0):
+        """read_message (expiry == 0 or expiry >= now_ms) -> (values, found flags)"""
+        blob, offs = pack_strings(topics)
+        n = len(offs) - 1
+        vals, found = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        self._check(self._lib.tm_retained_get(self._h, n, _ptr(blob), _ptr(offs), now_ms, _ptr(vals), _ptr(found)))
+        return vals, found.astype(bool)
+
+    def match_packed(self, blob, offs, now_ms: int = 0):
+        """tm_retained_match over packed filters -> (offsets[n + 1], values, err[n]); sizes, then fills"""
+        n = len(offs) - 1
+        hit = np.zeros(n + 1, np.uint64)
+        err = np.zeros(n, np.uint8)
+        rc = self._lib.tm_retained_match(self._h, n, _ptr(blob), _ptr(offs), now_ms, _ptr(hit), None, 0, _ptr(err))
+        if rc == TM_ECAP:
+            vals = np.zeros(int(hit[n]), np.uint32)
+            rc = self._lib.tm_retained_match(self._h, n, _ptr(blob), _ptr(offs), now_ms, _ptr(hit), _ptr(vals), len(vals),
+                                             _ptr(err))
+        else:
+            vals = np.zeros(0, np.uint32)
+        self._check(rc)
+        return hit, vals, err
+
+    def match(self, filters, now_ms: int = 0):
+        """match_messages for a batch of filters (expiry == 0 or expiry > now_ms) -> one array of values per filter,
+        in no particular order; an invalid filter ('#' not last) gives an empty one"""
+        blob, offs = pack_strings(filters)
+        hit, vals, _ = self.match_packed(blob, offs, now_ms)
+        return [vals[int(hit[i]):int(hit[i + 1])] for i in range(len(offs) - 1)]
+
+    def expire(self, deadline_ms: int, limit: int = 0):
+        """clear_expired -> (complete, values of the rows deleted)"""
+        st = self.stats()
+        out = np.zeros(max(int(limit) if limit else st["live_rows"], 1), np.uint32)
+        n, complete = C.c_uint64(), C.c_int()
+        self._check(self._lib.tm_retained_expire(self._h, deadline_ms, limit, _ptr(out), len(out), C.byref(n),
+                                                 C.byref(complete)))
+        return bool(complete.value), out[: n.value]
+
+    def compact(self):
+        self._check(self._lib.tm_retained_compact(self._h))
+
+    def stats(self) -> dict:
+        st = tm_retained_stats_t()
+        self._check(self._lib.tm_retained_stats(self._h, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in st._fields_}

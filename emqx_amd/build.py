@@ -31,6 +31,8 @@ AGGRE_SOURCE = "tm_aggre.hip"     # aggre/1 on the fan-out's output (likewise)
 DISPATCH_SOURCE = "tm_dispatch.hip"   # local dispatch: route hits expanded to subscribers (likewise)
 SHARE_SOURCE = "tm_share.hip"         # shared-subscription pick: one member per (message, group) (likewise)
 GROUP_SOURCE = "tm_group.hip"         # deliveries grouped by subscriber: a stable radix sort (likewise)
+RETAIN_SOURCE = "tm_retain.hip"       # the retained-message store's scan and apply kernels (likewise)
+RETAIN_HOST_SOURCE = "tm_retain_host.cpp"   # ... and its host side: a handle of its own (tm_retained)
 
 
 def source_hash() -> str:
@@ -61,8 +63,10 @@ def _run(cmd, cwd=None):
 
 def build_tmatch(force: bool = False) -> Path:
     srcs = [CSRC / "tm_host.cpp", CSRC / "tm_kernels.hip", CSRC / FANOUT_SOURCE, CSRC / AGGRE_SOURCE,
-            CSRC / DISPATCH_SOURCE, CSRC / SHARE_SOURCE, CSRC / GROUP_SOURCE]
-    deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", CSRC / "tm_subs.h", ROOT / "include" / "tmatch.h"]
+            CSRC / DISPATCH_SOURCE, CSRC / SHARE_SOURCE, CSRC / GROUP_SOURCE, CSRC / RETAIN_SOURCE,
+            CSRC / RETAIN_HOST_SOURCE]
+    deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", CSRC / "tm_subs.h", CSRC / "tm_retain.h",
+                   ROOT / "include" / "tmatch.h"]
     if force or _stale(LIB_TMATCH, deps):
         tmp = LIB_TMATCH.with_suffix(".so.tmp")
         _run(["hipcc", "-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-shared",
@@ -82,8 +86,10 @@ def build_variant(name: str, kernel_src: str | None = None, force: bool = False,
     out.parent.mkdir(exist_ok=True)
     kern = Path(kernel_src) if kernel_src else CSRC / "tm_kernels.hip"
     srcs = [Path(host_src) if host_src else CSRC / "tm_host.cpp", kern, CSRC / FANOUT_SOURCE, CSRC / AGGRE_SOURCE,
-            CSRC / DISPATCH_SOURCE, CSRC / SHARE_SOURCE, CSRC / GROUP_SOURCE]
-    deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", CSRC / "tm_subs.h", ROOT / "include" / "tmatch.h"]
+            CSRC / DISPATCH_SOURCE, CSRC / SHARE_SOURCE, CSRC / GROUP_SOURCE, CSRC / RETAIN_SOURCE,
+            CSRC / RETAIN_HOST_SOURCE]
+    deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", CSRC / "tm_subs.h", CSRC / "tm_retain.h",
+                   ROOT / "include" / "tmatch.h"]
     if force or _stale(out, deps):
         _run(["hipcc", "-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-shared", "-Wall",
               "-Wno-unused-function", f"-I{CSRC}", "-o", str(out)] + [str(s) for s in srcs])

@@ -1299,6 +1299,103 @@ int tm_debug_get(tm_index *h, uint32_t key, uint64_t *value);
 /* Last error text of the calling thread (h is ignored; kept for the ABI). */
 const char *tm_last_error(tm_index *h);
 
+/* The retained-message store (ABI minor 24): one subscription filter against
+ * the stored topic names, emqx_retainer:on_session_subscribed ->
+ * emqx_retainer_mnesia:match_messages/3.  A handle of its own, independent of
+ * tm_index: a host dictionary interns level words to ids, the rows are columns
+ * of ids on the device (the first RT_COLS = 8 levels, deeper ones in an
+ * overflow run), rows [0, base) sorted by id sequence and rows
+ * [base, base + tail) recent inserts; past tail_max tail rows the store
+ * compacts (dead rows dropped, tail merged, dictionary ids with no live row
+ * freed).  A stored topic T matches a filter F as emqx_topic:match/2 says
+ * (emqx_topic.erl:80-116): levels split on '/', the empty level an ordinary
+ * word; a filter level is a wildcard only when it is exactly '+' or '#'; a
+ * first level '+' or '#' never matches a topic whose first byte is '$'; a
+ * final '#' matches whatever is left, nothing included; without it the level
+ * counts are equal.  Calls on one store serialise on its mutex; stores are
+ * independent of each other.  A match after a write on the same store sees the
+ * write.  The error text of these calls is tm_retained_last_error's, per
+ * calling thread. */
+typedef struct tm_retained tm_retained;
+typedef struct {
+    uint32_t initial_rows;   /* rows allocated at first (0 = 1024); the arrays double */
+    uint32_t tail_max;       /* tail rows that trigger a compaction (0 = 4096)       */
+} tm_retained_opts;
+typedef struct {
+    uint64_t live_rows, base_rows, tail_rows, dead_rows;
+    uint64_t words;             /* dictionary entries                                   */
+    uint64_t compactions, growths;
+    uint64_t match_launches;    /* tm_retained_match calls that scanned on the device   */
+    uint64_t no_launch_filters; /* filters answered on the host alone                   */
+    uint64_t device_bytes;
+    uint64_t rt_cols, rt_tile;  /* the compiled RT_COLS and RT_TILE                     */
+} tm_retained_stats_t;
+
+/* An empty store on a device (-1: the current one).  opts may be NULL.  (The
+ * reference's create/1, emqx_retainer_mnesia.erl:143-166, makes the tables.) */
+int tm_retained_create(int device, const tm_retained_opts *opts, tm_retained **out);
+/* close/1 (emqx_retainer_mnesia.erl:205) keeps the tables; this frees the store
+ * and its device memory.  TM_EINVAL for a null handle (as tm_destroy). */
+int tm_retained_destroy(tm_retained *r);
+
+/* store_retained (emqx_retainer_mnesia.erl:207-224, 358-384): insert or replace
+ * n topics in order, topic i = topic_bytes[topic_offsets[i] .. topic_offsets[i+1]).
+ * values[i] is the caller's (any u32), expiry_ms[i] = 0 never expires
+ * (expiry_ms may be NULL: all 0).  out_code[i] (may be NULL): 0 replaced, 1 new,
+ * 2 invalid topic (empty, a level exactly '+' or '#', more than 65536 levels),
+ * which stores nothing.  One staged batch, one kernel (k_ret_apply). */
+int tm_retained_put(tm_retained *r, uint64_t n, const uint8_t *topic_bytes, const uint64_t *topic_offsets,
+                    const uint32_t *values, const uint64_t *expiry_ms, uint8_t *out_code);
+
+/* delete_message for exact topics (emqx_retainer_mnesia.erl:271-275, 477-494):
+ * out_found[i] (may be NULL) = 1 if the topic was stored.  A wildcard delete is
+ * a match with now_ms = 0 and a delete of each hit (:277-282), the caller's. */
+int tm_retained_delete(tm_retained *r, uint64_t n, const uint8_t *topic_bytes, const uint64_t *topic_offsets,
+                       uint8_t *out_found);
+
+/* read_message (emqx_retainer_mnesia.erl:285-286, 502-514): exact topics, host
+ * side only.  out_found[i] = 1 and out_value[i] set iff the topic is stored and
+ * expiry == 0 || expiry >= now_ms (the read path's >=, :510; the match path
+ * below uses >). */
+int tm_retained_get(tm_retained *r, uint64_t n, const uint8_t *topic_bytes, const uint64_t *topic_offsets,
+                    uint64_t now_ms, uint32_t *out_value, uint8_t *out_found);
+
+/* match_messages for n filters (emqx_retainer_mnesia.erl:288-304, 409-475;
+ * emqx_topic.erl:80-116).  A row is visible iff expiry == 0 || expiry > now_ms
+ * (:464-466, :518), so now_ms = 0 shows every row (:277).  The result is CSR:
+ * the values of filter i's rows are out_values[out_hit_offsets[i] ..
+ * out_hit_offsets[i+1]), in no particular order and without duplicates.
+ * out_hit_offsets[n+1] always holds the true counts; TM_ECAP if
+ * out_hit_offsets[n] > cap (out_values is then unspecified, and nothing is
+ * written at or past cap); out_values may be NULL with cap 0 to size a
+ * buffer.  out_err[i] (may be NULL) = 2: not a valid filter ('#' not last),
+ * its list is empty; else 0. */
+int tm_retained_match(tm_retained *r, uint64_t n, const uint8_t *filter_bytes, const uint64_t *filter_offsets,
+                      uint64_t now_ms, uint64_t *out_hit_offsets, uint32_t *out_values, uint64_t cap,
+                      uint8_t *out_err);
+
+/* clear_expired with msg_expiry_interval_override disabled
+ * (emqx_retainer_mnesia.erl:226-269, :231-234): deletes rows with
+ * expiry != 0 && expiry < deadline_ms, at most `limit` of them (0 = all) and,
+ * where out_values is not NULL, at most cap; their values go to out_values,
+ * their number to *out_n.  *out_complete is the reference's Complete: 1 iff the
+ * scan reached the table's end before `limit` rows were taken (:266-267: with
+ * exactly `limit` expired rows it is 0, and the next call answers 0 rows,
+ * complete).  Host side. */
+int tm_retained_expire(tm_retained *r, uint64_t deadline_ms, uint64_t limit, uint32_t *out_values,
+                       uint64_t cap, uint64_t *out_n, int *out_complete);
+
+/* Compact now: what passing tail_max does (no reference counterpart: mnesia
+ * keeps its own tables). */
+int tm_retained_compact(tm_retained *r);
+
+/* table_size (emqx_retainer_mnesia.erl:541-542) is live_rows; the rest is the
+ * store's own bookkeeping. */
+int tm_retained_stats(tm_retained *r, tm_retained_stats_t *out);
+
+/* Last error text of the calling thread from a tm_retained_* call. */
+const char *tm_retained_last_error(tm_retained *r);
+
 /* ABI version: (major << 16) | minor. */
 uint32_t tm_abi_version(void);
 
