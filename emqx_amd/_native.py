@@ -36,7 +36,7 @@ EXPORTS = ("tm_create", "tm_destroy", "tm_apply_deltas", "tm_sync", "tm_match_ba
            "tm_group_picks_dev", "tm_publish_deliver_batch", "tm_publish_deliver_batch32",
            "tm_retained_create", "tm_retained_destroy", "tm_retained_put", "tm_retained_delete", "tm_retained_get",
            "tm_retained_match", "tm_retained_expire", "tm_retained_compact", "tm_retained_stats",
-           "tm_retained_last_error")
+           "tm_retained_last_error", "tm_retained_match_page", "tm_retained_pin", "tm_retained_unpin")
 TM_ALLOC_VRAM = 1
 TM_ROUTE_AGGRE = 1          # tm_route_batch_ex / tm_route_batch32_ex: aggre/1 applied to the buckets
 NO_FILTER = 0xFFFFFFFF      # tm_set_route_filters: no filter known (equal to nothing)
@@ -79,6 +79,8 @@ MAX_DESTS = 65536           # tm_fanout_dev / tm_route_batch: n_dests is 1 .. MA
 # the retained-message store (emqx_amd/csrc/tm_retain.h): levels kept in columns, rows a block scans
 RT_COLS, RT_TILE = 8, 256
 RT_PUT_REPLACED, RT_PUT_NEW, RT_PUT_INVALID = 0, 1, 2   # tm_retained_put's out_code
+# match cursors (tm_retained_match_page): open, the end, and out_err's "cursor of another epoch"
+TM_RET_CURSOR_BEGIN, TM_RET_CURSOR_DONE, TM_RET_ESTALE = 0, 0xFFFFFFFFFFFFFFFF, 3
 
 
 class NativeUnavailable(RuntimeError):
@@ -211,6 +213,9 @@ def load_library(path: Path | None = None):
         "tm_retained_compact": (i32, [vp]),
         "tm_retained_stats": (i32, [vp, C.POINTER(tm_retained_stats_t)]),
         "tm_retained_last_error": (C.c_char_p, [vp]),
+        "tm_retained_match_page": (i32, [vp, u64, vp, vp, u64, vp, u32, u64, vp, vp, u64, vp, vp]),
+        "tm_retained_pin": (i32, [vp]),
+        "tm_retained_unpin": (i32, [vp]),
         "tm_debug_set": (i32, [vp, u32, u64]),
         "tm_debug_get": (i32, [vp, u32, C.POINTER(u64)]),
     }
@@ -1124,6 +1129,41 @@ class Retained:
         blob, offs = pack_strings(filters)
         hit, vals, _ = self.match_packed(blob, offs, now_ms)
         return [vals[int(hit[i]):int(hit[i + 1])] for i in range(len(offs) - 1)]
+
+    def match_page_packed(self, blob, offs, now_ms: int = 0, cursors=None, limit: int = 1000, scan_rows: int = 0):
+        """tm_retained_match_page over packed filters -> (offsets[n + 1], values, cursors[n], err[n]): one buffer of
+        n * limit values, one call"""
+        n = len(offs) - 1
+        if limit < 1:
+            raise ValueError("a page takes at least one value")
+        cur = None if cursors is None else np.ascontiguousarray(cursors, dtype=np.uint64)
+        if cur is not None and len(cur) != n:
+            raise ValueError("a cursor per filter")
+        hit = np.zeros(n + 1, np.uint64)
+        vals = np.empty(n * limit, np.uint32)
+        out_cur = np.zeros(n, np.uint64)
+        err = np.zeros(n, np.uint8)
+        self._check(self._lib.tm_retained_match_page(self._h, n, _ptr(blob), _ptr(offs), now_ms, _ptr(cur), limit, scan_rows,
+                                                     _ptr(hit), _ptr(vals), len(vals), _ptr(out_cur), _ptr(err)))
+        return hit, vals[: int(hit[n])], out_cur, err
+
+    def match_page(self, filters, now_ms: int = 0, cursors=None, limit: int = 1000, scan_rows: int = 0):
+        """One page of match_messages/3 for each filter (emqx_retainer_mnesia.erl:288-304): at most `limit` values
+        each, in scan order, from its cursor on (None: all from the start) -> (lists, cursors, err).  A cursor of
+        TM_RET_CURSOR_DONE is the end; err[i] == TM_RET_ESTALE: the store compacted since the cursor was handed out
+        (pin() prevents that), start again; scan_rows bounds the rows a filter examines in this call (a short page
+        with a live cursor is then legal)."""
+        blob, offs = pack_strings(filters)
+        hit, vals, cur, err = self.match_page_packed(blob, offs, now_ms, cursors, limit, scan_rows)
+        return [vals[int(hit[i]):int(hit[i + 1])] for i in range(len(offs) - 1)], cur, err
+
+    def pin(self):
+        """a holder of open cursors more: the store does not compact until every holder has unpinned"""
+        self._check(self._lib.tm_retained_pin(self._h))
+
+    def unpin(self):
+        """... and one fewer; the last one compacts if a compaction is due or the tail is past tail_max"""
+        self._check(self._lib.tm_retained_unpin(self._h))
 
     def expire(self, deadline_ms: int, limit: int = 0):
         """clear_expired -> (complete, values of the rows deleted)"""

@@ -33,6 +33,9 @@ SHARE_SOURCE = "tm_share.hip"         # shared-subscription pick: one member per
 GROUP_SOURCE = "tm_group.hip"         # deliveries grouped by subscriber: a stable radix sort (likewise)
 RETAIN_SOURCE = "tm_retain.hip"       # the retained-message store's scan and apply kernels (likewise)
 RETAIN_HOST_SOURCE = "tm_retain_host.cpp"   # ... and its host side: a handle of its own (tm_retained)
+RETAIN_PAGE_SOURCE = "tm_retain_page.hip"             # match cursors: a page of each filter's hits in scan order
+RETAIN_PAGE_HOST_SOURCE = "tm_retain_page_host.cpp"   # ... tm_retained_match_page, pin and unpin
+RETAIN_HEADERS = ("tm_retain.h", "tm_retain_dev.h", "tm_retain_store.h", "tm_retain_page.h")
 
 
 def source_hash() -> str:
@@ -64,9 +67,9 @@ def _run(cmd, cwd=None):
 def build_tmatch(force: bool = False) -> Path:
     srcs = [CSRC / "tm_host.cpp", CSRC / "tm_kernels.hip", CSRC / FANOUT_SOURCE, CSRC / AGGRE_SOURCE,
             CSRC / DISPATCH_SOURCE, CSRC / SHARE_SOURCE, CSRC / GROUP_SOURCE, CSRC / RETAIN_SOURCE,
-            CSRC / RETAIN_HOST_SOURCE]
-    deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", CSRC / "tm_subs.h", CSRC / "tm_retain.h",
-                   ROOT / "include" / "tmatch.h"]
+            CSRC / RETAIN_HOST_SOURCE, CSRC / RETAIN_PAGE_SOURCE, CSRC / RETAIN_PAGE_HOST_SOURCE]
+    deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", CSRC / "tm_subs.h",
+                   *(CSRC / h for h in RETAIN_HEADERS), ROOT / "include" / "tmatch.h"]
     if force or _stale(LIB_TMATCH, deps):
         tmp = LIB_TMATCH.with_suffix(".so.tmp")
         _run(["hipcc", "-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-shared",
@@ -87,9 +90,9 @@ def build_variant(name: str, kernel_src: str | None = None, force: bool = False,
     kern = Path(kernel_src) if kernel_src else CSRC / "tm_kernels.hip"
     srcs = [Path(host_src) if host_src else CSRC / "tm_host.cpp", kern, CSRC / FANOUT_SOURCE, CSRC / AGGRE_SOURCE,
             CSRC / DISPATCH_SOURCE, CSRC / SHARE_SOURCE, CSRC / GROUP_SOURCE, CSRC / RETAIN_SOURCE,
-            CSRC / RETAIN_HOST_SOURCE]
-    deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", CSRC / "tm_subs.h", CSRC / "tm_retain.h",
-                   ROOT / "include" / "tmatch.h"]
+            CSRC / RETAIN_HOST_SOURCE, CSRC / RETAIN_PAGE_SOURCE, CSRC / RETAIN_PAGE_HOST_SOURCE]
+    deps = srcs + [CSRC / "tm_layout.h", CSRC / "tm_dev.h", CSRC / "tm_scan.h", CSRC / "tm_subs.h",
+                   *(CSRC / h for h in RETAIN_HEADERS), ROOT / "include" / "tmatch.h"]
     if force or _stale(out, deps):
         _run(["hipcc", "-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-shared", "-Wall",
               "-Wno-unused-function", f"-I{CSRC}", "-o", str(out)] + [str(s) for s in srcs])

@@ -2187,7 +2187,7 @@ struct HostBatch {
 
 extern "C" {
 
-uint32_t tm_abi_version(void) { return (1u << 16) | 24u; }
+uint32_t tm_abi_version(void) { return (1u << 16) | 25u; }
 
 const char *tm_last_error(tm_index *) { return g_last_error.c_str(); }
 

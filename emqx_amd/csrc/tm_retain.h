@@ -1,6 +1,6 @@
 // tm_retain.h -- the retained-message store's device layout and launchers
 // (tm_retain.hip, tm_retain_host.cpp; tests/retain_cpu has the launchers in
-// plain C++).  Independent of the topic index (tm_dev.h): one filter against
+// plain C++; the paged lookup's descriptor and launchers: tm_retain_page.h).  Independent of the topic index (tm_dev.h): one filter against
 // many stored topic names, emqx_retainer_mnesia:match_messages/3.
 //
 // Rows are a column store.  A row's level words are u32 ids of an exact host

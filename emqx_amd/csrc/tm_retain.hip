@@ -15,33 +15,12 @@
 #include <hip/hip_runtime.h>
 
 #include "tm_retain.h"
+#include "tm_retain_dev.h"   // ret_row_matches, shared with tm_retain_page.hip
 
 namespace tmx {
 namespace {
 
 constexpr uint32_t SCAN_THREADS = 256;
-
-// does row `row` match filter q (levels skip .. nlev-1 still to test)?
-__device__ __forceinline__ bool ret_row_matches(const RetView &v, const RetQ &q, const uint32_t *__restrict__ ids,
-                                                uint32_t skip, uint64_t row, uint64_t now) {
-    const uint32_t meta = v.meta[row];
-    const uint32_t nlev = meta & RT_NLEV_MASK;
-    bool ok = (meta & RT_LIVE) != 0;
-    ok = ok && !((q.flags & RQ_WILD_FIRST) && (meta & RT_DOLLAR));
-    ok = ok && ((q.flags & RQ_HASH) ? nlev >= q.nlev : nlev == q.nlev);
-    // the level loop is uniform over the block; a lane that is out loads nothing more
-    for (uint32_t l = skip; l < q.nlev; ++l) {
-        const uint32_t want = ids[q.ids_off + l];
-        if (want == RT_PLUS) continue;
-        if (ok) {
-            // nlev >= q.nlev > l: the row has this level (in ovf when l >= RT_COLS, and then it is flagged)
-            const uint32_t have = l < RT_COLS ? v.cols[(uint64_t)l * v.stride + row] : v.ovf[v.ovf_off[row] + (l - RT_COLS)];
-            ok = have == want;
-        }
-    }
-    if (ok && (meta & RT_HAS_EXPIRY)) ok = v.expiry[row] > now;   // (:464-466; now == 0 shows every row)
-    return ok;
-}
 
 template <bool EMIT>
 __global__ __launch_bounds__(RT_TILE) void k_ret_rows(RetView v, const RetQ *__restrict__ qs, uint32_t nq,

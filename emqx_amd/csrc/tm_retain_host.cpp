@@ -21,80 +21,10 @@
 
 #include "../../include/tmatch.h"
 #include "tm_retain.h"
+#include "tm_retain_store.h"   // struct tm_retained and the helpers tm_retain_page_host.cpp shares
 
 using namespace tmx;
-
-namespace {
-
-thread_local std::string g_ret_error;
-
-int fail(int code, const std::string &msg) {
-    g_ret_error = msg;
-    return code;
-}
-
-#define RT_HIP(x)                                                                          \
-    do {                                                                                   \
-        hipError_t e_ = (x);                                                               \
-        if (e_ != hipSuccess) return fail(TM_EDEVICE, std::string(#x ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-struct DBuf {   // a device buffer that only grows
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
-struct Level {
-    const uint8_t *p;
-    size_t n;
-};
-
-void split_levels(const uint8_t *p, size_t n, std::vector<Level> &out) {
-    out.clear();
-    size_t b = 0;
-    for (size_t i = 0; i <= n; ++i)
-        if (i == n || p[i] == '/') {
-            out.push_back({p + b, i - b});
-            b = i + 1;
-        }
-}
-
-bool is_word(const Level &l, char c) { return l.n == 1 && l.p[0] == (uint8_t)c; }
-
-}  // namespace
-
-struct tm_retained {
-    std::mutex mu;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    uint32_t tail_max = 4096;
-
-    // the dictionary: exact (keyed by the word's bytes), counted by live rows
-    std::unordered_map<std::string, uint32_t> dict;
-    std::vector<uint32_t> refc;
-    std::vector<uint32_t> free_ids;
-
-    // the mirror, in the device's row order
-    std::vector<uint32_t> h_ids;      // every row's level ids, row-major
-    std::vector<uint64_t> h_off;      // rows + 1
-    std::vector<uint32_t> h_meta, h_val;
-    std::vector<uint64_t> h_exp, h_ovf;
-    uint64_t base = 0, tail = 0, live = 0, ovf_used = 0;
-    std::unordered_map<std::string, uint32_t> tail_rows;   // id sequence (bytes) -> row, tail rows only
-
-    // the device
-    RetView v{};
-    DBuf d_ops, d_words, d_q, d_ids, d_tps, d_counts, d_offs, d_cursor, d_out;
-    std::vector<RetOp> ops;
-    std::vector<uint32_t> words;
-    std::unordered_map<uint32_t, uint32_t> op_of_row;
-
-    uint64_t compactions = 0, growths = 0, launches = 0, no_launch = 0;
-
-    uint64_t rows() const { return base + tail; }
-    const uint32_t *ids_of(uint64_t r) const { return h_ids.data() + h_off[r]; }
-    uint32_t nlev_of(uint64_t r) const { return (uint32_t)(h_off[r + 1] - h_off[r]); }
-};
+using namespace tmx_ret;
 
 namespace {
 
@@ -107,31 +37,6 @@ int cmp_seq(const tm_retained *s, uint64_t r, const uint32_t *ids, uint32_t n) {
     return m < n ? -1 : m > n ? 1 : 0;
 }
 
-// row r against the prefix (ids, p): 0 when the row starts with it
-int cmp_prefix(const tm_retained *s, uint64_t r, const uint32_t *ids, uint32_t p) {
-    const uint32_t *a = s->ids_of(r);
-    const uint32_t m = s->nlev_of(r), k = std::min(m, p);
-    for (uint32_t i = 0; i < k; ++i)
-        if (a[i] != ids[i]) return a[i] < ids[i] ? -1 : 1;
-    return m < p ? -1 : 0;
-}
-
-// the base rows [lo, hi) that start with (ids, p)
-void prefix_range(const tm_retained *s, const uint32_t *ids, uint32_t p, uint64_t &lo, uint64_t &hi) {
-    uint64_t a = 0, b = s->base;
-    while (a < b) {
-        const uint64_t m = a + (b - a) / 2;
-        if (cmp_prefix(s, m, ids, p) < 0) a = m + 1; else b = m;
-    }
-    lo = a;
-    b = s->base;
-    while (a < b) {
-        const uint64_t m = a + (b - a) / 2;
-        if (cmp_prefix(s, m, ids, p) <= 0) a = m + 1; else b = m;
-    }
-    hi = a;
-}
-
 std::string seq_key(const uint32_t *ids, uint32_t n) { return std::string(reinterpret_cast<const char *>(ids), (size_t)n * 4); }
 
 // the row that holds this id sequence, live or dead (-1: none)
@@ -141,18 +46,6 @@ int64_t find_row(const tm_retained *s, const uint32_t *ids, uint32_t n) {
     if (lo < hi && s->nlev_of(lo) == n) return (int64_t)lo;   // a proper prefix sorts first
     auto it = s->tail_rows.find(seq_key(ids, n));
     return it == s->tail_rows.end() ? -1 : (int64_t)it->second;
-}
-
-// the ids of known words; false when a word is not in the dictionary
-bool lookup_ids(const tm_retained *s, const std::vector<Level> &lv, std::vector<uint32_t> &ids, std::string &tmp) {
-    ids.clear();
-    for (const Level &l : lv) {
-        tmp.assign(reinterpret_cast<const char *>(l.p), l.n);
-        auto it = s->dict.find(tmp);
-        if (it == s->dict.end()) return false;
-        ids.push_back(it->second);
-    }
-    return true;
 }
 
 uint32_t intern(tm_retained *s, const std::string &w) {
@@ -169,23 +62,6 @@ uint32_t intern(tm_retained *s, const std::string &w) {
     s->refc[id] = 0;
     s->dict.emplace(w, id);
     return id;
-}
-
-int dev_reserve(DBuf &b, size_t bytes) {
-    if (bytes <= b.bytes) return TM_OK;
-    size_t want = std::max(bytes, b.bytes * 2);
-    if (b.p) RT_HIP(hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-    if (hipMalloc(&b.p, want) != hipSuccess) return fail(TM_ENOMEM, "tm_retained: no device memory for a batch buffer");
-    b.bytes = want;
-    return TM_OK;
-}
-
-void dev_release(DBuf &b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
 }
 
 void free_view(tm_retained *s) {
@@ -251,8 +127,10 @@ int upload_all(tm_retained *s, uint64_t cap, uint64_t ovf_cap) {
     return TM_OK;
 }
 
+}  // namespace
+
 // the staged writes to the device: two copies and one kernel on the store's stream
-int flush(tm_retained *s) {
+int tmx_ret::flush(tm_retained *s) {
     s->v.base = s->base;
     s->v.tail = s->tail;
     if (s->ops.empty()) return TM_OK;
@@ -270,6 +148,8 @@ int flush(tm_retained *s) {
     s->op_of_row.clear();
     return TM_OK;
 }
+
+namespace {
 
 // row r's meta, value and expiry have changed in the mirror
 void stage_set(tm_retained *s, uint32_t r) {
@@ -296,8 +176,10 @@ void kill_row(tm_retained *s, uint32_t r) {
     stage_set(s, r);
 }
 
+}  // namespace
+
 // dead rows dropped, the tail merged into the sorted base, unused dictionary ids freed, everything uploaded
-int compact(tm_retained *s) {
+int tmx_ret::compact(tm_retained *s) {
     const uint64_t n = s->rows();
     std::vector<uint32_t> order;   // live tail rows, sorted by id sequence
     for (uint64_t r = s->base; r < n; ++r)
@@ -345,11 +227,15 @@ int compact(tm_retained *s) {
         }
     }
     s->compactions++;
+    s->compact_due = false;
     return upload_all(s, s->v.stride, s->v.ovf_cap);
 }
 
-// after a batch of writes: past tail_max the store compacts, else the staged writes go out
-int settle(tm_retained *s) { return s->tail > s->tail_max ? compact(s) : flush(s); }
+namespace {
+
+// after a batch of writes: past tail_max the store compacts, unless a match cursor has pinned it (row indices
+// then stay put, and the unpin that brings the count to 0 compacts); else the staged writes go out
+int settle(tm_retained *s) { return s->tail > s->tail_max && s->pins == 0 ? compact(s) : flush(s); }
 
 }  // namespace
 
@@ -395,6 +281,7 @@ int tm_retained_destroy(tm_retained *s) {
     free_view(s);
     for (DBuf *b : {&s->d_ops, &s->d_words, &s->d_q, &s->d_ids, &s->d_tps, &s->d_counts, &s->d_offs, &s->d_cursor, &s->d_out})
         dev_release(*b);
+    for (DBuf &b : s->d_page) dev_release(b);
     delete s;
     return TM_OK;
 }
@@ -670,6 +557,10 @@ int tm_retained_compact(tm_retained *s) {
     if (!s) return fail(TM_EINVAL, "tm_retained_compact: null handle");
     std::lock_guard<std::mutex> g(s->mu);
     RT_HIP(hipSetDevice(s->device));
+    if (s->pins) {   // pinned: the compaction becomes due (tm_retained_unpin)
+        s->compact_due = true;
+        return TM_OK;
+    }
     return compact(s);
 }
 
@@ -688,6 +579,7 @@ int tm_retained_stats(tm_retained *s, tm_retained_stats_t *out) {
     uint64_t bytes = view_bytes(s->v);
     for (const DBuf *b : {&s->d_ops, &s->d_words, &s->d_q, &s->d_ids, &s->d_tps, &s->d_counts, &s->d_offs, &s->d_cursor, &s->d_out})
         bytes += b->bytes;
+    for (const DBuf &b : s->d_page) bytes += b.bytes;
     out->device_bytes = bytes;
     out->rt_cols = RT_COLS;
     out->rt_tile = RT_TILE;

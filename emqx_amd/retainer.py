@@ -14,13 +14,22 @@ Callback by callback (emqx_retainer_mnesia.erl):
   looked up with ``now = 0`` so that expired rows go too (:277);
 * ``read_message``    :285-286, :502-514 -- exact, ``expiry == 0 or expiry >= now``;
 * ``match_messages``  :288-304, :409-475 -- ``expiry == 0 or expiry > now``;
+  with ``batch_read_number`` set, ``match_messages_cursor`` is ``match_messages/3``
+  with its cursor (:288-304), ``delete_cursor`` ends one early, and ``dispatch``
+  restates the dispatcher's loop over it (emqx_retainer_dispatcher.erl:248-301)
+  without the limiter;
 * ``clear_expired``   :226-269 -- ``(complete, n)``;
 * ``page_read``       :309-332 -- sorted by timestamp as ``compare_message`` does;
 * ``size``, ``clean`` :334-340.
 
 Not built: ``msg_expiry_interval_override`` (:235-250); clear_expired is the
-``disabled`` branch (:231-234).  Cursors (``match_messages/3`` with a batch
-read number) are not mirrored either: a lookup returns its whole list.
+``disabled`` branch (:231-234); the dispatcher's limiter.
+
+A cursor pins the store while it is open (rows then keep their places: no
+compaction), so every cursor is either drained to the end or handed to
+``delete_cursor``, as the dispatcher does.  Rows written while a cursor is open
+are seen if they land at or after it and not otherwise; the reference's ets
+stream is no stronger.
 """
 from __future__ import annotations
 
@@ -54,17 +63,39 @@ def _now_ms() -> int:
     return int(time.time() * 1000)
 
 
+CURSOR_BEGIN, CURSOR_DONE, ERR_STALE = 0, 0xFFFFFFFFFFFFFFFF, 3   # tm_retained_match_page's (include/tmatch.h)
+
+
+class StaleCursor(RuntimeError):
+    """The store compacted after the cursor was handed out (only a cursor whose pin was given up can see this):
+    its rows have moved.  The caller decides whether to start again."""
+
+
+class Cursor:
+    """An open match_messages/3 stream: the device cursor, the `now` of the first call (the reference captures
+    Now when it builds the stream, :290-292) and whether it still holds a pin on the store."""
+    __slots__ = ("flt", "pos", "now", "pinned")
+
+    def __init__(self, flt: bytes, now: int):
+        self.flt, self.pos, self.now, self.pinned = flt, CURSOR_BEGIN, now, False
+
+
 class Retainer:
     """store: a factory of stores with the interface of ``_native.Retained`` (put, delete, get, match, expire,
     stats, close); the default makes one on the current device with `store_opts`."""
 
-    def __init__(self, store=None, max_retained_messages: int = 0, **store_opts):
+    def __init__(self, store=None, max_retained_messages: int = 0, batch_read_number: int | None = None,
+                 scan_rows: int = 0, **store_opts):
         if store is None:
             from . import _native
             store = lambda: _native.Retained(**store_opts)
         self._factory = store
         self._store = store()
         self.max_retained_messages = max_retained_messages
+        # rows a cursor read returns (None: all_remaining, the whole list at once, :296-297); rows a device call
+        # examines per filter at most (0: no bound)
+        self.batch_read_number = batch_read_number
+        self.scan_rows = scan_rows
         self._slot = {}      # topic -> value slot
         self._rows = {}      # value slot -> (topic, msg, expiry_time, timestamp)
         self._free = []
@@ -121,6 +152,92 @@ class Retainer:
 
     def match_messages(self, flt: bytes, now: int | None = None) -> list:
         return self.match_messages_batch([flt], now)[0]
+
+    # ---- match_messages/3 with its cursor
+    def _release(self, cursor: Cursor) -> None:
+        if cursor.pinned:
+            cursor.pinned = False
+            self._store.unpin()
+
+    def match_messages_batch_cursor(self, filters, cursors=None, now: int | None = None):
+        """One read of batch_read_number rows for each of many subscribers, each at its own position, in one
+        device call per round -> (lists of messages, cursors); a cursor is None once its stream has ended.
+        cursors None opens a stream for every filter, with `now`; else it is what the previous call returned, and a
+        place that holds None stays ended: ([], None), as match_next(_, _, undefined) gives (:288-289)."""
+        n = len(filters)
+        if self.batch_read_number is None:   # all_remaining: no cursor comes back (:296-297)
+            if cursors is not None:   # ... so what comes in is ended
+                return [[] for _ in range(n)], [None] * n
+            return self.match_messages_batch(filters, now), [None] * n
+        now = _now_ms() if now is None else now
+        if cursors is None:
+            curs = [Cursor(bytes(f), now) for f in filters]
+        else:
+            curs = [Cursor(bytes(f), now) if c is None else c for f, c in zip(filters, cursors)]
+            for c, given in zip(curs, cursors):
+                if given is None:
+                    c.pos = CURSOR_DONE
+        want = self.batch_read_number
+        out = [[] for _ in range(n)]
+        todo = [i for i in range(n) if curs[i].pos != CURSOR_DONE]
+        try:
+            while todo:
+                # one `now` and one limit per device call: those that opened together and lack the same number of
+                # rows go out together (all of them, when they advance in step)
+                key = lambda i: (curs[i].now, want - len(out[i]))
+                group = [i for i in todo if key(i) == key(todo[0])]
+                limit = want - len(out[group[0]])
+                lists, pos, err = self._store.match_page([curs[i].flt for i in group], curs[group[0]].now,
+                                                         [curs[i].pos for i in group], limit, self.scan_rows)
+                for k, i in enumerate(group):
+                    c = curs[i]
+                    if int(err[k]) == ERR_STALE:
+                        raise StaleCursor(f"the store compacted under the cursor of {c.flt!r}")
+                    out[i].extend(self._rows[int(v)][1] for v in lists[k])
+                    c.pos = int(pos[k])
+                    if c.pos == CURSOR_DONE:
+                        self._release(c)
+                    elif not c.pinned:      # it opened with rows left: rows keep their places until it ends
+                        self._store.pin()
+                        c.pinned = True
+                # with scan_rows set a page may be short and its cursor live: call again
+                rest = [i for i in todo if i not in group]
+                todo = rest + [i for i in group if curs[i].pos != CURSOR_DONE and len(out[i]) < want]
+        except BaseException:
+            for c in curs:
+                self._release(c)
+            raise
+        return out, [None if c.pos == CURSOR_DONE else c for c in curs]
+
+    def match_messages_cursor(self, flt: bytes, cursor: Cursor | None = None, now: int | None = None):
+        """match_messages/3 (:288-304) -> (messages, cursor or None).  cursor None opens the stream, with Now fixed
+        for all of its reads; a returned cursor of None is the reference's `undefined`.  When exactly
+        batch_read_number rows were left the cursor stays open and the next read is ([], None), as
+        emqx_utils_stream:consume/2 makes it (:298-304)."""
+        out, curs = self.match_messages_batch_cursor([flt], None if cursor is None else [cursor], now)
+        return out[0], curs[0]
+
+    def delete_cursor(self, cursor: Cursor | None) -> None:
+        """delete_cursor/2 (:306-307): gives up the pin of a cursor that is still open"""
+        if cursor is not None:
+            self._release(cursor)
+            cursor.pos = CURSOR_DONE
+
+    def dispatch(self, flt: bytes, deliver, now: int | None = None) -> None:
+        """emqx_retainer_dispatcher's loop (emqx_retainer_dispatcher.erl:248-301) without the limiter: read a page,
+        hand it to deliver(messages), stop when that returns false or the stream ends; the cursor is always
+        deleted."""
+        cursor = None
+        try:
+            msgs, cursor = self.match_messages_cursor(flt, None, now)
+            while msgs:                                   # dispatch_with_cursor(_, [], Cursor, ..) ends (:271-273)
+                if deliver(msgs) is False:                # {drop, _} and no_receiver (:279-285)
+                    return
+                if cursor is None:                        # match_next(_, _, undefined) -> {ok, [], undefined} (:288-289)
+                    return
+                msgs, cursor = self.match_messages_cursor(flt, cursor)
+        finally:
+            self.delete_cursor(cursor)
 
     def clear_expired(self, deadline: int, limit: int | None = None):
         """-> (complete, n cleared); limit None is the reference's `all`"""

@@ -1386,12 +1386,80 @@ int tm_retained_expire(tm_retained *r, uint64_t deadline_ms, uint64_t limit, uin
                        uint64_t cap, uint64_t *out_n, int *out_complete);
 
 /* Compact now: what passing tail_max does (no reference counterpart: mnesia
- * keeps its own tables). */
+ * keeps its own tables).  Under a pin (tm_retained_pin) it is deferred. */
 int tm_retained_compact(tm_retained *r);
 
 /* table_size (emqx_retainer_mnesia.erl:541-542) is live_rows; the rest is the
  * store's own bookkeeping. */
 int tm_retained_stats(tm_retained *r, tm_retained_stats_t *out);
+
+/* Match cursors (ABI minor 25): match_messages/3 as the reference uses it.
+ * match_messages(State, Topic, undefined) opens a stream, every later call
+ * consumes batch_read_number rows of it (emqx_retainer_mnesia.erl:288-304), and
+ * the dispatcher loops over the cursor and ends with delete_cursor
+ * (emqx_retainer_dispatcher.erl:248-301).  tm_retained_match is the
+ * all_remaining form; tm_retained_match_page returns one bounded page per
+ * filter, each filter at its own position.
+ *
+ * Scan order: a filter's rows are visited first in the base range of its
+ * literal prefix by ascending row index, then in the tail by ascending row
+ * index, and its values come out in that order (tm_retained_match promises no
+ * order).  A cursor is opaque: TM_RET_CURSOR_BEGIN opens, TM_RET_CURSOR_DONE is
+ * the end; any other value names the store's epoch (compactions + 1, 24 bits)
+ * and the next row to visit (40 bits).  A cursor belongs to the store, not to
+ * the filter: handed to another filter it starts at that filter's first row at
+ * or after it (below its base range: the range's start; past it: the tail). */
+#define TM_RET_CURSOR_BEGIN 0ull
+#define TM_RET_CURSOR_DONE  0xFFFFFFFFFFFFFFFFull
+#define TM_RET_ESTALE 3      /* out_err[i]: the cursor is of another epoch */
+
+/* One page for each of n filters (emqx_retainer_mnesia.erl:288-304;
+ * emqx_utils_stream:consume/2 as :298-304 uses it).  The filter rules, the
+ * visibility rule (expiry == 0 || expiry > now_ms), out_err[i] == 2 and the
+ * TM_ECAP behaviour are tm_retained_match's: out_hit_offsets[n+1] always holds
+ * the true counts, and nothing is written at or past cap.  A filter takes at
+ * most `limit` (>= 1) values, so out_hit_offsets[n] <= n * limit and a caller
+ * that passes cap = n * limit never sees TM_ECAP: one call, one buffer.
+ * cursor_in[i] (NULL: all BEGIN) says where filter i goes on; only rows at or
+ * after it are scanned, at most scan_rows of them in this call (0: no bound),
+ * base range then tail.  out_cursor[i] is what to pass next:
+ *   - `limit` values were found: the row after the limit-th hit, even when that
+ *     is the end of the rows.  The next call then returns nothing and DONE, as
+ *     the reference returns {ok, [], undefined} after exactly BatchNum rows
+ *     were left;
+ *   - fewer, and the scan reached the end of the tail: DONE;
+ *   - fewer, because scan_rows rows were examined first: the row where the
+ *     window stopped.  A short (even empty) page with a live cursor is legal;
+ *     the caller calls again.
+ * DONE coming in, a literal the dictionary lacks, no rows at or after the
+ * cursor and an invalid filter all give an empty list and DONE.
+ *
+ * Staleness.  Row indices do not move under put, delete, expire or growth; they
+ * move only at a compaction, which bumps the epoch.  A cursor of another epoch
+ * gets out_err[i] = TM_RET_ESTALE, an empty list and out_cursor[i] = BEGIN: the
+ * caller decides whether to start again.  tm_retained_pin keeps the store from
+ * compacting while cursors are open.
+ *
+ * Concurrent writes.  A row written while a cursor is open is seen if it lands
+ * at or after the cursor (a new topic goes to the end of the tail; a replaced or
+ * re-put topic keeps its row) and not otherwise; a row deleted or expired before
+ * the cursor reaches it is not returned.  The reference's ets stream is no
+ * stronger.  now_ms is the caller's on every call: pass the one of the first
+ * call to keep the reference's Now, captured when the stream is built. */
+int tm_retained_match_page(tm_retained *r, uint64_t n, const uint8_t *filter_bytes, const uint64_t *filter_offsets,
+                           uint64_t now_ms, const uint64_t *cursor_in, uint32_t limit, uint64_t scan_rows,
+                           uint64_t *out_hit_offsets, uint32_t *out_values, uint64_t cap, uint64_t *out_cursor,
+                           uint8_t *out_err);
+
+/* Holders of open cursors (emqx_retainer_dispatcher.erl:248-301 holds one from
+ * the first read to delete_cursor).  While the count is above 0 the store does
+ * not compact: a batch of writes flushes and lets the tail pass tail_max, and
+ * tm_retained_compact returns TM_OK with the compaction due.  The
+ * tm_retained_unpin that brings the count to 0 compacts if one is due or the
+ * tail is past tail_max.  An unpin at count 0 is TM_EINVAL.  With no pin held
+ * every other call behaves as it did before ABI minor 25. */
+int tm_retained_pin(tm_retained *r);
+int tm_retained_unpin(tm_retained *r);
 
 /* Last error text of the calling thread from a tm_retained_* call. */
 const char *tm_retained_last_error(tm_retained *r);

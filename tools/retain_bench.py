@@ -2,7 +2,8 @@
 """Retained-message lookup: the device store against the torch composition.
 
     python tools/retain_bench.py --rows 1000000 [--out profiles/retain/bench_1m.jsonl]
-    rocprofv3 --kernel-trace --stats -d DIR -- python tools/retain_bench.py --rows 1000000 --trace full_scan:64
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/retain_bench.py --rows 1000000 --trace full_scan:64 [--page 1000]
+    python tools/retain_bench.py --rows 1000000 --page 1000 [--scan-rows N] [--out profiles/retain/page_1m.jsonl]
 
 Store: `--rows` distinct topics of the C3 workload's topic stream (seeded;
 the stream repeats a few topics, so it is drawn until the store holds that
@@ -24,6 +25,19 @@ slowest repeat beats the composition's fastest.
 The composition, per filter: (nlev == k or nlev >= k) & live & the '$' mask &
 the expiry mask & a conjunction of == over the literal levels' columns, then
 nonzero and a gather of the values.
+
+--page LIMIT measures match cursors instead (tm_retained_match_page): the first
+page of LIMIT values per filter for the classes hash and full_scan at batches
+of 1, 64 and 1,024, one call with one buffer of batch * LIMIT values, against
+tm_retained_match of the same filters (sizing and filling call) in the same
+run, alternating, --repeats times each.  For hash x 1,024 the full list cannot
+be held (1.0e9 values), so that leg is compared against the full match of the
+batch of 64 and says so.  Every page is checked against the full list: its
+length is min(LIMIT, the list's length) and its values are among the list's,
+without a duplicate.  Then one leg of '#' with LIMIT = 65,536 page by page to
+the end against the single full match, the drain's values compared as a sorted
+list.  "Faster" only where the slower side's fastest repeat is slower than the
+other's slowest.
 
 Kernel times are not taken here: --trace CLASS:BATCH runs that leg alone (no
 composition), for a rocprofv3 --kernel-trace --stats run of its own.
@@ -197,6 +211,84 @@ def run_leg(s, cols, topics, cls, batch, args, r):
     return leg
 
 
+def _timed(f):
+    t0 = time.perf_counter()
+    out = f()
+    return time.perf_counter() - t0, out
+
+
+def _verdict(leg, page_t, full_t):
+    leg["page_us"] = [round(x * 1e6, 1) for x in page_t]
+    leg["full_us"] = [round(x * 1e6, 1) for x in full_t]
+    leg["page_faster"] = max(page_t) < min(full_t)
+    leg["full_faster"] = max(full_t) < min(page_t)
+    leg["ratio_p50"] = round(float(np.median(full_t) / np.median(page_t)), 2)
+
+
+def page_leg(s, topics, cls, batch, args, r):
+    """the first page of args.page values per filter against the whole lists of the same filters"""
+    filters = make_filters(topics, cls, batch, r)
+    blob, offs = _native.pack_strings(filters)
+    full_batch = batch
+    leg = {"mode": "first_page", "class": cls, "batch": batch, "limit": args.page, "scan_rows": args.scan_rows,
+           "rows": len(topics)}
+    if cls == "hash" and batch > 64:   # 1.0e9 values: the full list cannot be held
+        full_batch = 64
+        leg["comparator"] = "tm_retained_match of a batch of 64 '#': the full list of %d cannot be held" % batch
+    fblob, foffs = _native.pack_strings(filters[:full_batch])
+    page = lambda: s.match_page_packed(blob, offs, NOW, None, args.page, args.scan_rows)
+    full = lambda: s.match_packed(fblob, foffs, NOW)
+    st0 = s.stats()["match_launches"]
+    hit, vals, cur, err = page()                                 # warm-up, and the check
+    leg["device_calls_per_lookup"] = s.stats()["match_launches"] - st0
+    fhit, fvals, _ = full()
+    assert not err.any()
+    for i in range(full_batch):
+        got, whole = vals[int(hit[i]):int(hit[i + 1])], fvals[int(fhit[i]):int(fhit[i + 1])]
+        if not args.scan_rows:
+            assert len(got) == min(args.page, len(whole)), (cls, batch, i, len(got), len(whole))
+            assert (int(cur[i]) == _native.TM_RET_CURSOR_DONE) == (len(got) < args.page)
+        assert len(np.unique(got)) == len(got) and np.isin(got, whole).all(), (cls, batch, i)
+    leg["page_values"], leg["full_values"] = int(hit[-1]), int(fhit[-1])
+    leg["live_cursors"] = int((cur != np.uint64(_native.TM_RET_CURSOR_DONE)).sum())
+    times, t_end = [], time.perf_counter() + args.window
+    while time.perf_counter() < t_end or len(times) < 5:
+        times.append(_timed(page)[0])
+    leg["page_p50_us"], leg["page_calls"] = round(float(np.median(times)) * 1e6, 1), len(times)
+    pt, ft = [], []
+    for _ in range(args.repeats):
+        pt.append(_timed(page)[0])
+        ft.append(_timed(full)[0])
+    _verdict(leg, pt, ft)
+    leg["outputs_checked"] = True
+    return leg
+
+
+def drain_leg(s, args):
+    """'#' page by page to the end with LIMIT = 65,536 against the single full match"""
+    limit = 65_536
+    blob, offs = _native.pack_strings([b"#"])
+
+    def drain():
+        parts, cur, calls = [], None, 0
+        while cur is None or int(cur[0]) != _native.TM_RET_CURSOR_DONE:
+            hit, vals, cur, _ = s.match_page_packed(blob, offs, NOW, cur, limit, args.scan_rows)
+            parts.append(vals)
+            calls += 1
+        return np.concatenate(parts), calls
+    full = lambda: s.match_packed(blob, offs, NOW)
+    (got, calls), (fhit, fvals, _) = drain(), full()
+    assert np.array_equal(np.sort(got), np.sort(fvals)), (len(got), len(fvals))
+    leg = {"mode": "full_drain", "class": "hash", "batch": 1, "limit": limit, "scan_rows": args.scan_rows,
+           "values": int(len(got)), "calls_per_drain": calls, "outputs_equal": True}
+    dt, ft = [], []
+    for _ in range(args.repeats):
+        dt.append(_timed(drain)[0])
+        ft.append(_timed(full)[0])
+    _verdict(leg, dt, ft)
+    return leg
+
+
 def tail_cost(s, topics, args, r, emit):
     """what a tail of T rows costs every filter, against what one compaction costs"""
     filters = make_filters(topics, "exact", 64, r)
@@ -232,6 +324,9 @@ def main():
     ap.add_argument("--max-hits", type=int, default=80_000_000)
     ap.add_argument("--trace", default=None, help="CLASS:BATCH -- that leg alone, 20 calls, no composition")
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--page", type=int, nargs="?", const=1000, default=None, metavar="LIMIT",
+                    help="match cursors: the first page of LIMIT values (default 1000) against the full match")
+    ap.add_argument("--scan-rows", type=int, default=0, help="with --page: rows a filter examines per call (0: no bound)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     lines = []
@@ -249,9 +344,17 @@ def main():
         filters = make_filters(topics, cls, int(batch), r)
         blob, offs = _native.pack_strings(filters)
         for _ in range(22):
-            hit, _, _ = s.match_packed(blob, offs, NOW)
+            if args.page is not None:                            # (with --page: that leg's first page alone)
+                hit = s.match_page_packed(blob, offs, NOW, None, args.page, args.scan_rows)[0]
+            else:
+                hit, _, _ = s.match_packed(blob, offs, NOW)
         emit({"trace": args.trace, "calls": 22, "hits": int(hit[-1]),
               "scan_bytes_per_pass": scan_bytes(cls, filters, len(topics), int(hit[-1]), 0.1)})
+    elif args.page is not None:
+        for cls in ("hash", "full_scan"):
+            for batch in BATCHES:
+                emit(page_leg(s, topics, cls, batch, args, r))
+        emit(drain_leg(s, args))
     else:
         cols = None if args.no_torch else Columns(topics, expiry)
         for cls in CLASSES:
